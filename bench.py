@@ -2,6 +2,13 @@
 """Headline benchmark: PNEC frame-pair solves/s (512 correspondences, 10 LM iterations).
 
   python bench.py --gpus N --steps K --warmup W [--workload sim100k|kitti_all] [--tracks file.npz]
+                  [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, higher_is_better, dtype,
+ms_per_step).  --full also measures and checks everything beyond that headline, after the timed steps: the roofline
+blocks (with one counted launch), the CPU baseline and its parity, the chain's stage times and one-at-a-time rate, and on
+sim100k with one GPU the `secondary` array (BASELINE configs 3, 4, 5 and the whole chain).  --dump-outputs DIR writes
+the per-pair results of the last timed step as DIR/<name>.npy (float64; a fixed sample of rows beyond 64 MB).
 
 One process per GPU.  Launched under torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE /
 MASTER_* in the environment) it joins that job; launched plainly with --gpus N > 1 it SPAWNS the N
@@ -234,12 +241,17 @@ def parse_args(argv=None):
     ap.add_argument("--cpl", type=int, default=0, help="launch tuning: correspondences per lane")
     ap.add_argument("--wpp", type=int, default=0, help="launch tuning: wavefronts per solve")
     ap.add_argument("--ldsk", type=int, default=0, help="launch tuning: correspondences per lane kept in LDS")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beyond the headline: rooflines, CPU "
+                         "baseline + parity, the chain's stage times, the `secondary` array (off: the plain, lean run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's per-pair results as DIR/<name>.npy (float64, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline (and the secondary array)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="sim100k on one GPU: skip the `secondary` array (BASELINE configs 3, 4, 5 and the whole chain, measured "
-                         "in the same process after the headline)")
+                    help="--full, sim100k on one GPU: skip the `secondary` array (BASELINE configs 3, 4, 5 and the whole chain, "
+                         "measured in the same process after the headline)")
     ap.add_argument("--quick-secondary", action="store_true", help="fewer steps / a shorter stream in the secondary runs (tests)")
-    ap.add_argument("--cpu-sample", type=int, default=0, help="pairs in the CPU baseline sample (0 = auto)")
+    ap.add_argument("--cpu-sample", type=int, default=0, help="--full: pairs in the CPU baseline sample (0 = auto)")
     ap.add_argument("--sync-gather", action="store_true", help="gather on the solve's stream (A/B of the overlap)")
     ap.add_argument("--single-process", action="store_true",
                     help="sim100k: drive all --gpus devices from THIS process through the persistent multi-device handle "
@@ -1098,6 +1110,38 @@ def secondary_lines(device, capi, quick=False):
 
 
 # ---------------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path computed in its last step, so that two builds can be compared output for output
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def record_arrays(rec, chain=False):
+    """The per-pair results a caller of the timed path receives, from the [P, 10] records of pack_records (q, t, cost,
+    iterations, status); --chain steps carry the inlier count in the iterations column and nothing in the others."""
+    rec = np.asarray(rec.detach().cpu() if hasattr(rec, "detach") else rec, dtype=np.float64)
+    out = {"q": rec[:, 0:4], "t": rec[:, 4:7]}
+    if chain:
+        out["inlier_count"] = rec[:, 8]
+    else:
+        out.update(cost=rec[:, 7], iterations=rec[:, 8], status=rec[:, 9])
+    return out
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """Every array as <path>/<name>.npy in float64.  Beyond `limit` bytes in all, the same fixed, seeded sample of rows of
+    each, sorted, and the rows' indices as row_index.npy."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    if sum(a.nbytes for a in arrays.values()) > limit:
+        row = sum(a.nbytes for a in arrays.values()) // max(n, 1) + 8
+        idx = np.sort(np.random.default_rng(0).choice(n, size=(limit - 4096) // row, replace=False))   # (room for the headers)
+        arrays = {k: np.ascontiguousarray(a[idx]) for k, a in arrays.items()}
+        arrays["row_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
+# ---------------------------------------------------------------------------------------------------
 def run(args):
     import torch
     import torch.distributed as dist
@@ -1232,6 +1276,8 @@ def run(args):
     gathered = gather.drain()
     fence()
     elapsed = time.perf_counter() - t_start
+    if args.dump_outputs and rank == 0:   # the gathered records of the last timed step, every rank's pairs in order
+        dump_outputs(args.dump_outputs, record_arrays(gathered, chain=args.chain))
     per_rank = None
     if world > 1:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if args.share_gpu else device)
@@ -1247,7 +1293,7 @@ def run(args):
         per_rank = torch.stack(allr).cpu().numpy()
         elapsed = float(tmax.item())
     one_at_a_time = None
-    if in_flight > 1 and world == 1:   # the same steps one after the other on one stream, for the record
+    if args.full and in_flight > 1 and world == 1:   # the same steps one after the other on one stream, for the record
         which[0] = 0
         t1 = time.perf_counter()
         for _ in range(args.steps):
@@ -1313,10 +1359,6 @@ def run(args):
             if args.workload == "kitti_all":
                 line["config"]["corr_per_rank"] = sh.shard_corr
         elif args.chain:
-            # the chain is a handful of kernels of different character: one roofline block per STAGE.
-            # Also reported: the device time of this rank's shard per step and the inlier statistics of the last step.
-            dev_ms = float(np.mean([a.elapsed_time(b) for a, b in zip(ev0, ev1)]))
-            inl = gathered[:, 8].detach().cpu()
             line["config"].update({"corr_per_rank": sh.shard_corr,
                                    "corr_min_mean_max": [int(sh.pair_sizes.min()), float(sh.pair_sizes.mean()),
                                                          int(sh.pair_sizes.max())],
@@ -1324,56 +1366,31 @@ def run(args):
                                               "weighted_iterations 10 + SCF, Ceres-default refinement"})
             line["config"]["steps_in_flight"] = in_flight
             line["config"]["eigensolver_scheme"] = args.es_scheme
-            sh.batches[0].set_eigensolver_scheme(args.es_scheme)     # (the stage-by-stage calls take the batch's scheme)
-            stage_ms, sres, ssel, sel_payload = chain_stage_times(sh.batches[0], sh.q0, sh.t0)
-            counts = load_chain_counts("kitti_all_chain" + ("" if args.es_scheme == 0 else f"_scheme{args.es_scheme}"),
-                                       sh.total_pairs, int(sh.pair_sizes.sum())) \
-                if (world == 1 and not args.tracks and args.outliers == 0.10) else None
-            line["roofline"] = chain_stage_rooflines(
-                counts, {"ransac_es": stage_ms["ransac_es"] + stage_ms["inlier_extraction"], "weighted_es": stage_ms["weighted_es"]},
-                sh.batches[0].payload_bytes // 2, sel_payload, refinement_roofline(ssel, sres, stage_ms["refinement"], True, capi))
-            line["chain"] = {"device_ms_per_step_rank0": dev_ms, "stage_ms_stage_by_stage_rank0": stage_ms,
-                             "steps_in_flight": in_flight,
-                             "pairs_per_s_one_step_at_a_time": one_at_a_time,
-                             "in_flight_note": "each step in flight runs on its own stream and its own copy of the batch; "
-                                               "device_ms_per_step is one step's span while the others run beside it",
-                             "inlier_share_mean": float((inl / torch.as_tensor(sh.pair_sizes, dtype=torch.float64)).mean()),
-                             "note": "one pnec_hip_solve_pipeline call per step and rank; `roofline` has one block per stage "
-                                     "(stage times from the same chain run stage by stage on rank 0; algorithmic flop from the "
-                                     "committed work counts, profiles/chain_work_latest.json); stage kernels: "
-                                     "profiles/r06_full_pipeline_kernels_scheme2.md"}
+            if args.full:
+                # the chain is a handful of kernels of different character: one roofline block per STAGE.
+                # Also reported: the device time of this rank's shard per step and the inlier statistics of the last step.
+                dev_ms = float(np.mean([a.elapsed_time(b) for a, b in zip(ev0, ev1)]))
+                inl = gathered[:, 8].detach().cpu()
+                sh.batches[0].set_eigensolver_scheme(args.es_scheme)     # (the stage-by-stage calls take the batch's scheme)
+                stage_ms, sres, ssel, sel_payload = chain_stage_times(sh.batches[0], sh.q0, sh.t0)
+                counts = load_chain_counts("kitti_all_chain" + ("" if args.es_scheme == 0 else f"_scheme{args.es_scheme}"),
+                                           sh.total_pairs, int(sh.pair_sizes.sum())) \
+                    if (world == 1 and not args.tracks and args.outliers == 0.10) else None
+                line["roofline"] = chain_stage_rooflines(
+                    counts, {"ransac_es": stage_ms["ransac_es"] + stage_ms["inlier_extraction"], "weighted_es": stage_ms["weighted_es"]},
+                    sh.batches[0].payload_bytes // 2, sel_payload, refinement_roofline(ssel, sres, stage_ms["refinement"], True, capi))
+                line["chain"] = {"device_ms_per_step_rank0": dev_ms, "stage_ms_stage_by_stage_rank0": stage_ms,
+                                 "steps_in_flight": in_flight,
+                                 "pairs_per_s_one_step_at_a_time": one_at_a_time,
+                                 "in_flight_note": "each step in flight runs on its own stream and its own copy of the batch; "
+                                                   "device_ms_per_step is one step's span while the others run beside it",
+                                 "inlier_share_mean": float((inl / torch.as_tensor(sh.pair_sizes, dtype=torch.float64)).mean()),
+                                 "note": "one pnec_hip_solve_pipeline call per step and rank; `roofline` has one block per stage "
+                                         "(stage times from the same chain run stage by stage on rank 0; algorithmic flop from the "
+                                         "committed work counts, profiles/chain_work_latest.json); stage kernels: "
+                                         "profiles/r06_full_pipeline_kernels_scheme2.md"}
         else:
-            step_ms = [a.elapsed_time(b) for a, b in zip(ev0, ev1)]
-            kernel_ms = float(np.mean(step_ms))
-            batch = sh.batch
-            payload = batch.payload_bytes                      # bytes the kernel must read once
             iters_done = res.iterations.to(torch.float64)
-            passes = float(iters_done.mean()) + 1.0 if my_pairs else 0.0   # iteration zero + one per LM iteration
-            achieved_gbs = payload / (kernel_ms * 1e-3) / 1e9
-            corr_passes = batch.num_correspondences * passes
-            if args.workload == "kitti_all" and my_pairs:      # ragged: weight each pair's passes by its size
-                w = torch.as_tensor(np.diff(batch.offsets), dtype=torch.float64, device=iters_done.device)
-                corr_passes = float(((iters_done + 1.0) * w).sum())
-            # a solve that runs into the iteration cap ends with ONE cost-only pass (fixed-count mode: every solve)
-            capped = res.status == capi.TERM_MAX_ITERATIONS
-            cost_corr = 0.0
-            if my_pairs:
-                wts = (torch.as_tensor(np.diff(batch.offsets), dtype=torch.float64, device=iters_done.device)
-                       if args.workload == "kitti_all" else
-                       torch.full_like(iters_done, batch.num_correspondences / max(my_pairs, 1)))
-                cost_corr = float((capped.to(torch.float64) * wts).sum())
-            full_corr = corr_passes - cost_corr
-            # what the kernel EXECUTED: it evaluates a candidate cost-only when it expects the step to be rejected (Ceres'
-            # own order: residuals first, the Jacobian once the step is accepted) -- one counted launch on the same inputs
-            passes_full_if_all_speculated = full_corr
-            full_corr, cost_corr = (float(x) for x in executed_passes(batch, sh.q0, sh.t0, opts, capi, reg=1e-13))
-            valu_tflops = (FLOP_PER_CORR_PASS * full_corr + FLOP_PER_CORR_COST_PASS * cost_corr) / (kernel_ms * 1e-3) / 1e12
-            issue_tflops_equiv = 2 * (VALU_INSTR_PER_CORR_PASS * full_corr + VALU_INSTR_PER_CORR_COST_PASS * cost_corr) \
-                / (kernel_ms * 1e-3) / 1e12
-            key = [args.workload, args.pairs if args.workload == "sim100k" else sh.total_pairs,
-                   args.corr if args.workload == "sim100k" else 0, args.iters if args.workload == "sim100k" else 0,
-                   [launch["corr_per_lane"], launch["waves_per_pair"], launch["lds_corr_per_lane"]]]
-            traffic, valu_busy, why = profiled_counters(capi.LIB_PATH, key)
             line["config"].update({
                 "lm_iterations_done_min_mean_max": [float(iters_done.min()), float(iters_done.mean()),
                                                     float(iters_done.max())] if my_pairs else None,
@@ -1386,57 +1403,88 @@ def run(args):
                 line["config"].update({"corr_per_rank": sh.shard_corr,
                                        "corr_min_mean_max": [int(sh.pair_sizes.min()), float(sh.pair_sizes.mean()),
                                                              int(sh.pair_sizes.max())]})
-            line["roofline"] = {
-                # the contract's block prices the kernel against HBM (bytes it must read once / its duration);
-                # the roof that BINDS this register-resident kernel is FP64 VALU issue: see bound_binding / 'valu'
-                "bound": "hbm", "bound_binding": "valu_fp64",
-                "binding_frac": valu_tflops / FP64_VALU_PEAK_TFLOPS,
-                "kernel": "lm_solve_kernel<TARGET>", "rank": 0,
-                "achieved": achieved_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved_gbs / HBM_PEAK_GBS, "traffic": traffic, "traffic_note": why,
-                "kernel_ms": kernel_ms,
-                # the spread over the K timed launches: a box whose clocks move shows here (round 6: two boxes at 2.72 ms, one at
-                # 3.03 ms mean whose rocprofv3 trace of the same command read 2.72 min / 2.90 mean); `achieved` / `frac` use the
-                # MEAN, as the contract says
-                "kernel_ms_min_median_max": [float(np.min(step_ms)), float(np.median(step_ms)), float(np.max(step_ms))],
-                "algorithmic_bytes_per_launch": payload,
-                "note": "register-resident design: the payload (96 B/correspondence) is read from HBM "
-                        "once per solve, not once per pass, so the kernel is FP64-VALU-bound, not "
-                        "HBM-bound; see 'valu' for the binding roof and DESIGN.md",
-                # SURVEY.md 8(d) quotes the streaming model (N x 96 B x passes per solve); against it:
-                "streaming_equivalent_GBs": achieved_gbs * passes,
-                "streaming_equivalent_frac": achieved_gbs * passes / HBM_PEAK_GBS,
-                "valu": {"bound": "valu_fp64", "achieved": valu_tflops, "peak": FP64_VALU_PEAK_TFLOPS,
-                         "unit": "TFLOP/s", "frac": valu_tflops / FP64_VALU_PEAK_TFLOPS,
-                         "flop_per_corr_pass": FLOP_PER_CORR_PASS, "passes": passes,
-                         "cost_only_passes_per_solve": (cost_corr / batch.num_correspondences) if batch.num_correspondences else 0.0,
-                         "flop_per_corr_cost_only_pass": FLOP_PER_CORR_COST_PASS,
-                         "flop_note": "62 FMA + 28 MUL + 1 rsq per correspondence per full pass = 153 flop in 91 issue slots; "
-                                      "a cost-only pass (after a rejected step, at the iteration cap): 67 flop in 43 slots; "
-                                      "the flop counted are those of the passes the kernel executed (a counted launch)",
-                         "correspondence_passes_executed": {"full": full_corr, "cost_only": cost_corr,
-                                                            "full_if_every_candidate_got_its_jacobian": passes_full_if_all_speculated},
-                         # the same work priced in issue slots (every VALU instruction = one FMA-sized slot)
-                         "issue_slot_frac_useful": issue_tflops_equiv / FP64_VALU_PEAK_TFLOPS,
-                         # share of cycles the vector ALU was issuing (any FP64/integer/cross-lane
-                         # instruction, useful or bookkeeping), from the committed rocprofv3 SQ counters
-                         "issue_busy_frac_profiled": valu_busy},
-            }
-            if not args.no_cpu_baseline and world == 1 and sh.sample is not None:
-                from oracle import pnec_oracle as po
-                cores = po.max_threads()
-                avail = len(sh.sample[0]) - 1
-                n_sample = args.cpu_sample or int(min(avail, max(64, 32 * cores)))
-                base, parity = cpu_baseline(sh.sample, n_sample, opts, res.q)
-                line["cpu_baseline"] = base
-                line["parity"] = parity
-            if args.workload == "sim100k" and world == 1 and not args.no_secondary and not args.no_cpu_baseline:
-                # the other configs + the chain, on this GPU, after the headline's timed region (the headline's batch is
-                # released first: nothing of it is timed any more)
-                sh.batch.close()
-                t_sec = time.perf_counter()
-                line["secondary"] = secondary_lines(device, capi, quick=args.quick_secondary)
-                line["secondary_wall_s"] = time.perf_counter() - t_sec
+            if args.full:
+                step_ms = [a.elapsed_time(b) for a, b in zip(ev0, ev1)]
+                kernel_ms = float(np.mean(step_ms))
+                batch = sh.batch
+                payload = batch.payload_bytes                      # bytes the kernel must read once
+                passes = float(iters_done.mean()) + 1.0 if my_pairs else 0.0   # iteration zero + one per LM iteration
+                achieved_gbs = payload / (kernel_ms * 1e-3) / 1e9
+                corr_passes = batch.num_correspondences * passes
+                if args.workload == "kitti_all" and my_pairs:      # ragged: weight each pair's passes by its size
+                    w = torch.as_tensor(np.diff(batch.offsets), dtype=torch.float64, device=iters_done.device)
+                    corr_passes = float(((iters_done + 1.0) * w).sum())
+                # a solve that runs into the iteration cap ends with ONE cost-only pass (fixed-count mode: every solve)
+                capped = res.status == capi.TERM_MAX_ITERATIONS
+                cost_corr = 0.0
+                if my_pairs:
+                    wts = (torch.as_tensor(np.diff(batch.offsets), dtype=torch.float64, device=iters_done.device)
+                           if args.workload == "kitti_all" else
+                           torch.full_like(iters_done, batch.num_correspondences / max(my_pairs, 1)))
+                    cost_corr = float((capped.to(torch.float64) * wts).sum())
+                full_corr = corr_passes - cost_corr
+                # what the kernel EXECUTED: it evaluates a candidate cost-only when it expects the step to be rejected (Ceres'
+                # own order: residuals first, the Jacobian once the step is accepted) -- one counted launch on the same inputs
+                passes_full_if_all_speculated = full_corr
+                full_corr, cost_corr = (float(x) for x in executed_passes(batch, sh.q0, sh.t0, opts, capi, reg=1e-13))
+                valu_tflops = (FLOP_PER_CORR_PASS * full_corr + FLOP_PER_CORR_COST_PASS * cost_corr) / (kernel_ms * 1e-3) / 1e12
+                issue_tflops_equiv = 2 * (VALU_INSTR_PER_CORR_PASS * full_corr + VALU_INSTR_PER_CORR_COST_PASS * cost_corr) \
+                    / (kernel_ms * 1e-3) / 1e12
+                key = [args.workload, args.pairs if args.workload == "sim100k" else sh.total_pairs,
+                       args.corr if args.workload == "sim100k" else 0, args.iters if args.workload == "sim100k" else 0,
+                       [launch["corr_per_lane"], launch["waves_per_pair"], launch["lds_corr_per_lane"]]]
+                traffic, valu_busy, why = profiled_counters(capi.LIB_PATH, key)
+                line["roofline"] = {
+                    # the contract's block prices the kernel against HBM (bytes it must read once / its duration);
+                    # the roof that BINDS this register-resident kernel is FP64 VALU issue: see bound_binding / 'valu'
+                    "bound": "hbm", "bound_binding": "valu_fp64",
+                    "binding_frac": valu_tflops / FP64_VALU_PEAK_TFLOPS,
+                    "kernel": "lm_solve_kernel<TARGET>", "rank": 0,
+                    "achieved": achieved_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": achieved_gbs / HBM_PEAK_GBS, "traffic": traffic, "traffic_note": why,
+                    "kernel_ms": kernel_ms,
+                    # the spread over the K timed launches: a box whose clocks move shows here (round 6: two boxes at 2.72 ms, one at
+                    # 3.03 ms mean whose rocprofv3 trace of the same command read 2.72 min / 2.90 mean); `achieved` / `frac` use the
+                    # MEAN, as the contract says
+                    "kernel_ms_min_median_max": [float(np.min(step_ms)), float(np.median(step_ms)), float(np.max(step_ms))],
+                    "algorithmic_bytes_per_launch": payload,
+                    "note": "register-resident design: the payload (96 B/correspondence) is read from HBM "
+                            "once per solve, not once per pass, so the kernel is FP64-VALU-bound, not "
+                            "HBM-bound; see 'valu' for the binding roof and DESIGN.md",
+                    # SURVEY.md 8(d) quotes the streaming model (N x 96 B x passes per solve); against it:
+                    "streaming_equivalent_GBs": achieved_gbs * passes,
+                    "streaming_equivalent_frac": achieved_gbs * passes / HBM_PEAK_GBS,
+                    "valu": {"bound": "valu_fp64", "achieved": valu_tflops, "peak": FP64_VALU_PEAK_TFLOPS,
+                             "unit": "TFLOP/s", "frac": valu_tflops / FP64_VALU_PEAK_TFLOPS,
+                             "flop_per_corr_pass": FLOP_PER_CORR_PASS, "passes": passes,
+                             "cost_only_passes_per_solve": (cost_corr / batch.num_correspondences) if batch.num_correspondences else 0.0,
+                             "flop_per_corr_cost_only_pass": FLOP_PER_CORR_COST_PASS,
+                             "flop_note": "62 FMA + 28 MUL + 1 rsq per correspondence per full pass = 153 flop in 91 issue slots; "
+                                          "a cost-only pass (after a rejected step, at the iteration cap): 67 flop in 43 slots; "
+                                          "the flop counted are those of the passes the kernel executed (a counted launch)",
+                             "correspondence_passes_executed": {"full": full_corr, "cost_only": cost_corr,
+                                                                "full_if_every_candidate_got_its_jacobian": passes_full_if_all_speculated},
+                             # the same work priced in issue slots (every VALU instruction = one FMA-sized slot)
+                             "issue_slot_frac_useful": issue_tflops_equiv / FP64_VALU_PEAK_TFLOPS,
+                             # share of cycles the vector ALU was issuing (any FP64/integer/cross-lane
+                             # instruction, useful or bookkeeping), from the committed rocprofv3 SQ counters
+                             "issue_busy_frac_profiled": valu_busy},
+                }
+                if not args.no_cpu_baseline and world == 1 and sh.sample is not None:
+                    from oracle import pnec_oracle as po
+                    cores = po.max_threads()
+                    avail = len(sh.sample[0]) - 1
+                    n_sample = args.cpu_sample or int(min(avail, max(64, 32 * cores)))
+                    base, parity = cpu_baseline(sh.sample, n_sample, opts, res.q)
+                    line["cpu_baseline"] = base
+                    line["parity"] = parity
+                if args.workload == "sim100k" and world == 1 and not args.no_secondary and not args.no_cpu_baseline:
+                    # the other configs + the chain, on this GPU, after the headline's timed region (the headline's batch is
+                    # released first: nothing of it is timed any more)
+                    sh.batch.close()
+                    t_sec = time.perf_counter()
+                    line["secondary"] = secondary_lines(device, capi, quick=args.quick_secondary)
+                    line["secondary_wall_s"] = time.perf_counter() - t_sec
         print(json.dumps(line), flush=True)
 
     if world > 1:
@@ -1487,6 +1535,8 @@ def run_single_process(args):
             for _ in range(args.steps):
                 rec = one()
             wall = (time.perf_counter() - t_0) / args.steps * 1e3
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, record_arrays(rec, chain=args.chain))
             bounds = mb.bounds.tolist()
         line = {"metric": ("PNEC::Solve frame pairs/sec, whole chain (all KITTI 00-10 pairs, ragged, reference-default Options)" if args.chain
                            else "PNEC pose solves/sec (all KITTI 00-10 pairs, ragged, Ceres-default termination)"),
@@ -1523,6 +1573,8 @@ def run_single_process(args):
             res = mb.solve(q0, t0, options=opts)
         wall = (time.perf_counter() - t_0) / args.steps * 1e3
         a1 = alloc_counters()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {k: res[k] for k in ("q", "t", "cost", "iterations", "status")})
         bounds = mb.bounds.tolist()
     line = {"metric": "PNEC pose solves/sec (512 corr, 10 GN iters)", "value": P / (wall * 1e-3), "unit": "solves/s", "n_gpus": N, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": wall, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,

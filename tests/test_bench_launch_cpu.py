@@ -148,7 +148,7 @@ def test_profiled_counters_are_dropped_when_the_device_code_changed(tmp_path, mo
         "profiles/traffic_latest.json is stale: re-run tools/profile_bench.sh + tools/make_traffic_json.py"
 
 
-def test_front_flop_model_and_work_counts_belong_to_the_committed_front_stage_code():
+def test_front_flop_model_and_work_counts_belong_to_the_committed_front_stage_code(tmp_path):
     """The chain's stage rooflines multiply committed work counts (profiles/chain_work_latest.json, a -DPNEC_WORK_COUNT run) by
     a flop table in bench.py: both carry the sha256 of the front-stage sources they were made on, a line never uses stale
     counts, and the commit fails here when pnec_frontend.hip moves on without them (the table priced a
@@ -163,7 +163,7 @@ def test_front_flop_model_and_work_counts_belong_to_the_committed_front_stage_co
         "bench.py's FLOP_* table was derived on other front-stage code: re-derive it (tools/isa_front_regions.py) and re-stamp"
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import isa_front_regions
-    r = isa_front_regions.count()
+    r = isa_front_regions.count(out=str(tmp_path / "isa_front_probe.s"))   # (a scratch file of this test's own)
     straight = r["cayley"]["flop"] + r["m"]["flop"] + (r["with_gradient"]["flop"] - r["value_only"]["flop"])
     model = 47 + 339 + 292
     # (the gradient is read as a difference of two compilations: the value-only one also drops the eigenVECTOR's last
@@ -244,3 +244,42 @@ def test_world_size_8_dry_run_of_the_chain_workload_as_the_driver_launches_it():
     d1 = _run([sys.executable, BENCH, "--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "kitti_all", "--chain",
                "--dry-run-cpu"], env)
     assert d1["config"]["pairs_per_rank"] == [23190]
+
+
+def test_dump_outputs_writes_the_last_timed_steps_records(tmp_path):
+    """--dump-outputs DIR: the per-pair results of the LAST timed step as DIR/<name>.npy in float64, every rank's pairs in
+    order, the very records the line's digest is taken of (here the stub's: global pair index, step stamp, owner)."""
+    import hashlib
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = tmp_path / "out"
+    d = _run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--pairs", "500", "--dry-run-cpu",
+              "--dump-outputs", str(out)], env)
+    got = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    assert sorted(got) == ["cost", "iterations", "q", "status", "t"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["q"].shape == (1000, 4) and got["t"].shape == (1000, 3)
+    np.testing.assert_array_equal(got["cost"], np.arange(1000))               # the global pair index, in order
+    assert (got["iterations"] == 1 + 3 + 1).all()                              # warm-up + set-up step + the 3 timed ones
+    np.testing.assert_array_equal(got["status"], np.repeat([0.0, 1.0], 500))  # the owning rank
+    rec = np.concatenate([got["q"], got["t"]] + [got[k][:, None] for k in ("cost", "iterations", "status")], axis=1)
+    assert hashlib.sha256(rec.tobytes()).hexdigest() == d["records_sha256"]
+
+
+def test_dump_outputs_beyond_the_limit_is_a_fixed_sample_of_rows(tmp_path):
+    """An output larger than the limit is dumped as the same seeded sample of rows in every array (indices in
+    row_index.npy), within the limit, and the same sample from run to run."""
+    sys.path.insert(0, ROOT)
+    import bench
+    rec = np.random.default_rng(4).normal(size=(20000, 10))
+    for k in (0, 1):
+        bench.dump_outputs(str(tmp_path / str(k)), bench.record_arrays(rec), limit=200_000)
+    files = sorted(os.listdir(tmp_path / "0"))
+    assert files == ["cost.npy", "iterations.npy", "q.npy", "row_index.npy", "status.npy", "t.npy"]
+    assert sum(os.path.getsize(tmp_path / "0" / f) for f in files) <= 200_000
+    idx = np.load(tmp_path / "0" / "row_index.npy")
+    assert idx.dtype == np.float64 and len(idx) > 1000 and (np.diff(idx) > 0).all()
+    rows = idx.astype(np.int64)
+    np.testing.assert_array_equal(np.load(tmp_path / "0" / "q.npy"), rec[rows, 0:4])
+    np.testing.assert_array_equal(np.load(tmp_path / "0" / "status.npy"), rec[rows, 9])
+    for f in files:
+        np.testing.assert_array_equal(np.load(tmp_path / "0" / f), np.load(tmp_path / "1" / f))

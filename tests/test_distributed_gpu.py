@@ -154,8 +154,8 @@ def test_bench_two_ranks_share_the_gpu_config5_device_side_gather():
 def test_bench_chain_workload_two_ranks_share_the_gpu():
     """config 5 with something to scale: the whole PNEC::Solve chain per pair (`--chain`), two ranks on one GPU
     against one rank: same gathered records"""
-    two = _run_bench(["--gpus", "2", "--share-gpu", "--workload", "kitti_all", "--chain", "--steps", "2", "--warmup", "1"])
-    one = _run_bench(["--gpus", "1", "--workload", "kitti_all", "--chain", "--steps", "2", "--warmup", "1"])
+    two = _run_bench(["--gpus", "2", "--share-gpu", "--workload", "kitti_all", "--chain", "--steps", "2", "--warmup", "1", "--full"])
+    one = _run_bench(["--gpus", "1", "--workload", "kitti_all", "--chain", "--steps", "2", "--warmup", "1", "--full"])
     assert two["unit"] == one["unit"] == "pairs/s" and "chain" in two
     # one roofline block per stage (round 4); the work counts behind the flop figures belong to the one-rank synthetic set
     assert [b["bound"] for b in one["roofline"]] == ["valu_fp64", "valu_fp64", "hbm"] and one["roofline"][0]["frac"] is not None
@@ -164,7 +164,8 @@ def test_bench_chain_workload_two_ranks_share_the_gpu():
     assert two["records_sha256"] == one["records_sha256"]
     # ... and steps in flight (each on its own stream and copy of the batch; the default is three) against one at a time
     assert one["chain"]["steps_in_flight"] == 3 and one["chain"]["pairs_per_s_one_step_at_a_time"] > 0
-    seq = _run_bench(["--gpus", "1", "--workload", "kitti_all", "--chain", "--steps", "2", "--warmup", "1", "--in-flight", "1"])
+    seq = _run_bench(["--gpus", "1", "--workload", "kitti_all", "--chain", "--steps", "2", "--warmup", "1", "--in-flight", "1",
+                      "--full"])
     assert seq["chain"]["steps_in_flight"] == 1 and seq["records_sha256"] == one["records_sha256"]
 
 
@@ -265,13 +266,13 @@ def test_one_process_multi_device_entry_equals_the_single_device_call():
 
 
 def test_default_bench_line_carries_the_other_configs_and_the_chain():
-    """`python bench.py` on one GPU (what the driver runs): besides the headline the ONE JSON line has a `secondary` array
+    """`python bench.py --full` on one GPU: besides the headline the ONE JSON line has a `secondary` array
     -- BASELINE configs 3, 4, 5 and the whole PNEC::Solve chain, measured in the same process -- each with value, unit,
     ms_per_step, roofline and parity, none of them failed, parity within the north star's tolerance, the chain entry with
     one roofline block per stage (run here with fewer steps and a shorter headline batch)."""
     import json
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--pairs", "20000",
-                        "--quick-secondary", "--cpu-sample", "64"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--full", "--quick-secondary", "--cpu-sample", "64"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["metric"].startswith("PNEC pose solves/sec") and line["value"] > 1e6 and "roofline" in line and "cpu_baseline" in line
@@ -285,6 +286,35 @@ def test_default_bench_line_carries_the_other_configs_and_the_chain():
     assert chain["parity"]["inlier_masks_identical"] and [b["bound"] for b in chain["roofline"]] == ["valu_fp64", "valu_fp64", "hbm"]
     assert all(b["frac"] is not None and 0 < b["frac"] < 1 for b in chain["roofline"])
     assert chain["value"] >= chain["pairs_per_s_one_call_at_a_time"] * 0.9
+
+
+def test_plain_bench_run_is_lean_and_dumps_what_it_timed(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` prints the contract's line and nothing that takes runs of its own
+    (rooflines, CPU baseline, secondary: --full); --dump-outputs writes the last timed step's results -- the records the
+    line's digest is taken of -- and two runs with the same arguments write the same arrays bit for bit."""
+    import hashlib
+    import json
+
+    import numpy as np
+    outs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
+                            "--pairs", "20000", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 4 and line["warmup"] == 2 and line["unit"] == "solves/s" and line["dtype"] == "f64"
+        assert line["higher_is_better"] is True and line["value"] > 1e6
+        assert line["value"] * line["ms_per_step"] * 1e-3 == pytest.approx(20000)
+        assert not {"roofline", "cpu_baseline", "parity", "secondary"} & set(line), sorted(line)
+        got = {n: np.load(d / f"{n}.npy") for n in ("q", "t", "cost", "iterations", "status")}
+        assert got["q"].shape == (20000, 4) and all(a.dtype == np.float64 for a in got.values())
+        assert (got["iterations"] == 10).all()
+        rec = np.concatenate([got["q"], got["t"]] + [got[n][:, None] for n in ("cost", "iterations", "status")], axis=1)
+        assert hashlib.sha256(rec.tobytes()).hexdigest() == line["records_sha256"]
+        outs.append(got)
+    for n in outs[0]:
+        np.testing.assert_array_equal(outs[0][n], outs[1][n])
 
 
 def test_persistent_multi_device_handle_is_bitwise_the_single_device_calls_and_allocates_nothing(oracle):

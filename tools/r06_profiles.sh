@@ -7,7 +7,7 @@ QUICK=${1:-}
 mkdir -p $OUT
 cd $REPO
 # 1. the headline: bench line, kernel trace + PMC passes (HBM traffic, SQ counters)
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 bash tools/profile_bench.sh r06 > $OUT/profile_bench.log 2>&1
 # 2. the chain: stage timings per eigensolver scheme; kernel trace + SQ counters of the front kernels under the facade's
 #    default scheme (2) AND under the C ABI's (0)
@@ -24,11 +24,11 @@ if [ -z "$QUICK" ]; then
 python tools/bench_pipeline.py 100000 512 2 > $OUT/pipeline_100k.json 2> /dev/null
 PNEC_ES_SCHEME=2 python tools/bench_pipeline_kitti.py > $OUT/pipeline_kitti.json 2> /dev/null
 # 4. other bench lines
-python bench.py --workload kitti_all --steps 50 --warmup 10 > $OUT/bench_kitti.json 2> /dev/null
-python bench.py --workload kitti_all --chain --steps 30 --warmup 5 > $OUT/bench_kitti_chain.json 2> /dev/null
-python bench.py --workload kitti_all --chain --es-scheme 0 --steps 30 --warmup 5 > $OUT/bench_kitti_chain_scheme0.json 2> /dev/null
-python bench.py --workload kitti_all --chain --steps 30 --warmup 5 --in-flight 1 > $OUT/bench_kitti_chain_1.json 2> /dev/null
-python bench.py --gpus 2 --share-gpu --workload kitti_all --chain --steps 10 --warmup 3 > $OUT/bench_kitti_chain_2ranks.json 2> /dev/null
+python bench.py --full --workload kitti_all --steps 50 --warmup 10 > $OUT/bench_kitti.json 2> /dev/null
+python bench.py --full --workload kitti_all --chain --steps 30 --warmup 5 > $OUT/bench_kitti_chain.json 2> /dev/null
+python bench.py --full --workload kitti_all --chain --es-scheme 0 --steps 30 --warmup 5 > $OUT/bench_kitti_chain_scheme0.json 2> /dev/null
+python bench.py --full --workload kitti_all --chain --steps 30 --warmup 5 --in-flight 1 > $OUT/bench_kitti_chain_1.json 2> /dev/null
+python bench.py --full --gpus 2 --share-gpu --workload kitti_all --chain --steps 10 --warmup 3 > $OUT/bench_kitti_chain_2ranks.json 2> /dev/null
 python bench.py --gpus 2 --share-gpu --single-process --pairs 50000 --steps 10 --warmup 3 > $OUT/bench_single_process_2x.json 2> /dev/null
 python bench.py --gpus 1 --single-process --pairs 100000 --steps 10 --warmup 3 > $OUT/bench_single_process_1x.json 2> /dev/null
 # 5. residual families with roofline blocks
