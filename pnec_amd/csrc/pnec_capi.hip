@@ -5,6 +5,7 @@
 #include <thread>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -729,6 +730,16 @@ __global__ __launch_bounds__(1024) void offsets_scan_kernel(const int32_t *__res
 }
 
 // ---- device self-test kernels (cross-lane reduction, 5x5 solve) ---------------------------
+// edge arguments of atan2_c / acos_lean (start_angles' start poses on the axes and the seam)
+constexpr int kAtan2Edges = 26, kAcosEdges = 6, kEdgeOut = 344;
+__host__ __device__ constexpr double kAtan2EdgeY[kAtan2Edges] = {
+    0.0, -0.0, 0.0, -0.0, 0.0, -0.0, 0.0, -0.0, 1.0, 1.0, -1.0, -1.0, 0.0, -0.0, 1e-300, -1e-300,
+    1.2246467991473532e-16, -1.2246467991473532e-16, 1.0, -1.0, 1.0, -1.0, 1e-12, -1e-12, 0.0, -0.0};
+__host__ __device__ constexpr double kAtan2EdgeX[kAtan2Edges] = {
+    0.0, 0.0, -0.0, -0.0, -1.0, -1.0, 1.0, 1.0, 0.0, -0.0, 0.0, -0.0, -2.5, -0.3, -1.0, -1.0,
+    -1.0, -1.0, -1.0, -1.0, 1.0, 1.0, -1.0, -1.0, 1e-300, -1e-300};
+__host__ __device__ constexpr double kAcosEdge[kAcosEdges] = {1.0, -1.0, 0.0, -0.0, 1.0 - 0x1p-53, -1.0 + 0x1p-53};
+
 __global__ void selftest_kernel(double *out) {
   const int lane = threadIdx.x;
   // sum of (lane+1)^2 over 64 lanes = 89440; every lane must hold it
@@ -811,6 +822,10 @@ __global__ void selftest_kernel(double *out) {
     }
     out[152 + lane] = worst_a;
   }
+  // atan2_c / acos_lean at the signed zeros, the axes and the +-pi seam, where C fixes the sign of the result too
+  // (the host compares value AND sign bit with its own libm: pnec_hip_selftest)
+  if (lane < kAtan2Edges) out[kEdgeOut + lane] = atan2_c(kAtan2EdgeY[lane], kAtan2EdgeX[lane]);
+  else if (lane < kAtan2Edges + kAcosEdges) out[kEdgeOut + lane] = acos_lean(kAcosEdge[lane - kAtan2Edges]);
   // bounded sincos against libm over [-40, 40]
   double worst = 0.0;
   for (int k = 0; k < 64; ++k) {
@@ -2211,11 +2226,13 @@ int pnec_hip_selftest(int device) {
     }
   }
   double *d = nullptr;
-  PNEC_HIP_TRY(dev_alloc(&d, sizeof(double) * 352));
+  constexpr int kSelfOut = kEdgeOut + kAtan2Edges + kAcosEdges;
+  static_assert(kAtan2Edges + kAcosEdges <= kWave, "one edge case per lane");
+  PNEC_HIP_TRY(dev_alloc(&d, sizeof(double) * kSelfOut));
   hipLaunchKernelGGL(selftest_kernel, dim3(1), dim3(kWave), 0, 0, d);
-  double h[352];
+  double h[kSelfOut];
   hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpy(h, d, sizeof(double) * 344, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(h, d, sizeof(double) * kSelfOut, hipMemcpyDeviceToHost);
   (void)dev_free(d);
   if (e != hipSuccess) return fail_hip(e, "selftest_kernel");
   for (int i = 0; i < kWave; ++i)
@@ -2257,6 +2274,20 @@ int pnec_hip_selftest(int device) {
       std::snprintf(buf, sizeof(buf), "acos_lean / atan2_lean deviate from libm by %.3g", h[152 + i]);
       return fail(PNEC_HIP_ERR_HIP_RUNTIME, buf);
     }
+  for (int i = 0; i < kAtan2Edges + kAcosEdges; ++i) {
+    const bool is_atan2 = i < kAtan2Edges;
+    const double want = is_atan2 ? std::atan2(kAtan2EdgeY[i], kAtan2EdgeX[i]) : std::acos(kAcosEdge[i - kAtan2Edges]);
+    const double got = h[kEdgeOut + i];
+    if (std::signbit(got) != std::signbit(want) || !(std::abs(got - want) <= 9e-16 * std::abs(want))) {
+      char buf[192];
+      if (is_atan2)
+        std::snprintf(buf, sizeof(buf), "atan2_c(%.17g, %.17g) = %.17g, libm %.17g", kAtan2EdgeY[i], kAtan2EdgeX[i],
+                      got, want);
+      else
+        std::snprintf(buf, sizeof(buf), "acos_lean(%.17g) = %.17g, libm %.17g", kAcosEdge[i - kAtan2Edges], got, want);
+      return fail(PNEC_HIP_ERR_HIP_RUNTIME, buf);
+    }
+  }
   return 0;
 }
 

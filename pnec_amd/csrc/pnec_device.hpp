@@ -156,7 +156,7 @@ __device__ __forceinline__ double atan_lean(double x) {
 // atan2 for finite arguments (the callers pass components of a unit vector)
 __device__ __forceinline__ double atan2_lean(double y, double x) {
   const double kPi = 3.14159265358979311600e+00, kPiLo = 1.2246467991473531772e-16;
-  if (x == 0.0 && y == 0.0) return 0.0;  // the +-0 / pi cases of libm: sign of x (callers never need -0)
+  if (x == 0.0 && y == 0.0) return 0.0;  // NOT libm's +-0 / +-pi here: atan2_c (pnec_solve_kernel.hpp) has them
   if (x == 0.0) return y > 0.0 ? 0.5 * kPi : -0.5 * kPi;
   const double a = atan_lean(fabs(y / x));
   double res = x > 0.0 ? a : kPi - (a - kPiLo);
@@ -502,7 +502,8 @@ __device__ __forceinline__ void make_uniforms(double theta, double phi, const do
   U.bph[0] = to_sgpr(-st * sp); U.bph[1] = to_sgpr(st * cp); U.bph[2] = 0.0;
 }
 
-// common.cc:103-116 (AnglesFromVec)
+// common.cc:103-116 (AnglesFromVec) without C's signed zeros (atan2_lean above): the solve kernels start
+// from start_angles (pnec_solve_kernel.hpp), which has them
 __device__ __forceinline__ void angles_from_vec(double x, double y, double z, double &theta,
                                                 double &phi) {
   const double n = sqrt(x * x + y * y + z * z);

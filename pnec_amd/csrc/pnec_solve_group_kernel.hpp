@@ -99,7 +99,7 @@ __global__ __launch_bounds__(kWave *WPP, (CPL == 8 && LDSK == 0) ? 1 : 2) void l
       const int64_t s = pair * a.n_hyp + h0 + h;
       double th, ph;
       const double *t0 = a.hyp_t ? a.hyp_t + 3 * s : a.init_t + 3 * pair;
-      angles_from_vec(t0[0], t0[1], t0[2], th, ph);
+      start_angles(t0[0], t0[1], t0[2], th, ph);
       double q[4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -262,7 +262,7 @@ __global__ __launch_bounds__(kWave, (CPL == 8 && LDSK == 0) ? 1 : 2) void lm_sol
       const int64_t s = pair * a.n_hyp + h0 + h;
       double th, ph;
       const double *t0 = a.hyp_t ? a.hyp_t + 3 * s : a.init_t + 3 * pair;
-      angles_from_vec(t0[0], t0[1], t0[2], th, ph);
+      start_angles(t0[0], t0[1], t0[2], th, ph);
       double q[4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) {

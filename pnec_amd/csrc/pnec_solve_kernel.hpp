@@ -160,6 +160,25 @@ __host__ __device__ constexpr bool geometry_ok(int mode, int cpl, int wpp, int l
 
 
 // ---- shared by the solve kernels -------------------------------------------------------------
+// atan2 with C's signed zeros, which the reference's AnglesFromVec gets from std::atan2: for y = +-0 the
+// result is +-0 (x > 0 or x = +0) or +-pi (x < 0 or x = -0); otherwise atan2_lean's.  A start
+// t0 = (-0.0, 0, -1) lands on phi = pi and t0 = (-1, -0.0, z) on phi = -pi, as in the reference.
+__device__ __forceinline__ double atan2_c(double y, double x) {
+  if (y == 0.0) return copysign(signbit(x) ? 3.14159265358979311600e+00 : 0.0, y);
+  return atan2_lean(y, x);
+}
+// PNECCeres::InitValues' AnglesFromVec (common.cc:103-116), C semantics at the axes and the phi = +-pi seam
+__device__ __forceinline__ void start_angles(double x, double y, double z, double &theta, double &phi) {
+  const double n = sqrt(x * x + y * y + z * z);
+  if (n == 0.0) {
+    theta = 0.0;
+    phi = 0.0;
+    return;
+  }
+  theta = acos_lean(z / n);
+  phi = (fabs(theta) < 1e-10) ? 0.0 : atan2_c(y / n, x / n);
+}
+
 // Which correspondence a lane's slot k holds (relative to the wavefront's first): the REGK register
 // slots come in pairs (2j, 2j+1) <-> 128 j + 2 lane + {0, 1} -- two neighbouring correspondences per
 // 16-byte load, the CU's load path moving ~2x the bytes per clock of 8-byte loads -- a leftover odd
@@ -1167,7 +1186,7 @@ __global__ __launch_bounds__(kWave *(SRC == SRC_DUAL ? 2 : WPP), (CPL == 8 && LD
   if (lane == 0 && (WPP == 1 || wave == 0)) {
     double th, ph;
     const double *t0 = a.hyp_t ? a.hyp_t + 3 * s : a.init_t + 3 * pair;
-    angles_from_vec(t0[0], t0[1], t0[2], th, ph);
+    start_angles(t0[0], t0[1], t0[2], th, ph);
     double q[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {

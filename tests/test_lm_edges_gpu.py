@@ -1,0 +1,468 @@
+"""The LM solve (lm_solve_kernel and its group / pair-hypothesis twins) against the oracle where
+tests drawing from `sim.generate`'s defaults never go: every launch geometry of every residual
+family, and inputs at the edges -- start translations on the chart's axes and seam (signed zeros
+included), large rotations, quaternion sign and scale, covariance magnitudes, the epipole at
+reg = 0, noise-free and omnidirectional data, pure rotation.
+
+Bars, unless a case says otherwise (the analytic-Jacobian twin runs the kernel's own algorithm):
+equal iteration counts and termination codes, rotation <= 1e-9 rad, cost within rtol 1e-9,
+|t . t_oracle| > 1 - 1e-10.  Against the central-difference (reference-faithful) path: rotation
+<= 1e-6 rad with equal counts and codes.
+"""
+import math
+
+import numpy as np
+import pytest
+
+from pnec_amd import Batch, capi
+from pnec_amd import simulation as sim
+
+pytestmark = pytest.mark.gpu
+
+NEC, TARGET, HOST, SYM = capi.MODE_NEC, capi.MODE_TARGET, capi.MODE_HOST, capi.MODE_SYM
+FAMILIES = [NEC, TARGET, HOST, SYM]
+FAMILY_IDS = ["NEC", "TARGET", "HOST", "SYM"]
+BAD_INITIAL = 6   # PNEC_HIP_TERM_BAD_INITIAL / PNEC_ORACLE_TERM_BAD_INITIAL
+
+# The auto-tuner's ladders (pnec_capi.hip geometry_ladder, batch path), smallest capacity first;
+# beyond the last rung the streaming kernel runs.
+LADDER = {
+    NEC: [(1, 1, 0), (2, 1, 0), (4, 1, 0), (8, 1, 0), (12, 1, 3), (8, 2, 3), (8, 4, 3), (8, 8, 3)],
+    TARGET: [(1, 1, 0), (2, 1, 0), (4, 1, 0), (8, 1, 3), (12, 1, 3), (8, 2, 3), (8, 4, 3), (8, 8, 3)],
+    HOST: [(1, 1, 0), (2, 1, 0), (4, 1, 0), (8, 1, 3), (12, 1, 3), (8, 2, 3), (8, 4, 3), (8, 8, 3)],
+    SYM: [(1, 1, 0), (2, 1, 0), (4, 1, 0), (8, 1, 0), (4, 4, 0), (4, 8, 0)],
+}
+# PNEC_FOR_EACH_GEOMETRY (pnec_solve_kernel.hpp) and what geometry_ok refuses: the 18-plane SYM
+# payload does not fit the register budget of the (8, W, 3) family, and (12, 1, 3) is 12 planes at most
+ALL_GEOMETRIES = [(1, 1, 0), (2, 1, 0), (4, 1, 0), (4, 2, 0), (4, 4, 0), (4, 8, 0), (8, 1, 3), (12, 1, 3),
+                  (8, 2, 3), (8, 4, 3), (8, 8, 3), (8, 1, 0), (1, 8, 0)]
+REFUSED = {NEC: set(), TARGET: set(), HOST: set(),
+           SYM: {(8, 1, 3), (12, 1, 3), (8, 2, 3), (8, 4, 3), (8, 8, 3)}}
+# one multi-wavefront geometry per family for the input edges
+MULTI_WAVE = {NEC: (8, 2, 3), TARGET: (8, 2, 3), HOST: (8, 2, 3), SYM: (4, 4, 0)}
+
+DEFAULT = dict()
+FIXED10 = dict(max_num_iterations=10, check_convergence=0)
+
+
+def _cap(g):
+    return 64 * g[0] * g[1]
+
+
+def _odd_slot_count(g, prev):
+    """An odd count that leaves a register slot half-filled: inside the last wavefront's odd
+    register slot (slot_corr: REGK odd -> slot REGK - 1 holds 64 consecutive correspondences) or,
+    for the (12, 1, 3) tail and the even-REGK shapes, an odd count between the rung's bounds."""
+    cpl, wpp, ldsk = g
+    regk = min(cpl, 8) - ldsk
+    if cpl <= 8 and regk % 2 == 1 and regk > 1:
+        n = (wpp - 1) * 64 * cpl + 64 * (regk - 1) + 33
+    else:
+        n = (prev + _cap(g)) // 2 | 1
+    assert prev < n < _cap(g)
+    return n
+
+
+def _ladder_cases(mode):
+    """(geometry or None for streaming, [first count, odd count, full capacity])"""
+    out, prev = [], 0
+    for g in LADDER[mode]:
+        # the first rung starts at 10: fewer correspondences leave the 5-parameter problem (nearly)
+        # rank-deficient, where no two LM implementations follow one path (test_parity_gpu's ragged test)
+        first = max(prev + 1, 10)
+        out.append((g, [first, _odd_slot_count(g, prev), _cap(g)]))
+        prev = _cap(g)
+    out.append((None, [prev + 1, prev + 1001]))
+    return out
+
+
+def _rot_err(oracle, qa, qb):
+    return math.radians(oracle.rotational_difference_deg(oracle.rot_from_quat(qa), oracle.rot_from_quat(qb)))
+
+
+def _covs_for(mode, S2):
+    """(covs, covs_host) for a residual family (test_parity_gpu's derivation)"""
+    if mode == NEC:
+        return None, None
+    if mode == SYM:
+        return S2, np.roll(S2, 1, axis=0) * 0.8
+    return S2, None
+
+
+def _oracle_opts(oracle, hip_opts, jacobian_mode):
+    o = oracle.default_options(jacobian_mode=jacobian_mode)
+    for name in ("max_num_iterations", "check_convergence", "function_tolerance",
+                 "gradient_tolerance", "parameter_tolerance", "jacobi_scaling"):
+        setattr(o, name, getattr(hip_opts, name))
+    return o
+
+
+class Case:
+    """One uniform batch: B pairs of n correspondences (f1, f2 [B*n,3], covs [B*n,3,3] or None)."""
+
+    def __init__(self, mode, f1, f2, c2, c1, q0, t0, n, reg=1e-13):
+        self.mode, self.f1, self.f2, self.c2, self.c1 = mode, f1, f2, c2, c1
+        self.q0, self.t0, self.n, self.reg = np.asarray(q0, float), np.asarray(t0, float), n, reg
+        self.B = len(self.q0)
+        self.offsets = np.arange(self.B + 1, dtype=np.int64) * n
+
+    @classmethod
+    def sim(cls, mode, B, n, seed, **kw):
+        g = sim.generate(B, n, seed=seed, **kw)
+        c2, c1 = _covs_for(mode, g.covs2.reshape(-1, 3, 3).numpy())
+        return cls(mode, g.bvs1.reshape(-1, 3).numpy(), g.bvs2.reshape(-1, 3).numpy(), c2, c1,
+                   g.init_q.numpy(), g.init_t.numpy(), n)
+
+    def device(self, geometry=None, expect=None, hyp_t=None, n_hyp=1, q0=None, t0=None, **opts):
+        """solve on the device; `geometry` forces a launch shape ("stream" = the streaming kernel),
+        `expect` is the geometry describe_launch must report"""
+        if geometry == "stream":
+            opts.update(corr_per_lane=0, waves_per_pair=8)
+        elif geometry is not None:
+            opts.update(corr_per_lane=geometry[0], waves_per_pair=geometry[1], lds_corr_per_lane=geometry[2])
+        o = capi.default_options(**opts)
+        with Batch(self.mode, self.offsets) as b:
+            if expect is not None:
+                d = b.describe_launch(o if geometry is not None else None)
+                if expect == "stream":
+                    assert d["resident"] is False, d
+                else:
+                    assert d["resident"] is True, d
+                    assert (d["corr_per_lane"], d["waves_per_pair"], d["lds_corr_per_lane"]) == expect, d
+            b.fill(self.f1, self.f2, self.c2, self.c1)
+            res = b.solve(self.q0 if q0 is None else q0, None if hyp_t is not None else (self.t0 if t0 is None else t0),
+                          reg=self.reg, options=o, hyp_t=hyp_t, n_hyp=n_hyp)
+        return res, o
+
+    def oracle(self, oracle, o, jacobian_mode, hyp_t=None, n_hyp=1, q0=None, t0=None):
+        c2_9 = None if self.c2 is None else oracle.covs_to_colmajor9(self.c2)
+        c1_9 = None if self.c1 is None else oracle.covs_to_colmajor9(self.c1)
+        return oracle.solve_batch(self.mode, self.offsets, self.f1, self.f2, c2_9, c1_9, self.reg,
+                                  self.q0 if q0 is None else q0, self.t0 if t0 is None else t0,
+                                  n_hyp=n_hyp, hyp_t=hyp_t, options=_oracle_opts(oracle, o, jacobian_mode))
+
+
+def _agree(oracle, res, ref, what, rot_tol=1e-9, cost_rtol=1e-9, check_t=True, solves=None):
+    """device result vs an oracle solve_batch tuple, the module's bars"""
+    q, t, cost, it, st = ref
+    solves = range(len(it)) if solves is None else solves
+    for s in solves:
+        tag = f"{what}, solve {s}: device it/st {res.iterations[s]}/{res.status[s]}, oracle {it[s]}/{st[s]}"
+        assert res.iterations[s] == it[s] and res.status[s] == st[s], tag
+        err = _rot_err(oracle, res.q[s], q[s])
+        assert err <= rot_tol, f"{tag}: rotation {err:.3e} rad"
+        if cost_rtol is not None:
+            assert res.cost[s] == pytest.approx(cost[s], rel=cost_rtol, abs=0.0), \
+                f"{tag}: cost {res.cost[s]!r} vs {cost[s]!r}"
+        if check_t:
+            assert abs(float(res.t[s] @ t[s])) > 1 - 1e-10, f"{tag}: t {res.t[s]} vs {t[s]}"
+
+
+def _both_bars(oracle, case, res, o, what, numeric_solves=(0,), rot_tol=1e-9):
+    _agree(oracle, res, case.oracle(oracle, o, oracle.JAC_ANALYTIC), what, rot_tol=rot_tol)
+    if numeric_solves:
+        q, t, cost, it, st = case.oracle(oracle, o, oracle.JAC_NUMERIC_CENTRAL)
+        for s in numeric_solves:
+            assert res.iterations[s] == it[s] and res.status[s] == st[s], (what, "central", s)
+            assert _rot_err(oracle, res.q[s], q[s]) <= 1e-6, (what, "central", s)
+
+
+def _stream_handle_is_bitwise(case, res, o, what):
+    """the streaming handle's AoS-source kernels (load_resident_aos places correspondences by
+    slot_corr) on the same pairs: the batch path's bits"""
+    from pnec_amd.streaming import Stream
+    with Stream(max_corr=case.n * case.B, max_pairs=case.B, slots=2) as st:
+        got = st.wait(st.submit(case.mode, case.f1, case.f2, case.c2, case.c1, case.q0, case.t0, reg=case.reg,
+                                options=o, offsets=case.offsets))
+    for name in ("q", "t", "cost", "iterations", "status"):
+        np.testing.assert_array_equal(getattr(got, name), np.asarray(getattr(res, name)), err_msg=f"{what}: {name}")
+
+
+# ------------------------------------------------------------------------------ (a) geometries
+@pytest.mark.parametrize("mode", FAMILIES, ids=FAMILY_IDS)
+def test_every_ladder_rung_against_oracle(oracle, mode):
+    """Each rung of the family's ladder at its first count, an odd count that half-fills a register
+    slot, and its full capacity, plus the streaming fallback; describe_launch must report the rung
+    (a later ladder change cannot move a case silently).  Ceres-default termination and the fixed
+    10-iteration mode; the central-difference path on one pair per rung; the streaming handle at the
+    odd count, bit for bit."""
+    for r, (g, sizes) in enumerate(_ladder_cases(mode)):
+        for i, n in enumerate(sizes):
+            case = Case.sim(mode, 2, n, seed=7000 + 97 * mode + 10 * r + i)
+            for k, opts in enumerate((DEFAULT, FIXED10)):
+                res, o = case.device(expect=g if g is not None else "stream", **opts)
+                numeric = (0,) if (i == len(sizes) - 1 and k == 0) else ()
+                # 10 correspondences driven 10 iterations past convergence: the last steps move by rounding
+                # noise of a barely determined problem (measured 2.4e-9 rad, HOST); every other case 1e-9
+                tol = 1e-8 if (r == 0 and i == 0 and opts is FIXED10) else 1e-9
+                _both_bars(oracle, case, res, o, f"{FAMILY_IDS[mode]} rung {g} n={n} {opts}", numeric, rot_tol=tol)
+                if i == 1 and k == 0:
+                    _stream_handle_is_bitwise(case, res, o, f"{FAMILY_IDS[mode]} rung {g} n={n}")
+
+
+@pytest.mark.parametrize("mode", FAMILIES, ids=FAMILY_IDS)
+def test_every_forced_geometry_runs_or_is_refused(oracle, mode):
+    """Every geometry of PNEC_FOR_EACH_GEOMETRY, forced: the ones geometry_ok builds for this family
+    run and match the oracle (at a small pair and at one correspondence under the capacity), the
+    others raise PnecHipError(unsupported).  The streaming kernel forced as well."""
+    for gi, g in enumerate(ALL_GEOMETRIES + ["stream"]):
+        if g in REFUSED[mode]:
+            case = Case.sim(mode, 2, 60, seed=8100 + gi)
+            with pytest.raises(capi.PnecHipError) as e:
+                case.device(geometry=g)
+            assert e.value.code == capi.ERR_UNSUPPORTED
+            continue
+        for n in sorted({60, (_cap(g) - 1) if g != "stream" else 777}):
+            case = Case.sim(mode, 2, n, seed=8000 + 31 * mode + gi)
+            res, o = case.device(geometry=g, expect=g)
+            _both_bars(oracle, case, res, o, f"{FAMILY_IDS[mode]} forced {g} n={n}", numeric_solves=())
+
+
+@pytest.mark.parametrize("mode", FAMILIES, ids=FAMILY_IDS)
+def test_three_hypotheses_per_pair(oracle, mode):
+    """n_hyp = 3: the pair-hypothesis kernel (two per wavefront, the third alone) on a one-wavefront
+    rung and the group kernel (a short group) on a several-wavefront rung, against the oracle's own
+    n_hyp / hyp_t solve.  The hypotheses lie within ~0.3 of the start translation: from random
+    directions on the sphere the fixed 10 iterations end mid-descent at costs ~3e5, where the two
+    sides agree to 1.3e-8 only (measured); test_parity_gpu's multi-hypothesis test covers those."""
+    rng = np.random.default_rng(40 + mode)
+    for n, g in ((300, LADDER[mode][3]), (900, LADDER[mode][4] if mode == SYM else (8, 2, 3))):
+        case = Case.sim(mode, 2, n, seed=9000 + 10 * mode + n)
+        hyp = np.repeat(case.t0, 3, axis=0) + 0.3 * rng.normal(size=(2 * 3, 3))
+        hyp /= np.linalg.norm(hyp, axis=1, keepdims=True)
+        hyp[::3] = case.t0
+        for opts in (DEFAULT, FIXED10):
+            res, o = case.device(expect=g, hyp_t=hyp, n_hyp=3, **opts)
+            ref = case.oracle(oracle, o, oracle.JAC_ANALYTIC, hyp_t=hyp, n_hyp=3)
+            _agree(oracle, res, ref, f"{FAMILY_IDS[mode]} n_hyp=3 n={n} {opts}")
+
+
+# ------------------------------------------------------------------------------ (b) input edges
+def _edge_geometries(mode):
+    """(n, forced geometry or None, geometry describe_launch reports): one wavefront from the
+    ladder, and the multi-wavefront shape forced over a pair that spans several wavefronts"""
+    return [(200, None, (4, 1, 0)), (600, MULTI_WAVE[mode], MULTI_WAVE[mode])]
+
+
+def _start_translations(t):
+    """start translations at the chart's edges: +-z exactly with every sign pattern of +-0.0 in x
+    and y, +-z tilted by 1e-12 / 1e-10 / 1e-8, the phi = +-pi seam, t scaled by 1e-3 and 1e3, and
+    t = 0.  Returns (vectors [K,3], exact [K] bool: the components' arithmetic in angles_from_vec
+    and the sine / cosine of the resulting angles is exact, so the returned t is bit for bit C's)."""
+    v, exact = [], []
+    for z in (1.0, -1.0):
+        for sx in (0.0, -0.0):
+            for sy in (0.0, -0.0):
+                v.append((sx, sy, z)); exact.append(True)
+        for eps in (1e-12, 1e-10, 1e-8):
+            v.append((eps, 0.0, z)); exact.append(False)
+            v.append((-0.0, -eps, z)); exact.append(False)
+    for sy in (0.0, -0.0):
+        v.append((-1.0, sy, 0.0)); exact.append(True)
+        v.append((-1.0, sy, 0.3)); exact.append(False)
+    v.append(tuple(1e-3 * t)); exact.append(False)
+    v.append(tuple(1e3 * t)); exact.append(False)
+    v.append((0.0, 0.0, 0.0)); exact.append(True)
+    return np.array(v, dtype=float), np.array(exact)
+
+
+def _sign_pattern_equal(a, b):
+    """the signs of the non-zero components (the seam's t_y = sin(theta) sin(+-pi) is +-1.2e-16)"""
+    return bool((np.sign(a) == np.sign(b)).all())
+
+
+@pytest.mark.parametrize("mode", FAMILIES, ids=FAMILY_IDS)
+def test_start_translations_on_axes_and_seam(oracle, mode):
+    """Start translations where angles_from_vec meets signed zeros, the +-z axis and the phi = +-pi
+    seam (C atan2 / acos semantics, as the reference and the oracle use).  With
+    max_num_iterations = 0 the returned t is the start's (theta, phi) through sin / cos: bit for bit
+    the oracle's where every step is exact; elsewhere within 4e-15 per component -- the device's own
+    sin / cos and acos / atan2 bounds (pnec_hip_selftest: 4e-16 and 9e-16 relative on angles up to
+    pi) -- with the sign of every non-zero component equal.  The same vectors as hyp_t through the
+    pair-hypothesis and group kernels.  Full solves from each start at the module's bars."""
+    for n, geom, expect in _edge_geometries(mode):
+        base = Case.sim(mode, 1, n, seed=9500 + 10 * mode + n)
+        T, exact = _start_translations(base.t0[0])
+        K = len(T)
+        case = Case(mode, np.tile(base.f1, (K, 1)), np.tile(base.f2, (K, 1)),
+                    None if base.c2 is None else np.tile(base.c2, (K, 1, 1)),
+                    None if base.c1 is None else np.tile(base.c1, (K, 1, 1)),
+                    np.tile(base.q0, (K, 1)), T, n)
+        what = f"{FAMILY_IDS[mode]} n={n} {geom}"
+        res0, o0 = case.device(geometry=geom, expect=expect, max_num_iterations=0)
+        ref0 = case.oracle(oracle, o0, oracle.JAC_ANALYTIC)
+        assert (res0.iterations == 0).all() and (ref0[3] == 0).all()
+        for k in range(K):
+            if exact[k]:
+                np.testing.assert_array_equal(res0.t[k], ref0[1][k], err_msg=f"{what}: t0 = {T[k]!r}")
+            else:
+                np.testing.assert_allclose(res0.t[k], ref0[1][k], rtol=0, atol=4e-15, err_msg=f"{what}: t0 = {T[k]!r}")
+            assert _sign_pattern_equal(res0.t[k], ref0[1][k]), (what, T[k], res0.t[k], ref0[1][k])
+        # the same vectors as hypotheses: the pair-hypothesis kernel (one wavefront) / group kernel
+        one = Case(mode, base.f1, base.f2, base.c2, base.c1, base.q0, base.t0, n)
+        resh, oh = one.device(geometry=geom, expect=expect, hyp_t=T, n_hyp=K, max_num_iterations=0)
+        for k in range(K):
+            if exact[k]:
+                np.testing.assert_array_equal(resh.t[k], ref0[1][k], err_msg=f"{what} hyp_t: {T[k]!r}")
+            else:
+                np.testing.assert_allclose(resh.t[k], ref0[1][k], rtol=0, atol=4e-15, err_msg=f"{what} hyp_t: {T[k]!r}")
+            assert _sign_pattern_equal(resh.t[k], ref0[1][k]), (what, "hyp_t", T[k])
+        # full solves from every start, and through the hypothesis kernels.  A start at theta = pi exactly
+        # (-z, and -z tilted by less than acos(1 - 2^-53)) has sin(theta) = 1.2e-16: the phi column of J is
+        # rounding-sized and the first phi steps are decided by its last bits (measured 9.0e-7 rad, HOST
+        # (8, 2, 3), t0 = (0, 0, -1), equal counts): those solves get the reference bar, 1e-6 rad
+        # Starts on the seam point away from the truth and may crawl: past 30 iterations the rounding
+        # differences of the two sides' sums have compounded (measured 4.8e-9 rad after 43 equal
+        # iterations, HOST (8, 2, 3), t0 = (-1, 0, 0.3)): 1e-8 for those, counts and codes still equal
+        at_pi = [k for k in range(K) if oracle.angles_from_vec(T[k])[0] == math.pi]
+        for label, c, r in (("", case, None), (" hyp_t", one, T)):
+            if r is None:
+                res, o = c.device(geometry=geom, expect=expect)
+                ref = c.oracle(oracle, o, oracle.JAC_ANALYTIC)
+            else:
+                res, o = c.device(geometry=geom, expect=expect, hyp_t=T, n_hyp=K)
+                ref = c.oracle(oracle, o, oracle.JAC_ANALYTIC, hyp_t=T, n_hyp=K)
+            long_runs = [k for k in range(K) if k not in at_pi and ref[3][k] > 30]
+            other = [k for k in range(K) if k not in at_pi and k not in long_runs]
+            _agree(oracle, res, ref, what + label + " full", solves=other)
+            _agree(oracle, res, ref, what + label + " full, > 30 iterations", rot_tol=1e-8, solves=long_runs)
+            _agree(oracle, res, ref, what + label + " full, theta0 = pi", rot_tol=1e-6, cost_rtol=1e-6, solves=at_pi)
+
+
+def _scene(rng, n, R, t, camera_noise=1.0 / 800.0):
+    """bearings of points around the first camera (all directions: large rotations turn points
+    behind either camera), noisy in the tangent plane of f2 with a rank-2 tangent-plane covariance,
+    as the unscented transform produces"""
+    u = rng.normal(size=(n, 3))
+    P = u / np.linalg.norm(u, axis=1, keepdims=True) * rng.uniform(4.0, 8.0, size=(n, 1))
+    f1 = P / np.linalg.norm(P, axis=1, keepdims=True)
+    P2 = (P - t) @ R            # R' (P - t)
+    f2 = P2 / np.linalg.norm(P2, axis=1, keepdims=True)
+    a = np.cross(f2, rng.normal(size=(n, 3)))
+    a /= np.linalg.norm(a, axis=1, keepdims=True)
+    b = np.cross(f2, a)
+    sa, sb = rng.uniform(0.5, 1.5, size=(2, n, 1)) * camera_noise
+    cov = sa[..., None] ** 2 * a[:, :, None] * a[:, None, :] + sb[..., None] ** 2 * b[:, :, None] * b[:, None, :]
+    f2 = f2 + sa * rng.normal(size=(n, 1)) * a + sb * rng.normal(size=(n, 1)) * b
+    f2 /= np.linalg.norm(f2, axis=1, keepdims=True)
+    return f1, f2, cov
+
+
+def _axis_angle(axis, angle):
+    axis = axis / np.linalg.norm(axis)
+    return np.concatenate([axis * math.sin(angle / 2), [math.cos(angle / 2)]])
+
+
+@pytest.mark.parametrize("mode", FAMILIES, ids=FAMILY_IDS)
+def test_large_rotations_quaternion_sign_and_scale(oracle, mode):
+    """Ground truth and start rotated by 1, 2, 3 and pi - 1e-6 rad about random axes; each start as
+    q0 and as -q0 (against the oracle, and against each other: same counts, codes and rotation), and
+    scaled to |q0| = 0.5 and 2 (neither side normalises the start, by design)."""
+    rng = np.random.default_rng(60 + mode)
+    for n, geom, expect in _edge_geometries(mode):
+        f1s, f2s, cs, qs, ts = [], [], [], [], []
+        for angle in (1.0, 2.0, 3.0, math.pi - 1e-6):
+            q_gt = _axis_angle(rng.normal(size=3), angle)
+            R = oracle.rot_from_quat(q_gt)
+            t = rng.normal(size=3)
+            t /= np.linalg.norm(t)
+            f1, f2, cov = _scene(rng, n, R, t)
+            q0 = _axis_angle(rng.normal(size=3), 0.01)          # a start 0.01 rad from the truth
+            q0 = np.array([*(q0[3] * q_gt[:3] + q_gt[3] * q0[:3] + np.cross(q0[:3], q_gt[:3])),
+                           q0[3] * q_gt[3] - q0[:3] @ q_gt[:3]])
+            t0 = t + 0.01 * rng.normal(size=3)
+            for scale in (1.0, -1.0, 0.5, 2.0):
+                f1s.append(f1); f2s.append(f2); cs.append(cov); qs.append(scale * q0); ts.append(t0 / np.linalg.norm(t0))
+        c2, c1 = _covs_for(mode, np.concatenate(cs))
+        case = Case(mode, np.concatenate(f1s), np.concatenate(f2s), c2, c1, np.array(qs), np.array(ts), n)
+        what = f"{FAMILY_IDS[mode]} n={n} {geom}"
+        for opts in (DEFAULT, FIXED10):
+            res, o = case.device(geometry=geom, expect=expect, **opts)
+            _both_bars(oracle, case, res, o, f"{what} {opts}", numeric_solves=(0, 4, 8, 12) if not opts else ())
+            # q0 and -q0: the same counts and codes (the rotations need not agree to 1e-9: the oracle's two
+            # runs differ by 6.8e-6 rad on a SYM start at 1 rad, and the device follows each to 1e-9)
+            for s in range(0, case.B, 4):
+                assert res.iterations[s] == res.iterations[s + 1] and res.status[s] == res.status[s + 1], (what, s)
+
+
+@pytest.mark.parametrize("mode", [TARGET, HOST, SYM], ids=["TARGET", "HOST", "SYM"])
+def test_covariance_magnitudes_and_zero_regularisation(oracle, mode):
+    """Covariances scaled by 10^k, k in {-12, -6, 0, 6, 12}, with reg 0 and 1e-13: the cost moves
+    over 24 decades while Ceres' gradient tolerance stays absolute, so the termination decisions move
+    with it.  The covariances are the simulator's unscented-transform ones: rank 2, tangent plane."""
+    for n, geom, expect in _edge_geometries(mode):
+        base = Case.sim(mode, 3, n, seed=9700 + 10 * mode + n)
+        for reg in (0.0, 1e-13):
+            for k in (-12, -6, 0, 6, 12):
+                s = 10.0 ** k
+                case = Case(mode, base.f1, base.f2, base.c2 * s, None if base.c1 is None else base.c1 * s,
+                            base.q0, base.t0, n, reg=reg)
+                res, o = case.device(geometry=geom, expect=expect)
+                _agree(oracle, res, case.oracle(oracle, o, oracle.JAC_ANALYTIC), f"{FAMILY_IDS[mode]} n={n} {geom} 1e{k} reg={reg}")
+
+
+# Known divergence at reg = 0: eval_corr clamps the denominator at 1e-300 (pnec_device.hpp), so the
+# device's r is 0 with a finite Jacobian where the reference divides 0 by 0.  Measured: the device
+# solves on (TARGET 6 iterations, HOST 9, status 0) where the oracle fails at iteration 0 (status 6).
+# Strict: the day the clamp follows the reference, this case passes and the marker has to go.
+EPIPOLE_REG0 = pytest.mark.xfail(strict=True, reason="eval_corr's 1e-300 clamp turns the reference's 0/0 "
+                                                    "on the epipole into r = 0 and a finite Jacobian")
+
+
+@pytest.mark.parametrize("reg", [pytest.param(0.0, marks=EPIPOLE_REG0), 1e-13], ids=["reg0", "reg1e-13"])
+@pytest.mark.parametrize("mode", [TARGET, HOST], ids=["TARGET", "HOST"])
+def test_correspondence_on_the_epipole(oracle, mode, reg):
+    """One correspondence exactly on the epipole of the start: TARGET with f1 = t0 = (0, 0, 1);
+    HOST with R0 f1 || t0 (R0 about z, f1 = t0 = (0, 0, 1)).  Its denominator is exactly reg: at
+    reg = 0 the reference's residual is 0 / 0, a failed evaluation at the start (Ceres: the solve
+    fails at iteration 0); at reg = 1e-13 it is an ordinary correspondence.  The expected status and
+    count are the oracle's.  The correspondence sits first in one pair and last (the lane next to the
+    padding) in the other."""
+    rng = np.random.default_rng(80 + mode)
+    for n, geom, expect in _edge_geometries(mode):
+        base = Case.sim(mode, 2, n, seed=9800 + 10 * mode + n)
+        f1 = base.f1.copy()
+        f1[0] = (0.0, 0.0, 1.0)
+        f1[2 * n - 1] = (0.0, 0.0, 1.0)
+        t0 = np.array([[0.0, 0.0, 1.0]] * 2)
+        if mode == HOST:
+            q0 = np.array([_axis_angle(np.array([0.0, 0.0, 1.0]), a) for a in rng.uniform(0.1, 0.3, size=2)])
+        else:
+            q0 = base.q0
+        case = Case(mode, f1, base.f2, base.c2, base.c1, q0, t0, n, reg=reg)
+        ref = case.oracle(oracle, capi.default_options(), oracle.JAC_ANALYTIC)
+        what = f"{FAMILY_IDS[mode]} n={n} {geom} reg={reg}"
+        if reg == 0.0:
+            assert (ref[4] == BAD_INITIAL).all() and (ref[3] == 0).all(), (what, ref[3], ref[4])
+        res, o = case.device(geometry=geom, expect=expect)
+        assert np.isfinite(res.q).all() and np.isfinite(res.t).all()
+        _agree(oracle, res, ref, what, cost_rtol=None if reg == 0.0 else 1e-9)
+
+
+@pytest.mark.parametrize("mode", FAMILIES, ids=FAMILY_IDS)
+def test_noise_free_omnidirectional_and_far_starts(oracle, mode):
+    """Noise-free data (noise_level 1e-30: the cost ends near rounding level, where the gradient
+    tolerance decides), omnidirectional bearings (f1 behind the camera), and starts ten times
+    farther from the truth than the simulator's default.  Noise-free costs are the square of what the
+    last step left of the pose error, ~1e-8 of the start's: they agree to 2.8e-6 (measured, TARGET
+    n = 200), compared at rtol 1e-4; counts, codes, rotation and t at the module's bars."""
+    for n, geom, expect in _edge_geometries(mode):
+        for label, kw in (("noise-free", dict(noise_level=1e-30)), ("omni", dict(camera="omnidirectional")),
+                          ("far", dict(init_scaling=10.0))):
+            case = Case.sim(mode, 3, n, seed=9900 + 10 * mode + n, **kw)
+            res, o = case.device(geometry=geom, expect=expect)
+            _agree(oracle, res, case.oracle(oracle, o, oracle.JAC_ANALYTIC), f"{FAMILY_IDS[mode]} n={n} {geom} {label}",
+                   cost_rtol=1e-4 if label == "noise-free" else 1e-9)
+
+
+@pytest.mark.parametrize("mode", FAMILIES, ids=FAMILY_IDS)
+def test_pure_rotation(oracle, mode):
+    """translation=False: the true t is 0, so t is not observable -- every direction explains the
+    data to the noise level and the t each side ends at is decided by rounding noise.  Only the
+    rotation (which the bearings do fix) is compared, against the central-difference path's bar."""
+    for n, geom, expect in _edge_geometries(mode):
+        case = Case.sim(mode, 3, n, seed=9950 + 10 * mode + n, translation=False)
+        res, o = case.device(geometry=geom, expect=expect)
+        q = case.oracle(oracle, o, oracle.JAC_ANALYTIC)[0]
+        for s in range(case.B):
+            assert _rot_err(oracle, res.q[s], q[s]) <= 1e-6, (FAMILY_IDS[mode], n, s)
