@@ -187,7 +187,7 @@ __global__ __launch_bounds__(kWave *WPP, (CPL == 8 && LDSK == 0) ? 1 : 2) void l
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     if (lane < 4 && ist_all[hw][kITerm] < 0) {
-      const int t = lm_advance<kCostFirst>(slab_all[hw], ist_all[hw], unif_all[hw], o, inv_max_radius, inv_min_radius);
+      const int t = lm_advance<true>(slab_all[hw], ist_all[hw], unif_all[hw], o, inv_max_radius, inv_min_radius);
       if (lane == 0) ist_all[hw][kITerm] = t;
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -210,9 +210,10 @@ __global__ __launch_bounds__(kWave *WPP, (CPL == 8 && LDSK == 0) ? 1 : 2) void l
 // The same idea where a solve is ONE wavefront (the (1..8, 1, *) geometries): the wavefront keeps the pair's payload and
 // walks two of its hypotheses -- two passes against the resident data, then BOTH LM steps at once, hypothesis h in quad h
 // (lm_advance is per-lane code whose only cross-lane traffic stays inside a quad) -- so the ~400 issue slots of a step are
-// paid once per two solves, with no barrier at all: what round 5's SRC_DUAL form (two solves of DIFFERENT pairs per block)
-// bought with two block barriers per iteration and lost to them.  Two is what fits: the second hypothesis' state (880 B)
-// still leaves eight wavefronts per CU beside the (8, 1, 3) payload (8 x 20 192 B <= 160 KB; a third would not).
+// paid once per two solves, with no barrier at all (two solves of DIFFERENT pairs per block sharing one step needed two
+// block barriers per iteration and measured 8.8 % slower; NOTES/round-5.md).  Two is what fits: the second hypothesis'
+// state (880 B) still leaves eight wavefronts per CU beside the (8, 1, 3) payload (8 x 20 192 B <= 160 KB; a third
+// would not).
 // Bit-identical to one solve per block.
 constexpr int kPairHyp = 2;
 #define PNEC_FOR_EACH_PAIRHYP_GEOMETRY(X) X(1, 1, 0) X(2, 1, 0) X(4, 1, 0) X(8, 1, 3) X(8, 1, 0)
@@ -338,7 +339,7 @@ __global__ __launch_bounds__(kWave, (CPL == 8 && LDSK == 0) ? 1 : 2) void lm_sol
       const int h = lane >> 2;
       __builtin_amdgcn_s_setprio(3);
       if (h < G && ist_all[h][kITerm] < 0) {
-        const int t = lm_advance<kCostFirst>(slab_all[h], ist_all[h], unif_all[h], o, inv_max_radius, inv_min_radius);
+        const int t = lm_advance<true>(slab_all[h], ist_all[h], unif_all[h], o, inv_max_radius, inv_min_radius);
         if ((lane & 3) == 0) ist_all[h][kITerm] = t;
       }
       __builtin_amdgcn_s_setprio(0);

@@ -128,12 +128,6 @@ enum : int {
   kSlab = 88
 };
 constexpr int kUnif = 18;   // pass uniforms of the candidate: R[9] | t[3] | dt/dtheta[3] | dt/dphi[2] | pad
-// cost-only pass after a rejected step (lm_advance<COST_FIRST>); -DPNEC_NO_COST_FIRST: the always-speculating kernel (A/B)
-#ifdef PNEC_NO_COST_FIRST
-constexpr bool kCostFirst = false;
-#else
-constexpr bool kCostFirst = true;
-#endif
 // per-solve integer state (LDS)
 enum : int { kIIter = 0, kIFirst, kIReuseDiag, kINumInvalid, kIStepOk,
               kILast,  // the published candidate is evaluated at the iteration cap: its Jacobian can never be used
@@ -147,12 +141,7 @@ enum : int { kIIter = 0, kIFirst, kIReuseDiag, kINumInvalid, kIStepOk,
 __host__ __device__ constexpr bool geometry_ok(int mode, int cpl, int wpp, int ldsk) {
   const int nc = num_components(mode);
   if (cpl == 12) return wpp == 1 && ldsk == 3 && nc <= 12;  // (8, 1, 3) + tail: the 6- and 12-plane payloads
-#ifdef PNEC_ADVANCE_ROWS
-  constexpr long ab_lds = 16 * 8 * 4;  // gather offsets of lm_advance_rows (A/B build only)
-#else
-  constexpr long ab_lds = 0;
-#endif
-  const long lds = (long)wpp * (ldsk * nc * kWave * 8 + (kSlab + kUnif) * 8 + kINumI * 4) + (wpp > 1 ? 2L * wpp * kSumSlots * 8 : 0) + ab_lds;
+  const long lds = (long)wpp * (ldsk * nc * kWave * 8 + (kSlab + kUnif) * 8 + kINumI * 4) + (wpp > 1 ? 2L * wpp * kSumSlots * 8 : 0);
   if (lds > 160 * 1024) return false;
   if (cpl == 8 && ldsk == 0) return nc <= 18;
   return nc * (cpl - ldsk) <= 72;
@@ -454,8 +443,11 @@ __device__ __forceinline__ void write_result(const SolveArgs &a, int64_t s, cons
 // (counted on the CPU checker: DESIGN.md 6).  The cost-only pass is 43 instructions per correspondence and one sum
 // through the reduction tree instead of 21; when such a step IS accepted the same candidate is evaluated once more in
 // full and this function runs again on the complete sums -- same cost bits (the cost-only pass reduces through the same
-// tree), same decision, same everything downstream: the results are bit for bit those of the always-speculating kernel.
-// With Ceres-default termination there is next to nothing to gain or lose (18 rejected steps in 10 046).
+// tree), same decision, same everything downstream: the results are bit for bit those of always speculating.
+// With Ceres-default termination there is next to nothing to gain or lose (18 rejected steps in 10 046).  The
+// register-resident kernels run with COST_FIRST; the streaming fallback (whose passes are always full) without.
+// Always speculating measured 33.7-34.5 against 36.6-36.75 M solves/s on one box (NOTES/rounds-1-4.md), and running
+// this step across the lanes of a row instead of one quad measured 2 % slower (NOTES/rounds-1-4.md, lane-parallel LM step).
 template <bool COST_FIRST>
 __device__ __forceinline__ int lm_advance(double *slab, int *ist, double *unif, const pnec_hip_options &o,
                                           double inv_max_radius, double inv_min_radius) {
@@ -715,292 +707,6 @@ __device__ __forceinline__ int lm_advance(double *slab, int *ist, double *unif, 
   return term;
 }
 
-// ---- the same step, ACROSS THE LANES OF A ROW: an A/B build (-DPNEC_ADVANCE_ROWS), NOT the default.  Measured on the
-// benchmark (same box, same call): SQ_INSTS_VALU 14 202 -> 13 936 per solve (-1.9 %), 33.8 -> 33.1 M solves/s (-2 %).
-// The kernel sits where two limits meet -- the VALU issue slots of two wavefronts per SIMD and the latency of this
-// chain against the other wavefront's pass -- and this form buys its fewer slots with a longer chain (the gather is
-// two dependent LDS round trips instead of one, every fused broadcast waits out the DPP hazard).  Kept because it is
-// the measured answer to "run the 5x5 solve across lanes" and the home of the DP-ALU DPP primitives.
-// lm_advance runs one solve's step identically in four lanes: a wavefront instruction costs its four issue
-// clocks whether four or sixty-four lanes are live, so everything that is a 5-vector or a 5x5 matrix is paid for
-// five (or fifteen) times over.  Here the WHOLE wavefront executes the step (EXEC full: the 64-bit DPP broadcasts
-// need their source lanes active) and lane i (i = 0..4) of every 16-lane row owns component i: row i of the normal
-// equations, g_i, the LM diagonal, the Jacobi scale, the step p_i.  Cross-lane traffic is the DP ALU's
-// row_newbcast fused into v_fmac_f64 (pnec_device.hpp: fmac_row / fnmac_row / bcast_row), i.e. free of its own
-// instruction: the 5x5 system is a Gauss-Jordan elimination across lanes (gj_solve5_rows, ~70 slots against ~125),
-// the clamped diagonal, the scaled step and the model decrease are one lane-parallel expression each, and the six
-// sines / cosines of the step reach the quaternion and the pose uniforms through one 64-bit broadcast each instead
-// of two 32-bit DPP moves.  Scalars of the solve (cost, radius, iteration counters, the quaternion) stay replicated in
-// every lane exactly as before; the control flow is the same code, statement for statement.
-//
-// Lane i finds its row in the 24-slot tables of sums through `gidx` (LDS, 8 ints per lane, written once per
-// kernel): byte offsets of H(i,0..4) and g_i inside a table (lanes >= 5: offset 0, harmless).  The four rows of
-// the wavefront do the same thing on the same data; stores are made by lane 0 (or lanes 0..4) only.
-constexpr int kGatherInts = 8;  // per lane: H(i,0) .. H(i,4), g_i, H(i,i), pad   (byte offsets into a table of sums)
-__device__ __forceinline__ void gather_index_init(int *gidx, int lane) {
-  if (lane < 16) {
-    int v[kGatherInts];
-#pragma unroll
-    for (int k = 0; k < kGatherInts; ++k) v[k] = 0;
-#pragma unroll
-    for (int i = 0; i < 5; ++i)
-      if (lane == i) {
-#pragma unroll
-        for (int k = 0; k < 5; ++k) v[k] = 8 * sum_slot(6 + tri(i < k ? i : k, i < k ? k : i));
-        v[5] = 8 * sum_slot(1 + i);
-        v[6] = 8 * sum_slot(6 + tri(i, i));
-      }
-#pragma unroll
-    for (int k = 0; k < kGatherInts; ++k) gidx[lane * kGatherInts + k] = v[k];
-  }
-}
-
-__device__ __forceinline__ int lm_advance_rows(double *slab, int *ist, double *unif, const int *gidx,
-                                               const pnec_hip_options &o, double inv_max_radius,
-                                               double inv_min_radius, int lane) {
-  const int li = lane & 15;
-  const bool own = li < 5;          // this lane owns a component
-  const bool writer = lane == 0;    // the one lane that stores scalars
-  const bool cwriter = lane < 5;    // the lanes that store 5-vectors
-  int iteration = ist[kIIter], reuse_diagonal = ist[kIReuseDiag];
-  int num_invalid = ist[kINumInvalid], step_ok = ist[kIStepOk];
-  const int first = ist[kIFirst];
-  const bool last = ist[kILast] != 0;  // the pass was the cost-only one: sums 1..20 do not exist
-  int park = ist[kIPark];
-  int term = -1;
-
-  // ---- loads: the scalars (broadcast reads) and this lane's gather offsets
-  const char *cand_tab = reinterpret_cast<const char *>(slab + kSums + (park ^ 1) * kSumSlots);
-  const double S0 = *reinterpret_cast<const double *>(cand_tab + 8 * sum_slot(0));
-  const bool rest_ok = slab[kSumsFinite] != 0.0;
-  const double qc0 = slab[kQc + 0], qc1 = slab[kQc + 1], qc2 = slab[kQc + 2], qc3 = slab[kQc + 3];
-  const double thc0 = slab[kThetaC], phc0 = slab[kPhiC];
-  const double cost = slab[kCost], model = slab[kModel], xnorm = slab[kXNorm];
-  double inv_radius = slab[kInvRadius], dec = slab[kDec], gmax = slab[kGmax];
-  int go[7];
-#pragma unroll
-  for (int k = 0; k < 7; ++k) go[k] = gidx[li * kGatherInts + k];
-  auto row_of = [&](const char *tab, double (&A)[5], double &gi) {
-#pragma unroll
-    for (int k = 0; k < 5; ++k) A[k] = *reinterpret_cast<const double *>(tab + go[k]);
-    gi = *reinterpret_cast<const double *>(tab + go[5]);
-  };
-  // this lane's own diagonal entry H(i,i) is column i of its row: its own gather offset, not a register select
-  auto diag_of = [&](const char *tab) { return *reinterpret_cast<const double *>(tab + go[6]); };
-  const double fcol = li >= 2 ? 2.0 : 1.0;  // the rotation columns of Ceres' tangent Jacobian are 2 x the pass's
-  double x[6];
-
-  double cost_c = 0.5 * S0;
-  const bool cost_ok = finite_d(cost_c);
-  bool accept = false;
-  double rho = 0.0;
-  if (first) {
-    if (!(cost_ok && rest_ok)) {
-      if (writer) {
-        slab[kQ + 0] = qc0; slab[kQ + 1] = qc1; slab[kQ + 2] = qc2; slab[kQ + 3] = qc3;
-        slab[kTheta] = thc0;
-        slab[kPhi] = phc0;
-        slab[kTcur + 0] = unif[9]; slab[kTcur + 1] = unif[10]; slab[kTcur + 2] = unif[11];
-        slab[kCost] = cost_c;
-      }
-      term = PNEC_HIP_TERM_BAD_INITIAL;
-    } else {
-      // jacobi_scaling: s = 1 / (1 + sqrt(diag(J'J))) on the Ceres-tangent Jacobian; frozen after iteration zero.
-      // Parked: (f s)^2 and its inverse, f = 2 for the rotation columns.  One component per lane.
-      const double hii = diag_of(cand_tab) * (fcol * fcol);
-      const double a = (o.jacobi_scaling ? 1.0 + fast_sqrt(hii) : 1.0) * (li >= 2 ? 0.5 : 1.0);  // 1 / (f s)
-      if (cwriter) {
-        slab[kInvScaleSq + li] = a * a;
-        slab[kScaleSq + li] = fast_rcp(a * a);
-      }
-      accept = true;
-    }
-  } else {
-    if (!cost_ok) cost_c = 1.7976931348623157e308;
-    if (o.check_convergence) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) x[k] = slab[kQ + k];
-      x[4] = slab[kTheta];
-      x[5] = slab[kPhi];
-      double dn = (x[4] - thc0) * (x[4] - thc0) + (x[5] - phc0) * (x[5] - phc0);
-      dn = __builtin_fma(x[0] - qc0, x[0] - qc0, dn);
-      dn = __builtin_fma(x[1] - qc1, x[1] - qc1, dn);
-      dn = __builtin_fma(x[2] - qc2, x[2] - qc2, dn);
-      dn = __builtin_fma(x[3] - qc3, x[3] - qc3, dn);
-      const double step_norm = fast_sqrt(dn);
-      if (step_norm <= o.parameter_tolerance * (xnorm + o.parameter_tolerance))
-        term = PNEC_HIP_TERM_PARAMETER_TOL;
-      else if (fabs(cost - cost_c) <= o.function_tolerance * cost)
-        term = PNEC_HIP_TERM_FUNCTION_TOL;
-    }
-    if (term < 0) {
-      rho = (cost - cost_c) * fast_rcp(model);
-      accept = rho > o.min_relative_decrease;
-      if (accept && !rest_ok) term = PNEC_HIP_TERM_BAD_INITIAL;  // finite cost, non-finite Jacobian: Ceres fails here
-    }
-  }
-
-  if (term < 0 && last) {
-    // at the iteration cap the solve ends here whatever the verdict on the step
-    if (accept && writer) {
-      slab[kQ + 0] = qc0; slab[kQ + 1] = qc1; slab[kQ + 2] = qc2; slab[kQ + 3] = qc3;
-      slab[kTheta] = thc0;
-      slab[kPhi] = phc0;
-        slab[kTcur + 0] = unif[9]; slab[kTcur + 1] = unif[10]; slab[kTcur + 2] = unif[11];
-      slab[kCost] = cost_c;
-    }
-    term = PNEC_HIP_TERM_MAX_ITERATIONS;
-  }
-  if (term < 0) {
-    double Hr[5], gi, diag = 0.0;   // this lane's row of J'J, its g_i, its LM diagonal entry
-    const char *cur_tab;            // the table of the point the next step starts from
-    if (accept) {
-      // x <- candidate; its normal equations are the sums of the pass just made
-      x[0] = qc0; x[1] = qc1; x[2] = qc2; x[3] = qc3; x[4] = thc0; x[5] = phc0;
-      cur_tab = cand_tab;
-      row_of(cur_tab, Hr, gi);
-      if (o.check_convergence) {  // only the gradient-tolerance test reads it: max_i |g_i| f_i over the five lanes
-        const double ga = fabs(gi) * fcol;
-        gmax = fmax(fmax(fmax(bcast_row<0>(ga), bcast_row<1>(ga)), fmax(bcast_row<2>(ga), bcast_row<3>(ga))), bcast_row<4>(ga));
-      }
-      if (first) {
-        inv_radius = fast_rcp(o.initial_trust_region_radius);
-      } else {
-        const double c1 = 2.0 * rho - 1.0;
-        inv_radius = fmax(inv_max_radius, inv_radius * fmax(1.0 / 3.0, 1.0 - c1 * c1 * c1));
-      }
-      dec = 2.0;
-      park ^= 1;  // the candidate's table is the current point's from now on (nothing is copied)
-      step_ok = 1;
-      reuse_diagonal = 0;
-      if (writer) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) slab[kQ + k] = x[k];
-        slab[kTheta] = x[4];
-        slab[kPhi] = x[5];
-        slab[kTcur + 0] = unif[9]; slab[kTcur + 1] = unif[10]; slab[kTcur + 2] = unif[11];
-        slab[kCost] = cost_c;
-        if (o.check_convergence) {  // |x| is only read by the parameter-tolerance test
-          slab[kXNorm] = fast_sqrt(x[4] * x[4] + x[5] * x[5] + x[0] * x[0] + x[1] * x[1] + x[2] * x[2] + x[3] * x[3]);
-          slab[kGmax] = gmax;
-        }
-      }
-    } else {
-      // rejected: back to the parked point (its normal equations are still in its table), smaller region
-#pragma unroll
-      for (int k = 0; k < 4; ++k) x[k] = slab[kQ + k];
-      x[4] = slab[kTheta];
-      x[5] = slab[kPhi];
-      cur_tab = reinterpret_cast<const char *>(slab + kSums + park * kSumSlots);
-      row_of(cur_tab, Hr, gi);
-      inv_radius = inv_radius * dec;
-      dec = 2.0 * dec;
-      reuse_diagonal = 1;
-    }
-    const double hii = diag_of(cur_tab);
-    if (reuse_diagonal) diag = slab[kDiag + (own ? li : 0)];
-    const double scale_sq = slab[kScaleSq + (own ? li : 0)], inv_scale_sq = slab[kInvScaleSq + (own ? li : 0)];
-    const double xang = li == 0 ? x[4] : x[5];   // lane 0 steps theta, lane 1 phi
-
-    // ---- FinalizeIterationAndCheckIfMinimizerCanContinue + the next trust-region step
-    for (;;) {
-      if (iteration >= o.max_num_iterations) { term = PNEC_HIP_TERM_MAX_ITERATIONS; break; }
-      if (o.check_convergence && step_ok && gmax <= o.gradient_tolerance) {
-        term = PNEC_HIP_TERM_GRADIENT_TOL; break;
-      }
-      if (inv_radius > inv_min_radius) { term = PNEC_HIP_TERM_MIN_RADIUS; break; }  // radius < min_radius
-      ++iteration;
-      step_ok = 0;
-
-      // LevenbergMarquardtStrategy::ComputeStep in parameter scale (see lm_advance): (H + D'/radius) p = -g,
-      // D'_i = clamp(s_i^2 H_ii) / s_i^2 -- one component per lane
-      if (!reuse_diagonal) {
-        diag = fmin(fmax(hii * scale_sq, o.min_lm_diagonal), o.max_lm_diagonal) * inv_scale_sq;
-        if (cwriter) slab[kDiag + li] = diag;
-      }
-      const double dr = diag * inv_radius;
-      double A[5];   // the elimination works in place: a retry starts from the row again
-#pragma unroll
-      for (int k = 0; k < 5; ++k) A[k] = Hr[k];
-      double p = -gi;
-      bool valid = gj_solve5_rows(A, dr, p, li);   // p_i = step component i (parameter scale), lanes 0..4
-      // model cost change (-g'p + p'(D'/radius)p) / 2: the lanes' terms summed through broadcasts; a non-finite
-      // step component makes the sum NaN (0 x inf), and NaN > 0 is false
-      double e = __builtin_fma(dr * p, p, -(p * gi));
-      e = __builtin_fma(p, 0.0, e);
-      double msum = 0.0;
-      fmac_row<0>(msum, e, 0.5);
-      fmac_row<1>(msum, e, 0.5);
-      fmac_row<2>(msum, e, 0.5);
-      fmac_row<3>(msum, e, 0.5);
-      fmac_row<4>(msum, e, 0.5);
-      const double model_change = msum;
-      valid = valid && (model_change > 0.0);
-      if (!valid) {
-        if (++num_invalid >= o.max_num_consecutive_invalid_steps) { term = PNEC_HIP_TERM_INVALID_STEPS; break; }
-        // [EXT, recalled] TrustRegionMinimizer::HandleInvalidStep -> LevenbergMarquardtStrategy::StepIsInvalid():
-        // radius *= 0.5, reuse_diagonal = true -- NOT the rejected-step rule: decrease_factor stays as it is
-        inv_radius = 2.0 * inv_radius;
-        reuse_diagonal = 1;
-        continue;
-      }
-      num_invalid = 0;
-
-      // candidate = Plus(x, p): theta + p_0 (lane 0), phi + p_1 (lane 1); EigenQuaternionManifold::Plus on q with
-      // delta = (p_2, p_3, p_4) / 2 (lanes 2, 3, 4)
-      const double hp = 0.5 * p;
-      const double hp2 = hp * hp;
-      double nd2 = 0.0;
-      fmac_row<2>(nd2, hp2, 1.0);
-      fmac_row<3>(nd2, hp2, 1.0);
-      fmac_row<4>(nd2, hp2, 1.0);
-      const double ind = nd2 > 0.0 ? fast_rsqrt(nd2) : 0.0, nd = nd2 * ind;
-      // the three sine / cosine pairs of the step in ONE evaluation: lane 0 theta, lane 1 phi, lane 2 |delta|
-      const double angle = li == 2 ? nd : xang + p;
-      double sa, ca;
-      sincos_bounded(angle, sa, ca);
-      const double st = bcast_row<0>(sa), ct = bcast_row<0>(ca);
-      const double sp = bcast_row<1>(sa), cp = bcast_row<1>(ca);
-      const double aw = bcast_row<2>(ca);
-      double sbd = 0.0;                 // sin|delta| / |delta| (0 for a zero step: qc = x)
-      fmac_row<2>(sbd, sa, ind);
-      double ax = 0.0, ay = 0.0, az = 0.0;
-      fmac_row<2>(ax, hp, sbd);
-      fmac_row<3>(ay, hp, sbd);
-      fmac_row<4>(az, hp, sbd);
-      double qc[4];
-      qc[0] = aw * x[0] + ax * x[3] + ay * x[2] - az * x[1];
-      qc[1] = aw * x[1] - ax * x[2] + ay * x[3] + az * x[0];
-      qc[2] = aw * x[2] + ax * x[1] - ay * x[0] + az * x[3];
-      qc[3] = aw * x[3] - ax * x[0] - ay * x[1] - az * x[2];
-      const double thc = bcast_row<0>(angle), phc = bcast_row<1>(angle);
-      if (writer) {
-        pose_uniforms_sc(st, ct, sp, cp, qc, unif);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) slab[kQc + k] = qc[k];
-        slab[kThetaC] = thc;
-        slab[kPhiC] = phc;
-        slab[kModel] = model_change;
-        ist[kILast] = iteration >= o.max_num_iterations ? 1 : 0;
-      }
-      break;
-    }
-    if (writer) {
-      slab[kInvRadius] = inv_radius;
-      slab[kDec] = dec;
-    }
-  }
-  if (writer) {
-    ist[kIPark] = park;
-    ist[kIIter] = iteration;
-    ist[kIFirst] = (term < 0 || !first) ? 0 : 1;
-    ist[kIReuseDiag] = reuse_diagonal;
-    ist[kINumInvalid] = num_invalid;
-    ist[kIStepOk] = step_ok;
-  }
-  return term;
-}
-
 // ---- PNEC_HIP_OPT_JACOBIAN_NUMERIC_CENTRAL: the reference's own differentiation, for verification --------------------
 // ceres::NumericDiffCostFunction<Functor, CENTRAL, 1, 1, 1, 4> (pnec_ceres.cc:84-97) [EXT, SURVEY Appendix B]: per ambient
 // parameter x_j of (theta, phi, qx, qy, qz, qw): h = max(sqrt(eps), 1e-6 |x_j|), J_j = (r(x + h e_j) - r(x - h e_j)) / 2h;
@@ -1068,22 +774,11 @@ __device__ __forceinline__ void eval_corr_numeric(const double (&e)[num_componen
 
 constexpr int SRC_PLANES = 0;  // the batch's SoA planes in HBM (pnec_hip_problem)
 constexpr int SRC_AOS = 1;     // the caller's arrays in the reference layout (streaming handle)
-// SRC_DUAL (round 5, an A/B form: -DPNEC_SOLVE_DUAL_AB builds + PNEC_SOLVE_DUAL=1; not instantiated otherwise): the batch's planes, TWO one-wavefront solves per block whose LM steps
-// run as ONE instruction stream -- after both wavefronts' passes (a barrier) the first wavefront advances solve 0 in its
-// lanes 0..3 and solve 1 in lanes 4..7 (lm_advance is per-lane code on an LDS slab; its only cross-lane traffic is inside
-// a quad), then a second barrier publishes both candidates.  Per pair of solves and iteration the step's ~400 issue slots
-// are paid once instead of twice; the price is two block barriers per iteration and a wavefront that waits while the
-// other steps.  Same arithmetic per solve, hence the same bits -- and 8.8 % SLOWER on the benchmark (36.68 -> 33.45 M solves/s):
-// the barriers cost more than the shared step saves.  The measured answer to the round-4 review's "one LM step for two
-// solves"; NOTES/round-5.md.
-constexpr int SRC_DUAL = 2;
+// (Two solves per block sharing one LM step were measured 8.8 % slower: the two block barriers per iteration cost more
+// than the shared step saved; NOTES/round-5.md.)
 template <int MODE, int CPL, int WPP, int LDSK, bool RESIDENT, int SRC = SRC_PLANES>
-__global__ __launch_bounds__(kWave *(SRC == SRC_DUAL ? 2 : WPP), (CPL == 8 && LDSK == 0) ? 1 : 2) void lm_solve_kernel(
-    const SolveArgs a) {
+__global__ __launch_bounds__(kWave *WPP, (CPL == 8 && LDSK == 0) ? 1 : 2) void lm_solve_kernel(const SolveArgs a) {
   static_assert(SRC != SRC_AOS || RESIDENT, "the AoS source is only built for the on-chip-resident geometries");
-  constexpr bool DUAL = SRC == SRC_DUAL;
-  static_assert(!DUAL || (WPP == 1 && RESIDENT), "the dual form pairs one-wavefront resident solves");
-  constexpr int NW = DUAL ? 2 : WPP;   // wavefronts of the block
   constexpr int NC = num_components(MODE);
   constexpr int RCPL = CPL > 8 ? 8 : CPL;          // correspondences per lane resident on chip
   constexpr int TAILK = CPL - RCPL;                // ... and re-read from memory in every pass (one wavefront only)
@@ -1091,11 +786,7 @@ __global__ __launch_bounds__(kWave *(SRC == SRC_DUAL ? 2 : WPP), (CPL == 8 && LD
   constexpr int REGK = RESIDENT ? RCPL - LDSK : 1;  // correspondences per lane kept in registers
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = threadIdx.x >> 6;
-  // DUAL: block b holds solves 2 b and 2 b + 1 (of the XCD-contiguous order); an odd batch's last block has one
-  const int64_t slot_raw = DUAL ? 2 * xcd_contiguous_index(blockIdx.x, (a.n_solves + 1) / 2) + (threadIdx.x >> 6)
-                                : xcd_contiguous_index(blockIdx.x, a.n_solves);
-  [[maybe_unused]] const bool exists = !DUAL || slot_raw < a.n_solves;
-  const int64_t slot = exists ? slot_raw : a.n_solves - 1;   // (a wavefront without a solve shadows the last one and writes nothing)
+  const int64_t slot = xcd_contiguous_index(blockIdx.x, a.n_solves);
   const int64_t pair = a.pair_index ? (int64_t)a.pair_index[slot / a.n_hyp] : slot / a.n_hyp;
   const int64_t s = pair * a.n_hyp + slot % a.n_hyp;
   const double *__restrict__ base = nullptr;
@@ -1119,16 +810,13 @@ __global__ __launch_bounds__(kWave *(SRC == SRC_DUAL ? 2 : WPP), (CPL == 8 && LD
   // the others wait at the block's barrier -- their SIMDs run other solves' wavefronts meanwhile.  (Until round 2
   // every wavefront kept a copy and advanced it identically to save that barrier: WPP x the ~400 instructions
   // of the step per iteration, 18 % of a two-wavefront solve's issue slots, 28 % of an eight-wavefront one's.)
-  __shared__ double slab_all[NW][kSlab];
-  __shared__ double unif_all[NW][kUnif];
-  __shared__ int ist_all[NW][kINumI];
-#ifdef PNEC_ADVANCE_ROWS
-  __shared__ int gidx_all[1][16 * kGatherInts];  // lm_advance_rows: each lane's row of the tables of sums
-#endif
+  __shared__ double slab_all[WPP][kSlab];
+  __shared__ double unif_all[WPP][kUnif];
+  __shared__ int ist_all[WPP][kINumI];
   [[maybe_unused]] __shared__ double xw[2][WPP > 1 ? WPP : 1][kSumSlots];
   [[maybe_unused]] __shared__ double nunif[RESIDENT ? 1 : kNumPoses][12];   // numeric Jacobian: R | t of the perturbed poses
   [[maybe_unused]] __shared__ double ninv2h[8];
-  [[maybe_unused]] __shared__ double ldata[LDSK > 0 ? NW : 1][LDSK > 0 ? LDSK : 1][NC][LDSK > 0 ? kWave : 1];
+  [[maybe_unused]] __shared__ double ldata[LDSK > 0 ? WPP : 1][LDSK > 0 ? LDSK : 1][NC][LDSK > 0 ? kWave : 1];
   double *slab = slab_all[WPP > 1 ? 0 : wave];
   double *unif = unif_all[WPP > 1 ? 0 : wave];
   int *ist = ist_all[WPP > 1 ? 0 : wave];
@@ -1141,13 +829,13 @@ __global__ __launch_bounds__(kWave *(SRC == SRC_DUAL ? 2 : WPP), (CPL == 8 && LD
                                      NC >= 18 ? a.aos_covs_host + 9 * aos0 : nullptr, n, wave * RCPL * kWave, lane, d,
                                      &ldata[LDSK > 0 ? wave : 0][0][0][0]);
   else if constexpr (RESIDENT)
-    load_resident<NC, RCPL, REGK>(base, n, stride, (DUAL ? 0 : wave) * RCPL * kWave, lane, d, &ldata[LDSK > 0 ? wave : 0][0][0][0]);
+    load_resident<NC, RCPL, REGK>(base, n, stride, wave * RCPL * kWave, lane, d, &ldata[LDSK > 0 ? wave : 0][0][0][0]);
   // how many of this wavefront's CPL slots hold any correspondence of the pair (wave-uniform): slot k
   // starts at correspondence first + 128 (k / 2) + (k & 1) (load_resident), lane 0 being the first
   [[maybe_unused]] int nslots = 0;
   if constexpr (RESIDENT) {
 #pragma unroll
-    for (int k = 0; k < RCPL; ++k) nslots += (n > (DUAL ? 0 : wave) * RCPL * kWave + slot_corr<RCPL, REGK>(k, 0)) ? 1 : 0;
+    for (int k = 0; k < RCPL; ++k) nslots += (n > wave * RCPL * kWave + slot_corr<RCPL, REGK>(k, 0)) ? 1 : 0;
   }
   // The tail (TAILK = 4): correspondences 512 .. 767 as the SECOND wavefront of (8, 2, 3) would hold them in its first
   // four register slots -- tail slot t <-> 512 + 128 (t / 2) + 2 lane + (t & 1) -- accumulated from zero in that order,
@@ -1180,9 +868,6 @@ __global__ __launch_bounds__(kWave *(SRC == SRC_DUAL ? 2 : WPP), (CPL == 8 && LD
   // Everything that is one value per solve runs in a few lanes only (here lane 0, lm_advance on
   // a quad) against the LDS slab: not faster to issue (measured), but one copy of the state and
   // plain per-lane control flow instead of wave-uniform bookkeeping in scalar registers.
-#ifdef PNEC_ADVANCE_ROWS
-  if (WPP == 1 || wave == 0) gather_index_init(gidx_all[0], lane);
-#endif
   if (lane == 0 && (WPP == 1 || wave == 0)) {
     double th, ph;
     const double *t0 = a.hyp_t ? a.hyp_t + 3 * s : a.init_t + 3 * pair;
@@ -1203,19 +888,16 @@ __global__ __launch_bounds__(kWave *(SRC == SRC_DUAL ? 2 : WPP), (CPL == 8 && LD
     ist[kIStepOk] = 1;
     ist[kILast] = o.max_num_iterations <= 0 ? 1 : 0;
     ist[kIPark] = 0;
-    if constexpr (DUAL) ist[kITerm] = exists ? -1 : PNEC_HIP_TERM_MAX_ITERATIONS;   // (>= 0: this slot is done -- or was never there)
   }
   const double inv_max_radius = a.inv_max_radius, inv_min_radius = a.inv_min_radius;  // kernel arguments: scalar
   // the LDS slots arrive by DMA (vmcnt-tracked): they must have landed before the first pass reads them
   if constexpr (RESIDENT && LDSK > 0 && SRC != SRC_AOS) __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  if constexpr (WPP > 1 || DUAL) __syncthreads();  // the first wavefront's start state is what all of them read
+  if constexpr (WPP > 1) __syncthreads();  // the first wavefront's start state is what all of them read
 
   int term;
-  [[maybe_unused]] bool alive = exists;      // DUAL: this wavefront's solve still iterates (wave-uniform)
   int n_full_passes = 0, n_cost_passes = 0;  // wave-uniform (diagnostics: SolveArgs::work)
   for (;;) {
-    if (!DUAL || alive) {
     // ---- one fused pass at the candidate: sum r^2, J'r, J'J ------------------------------
     PNEC_MARK("uniforms");
     {
@@ -1387,53 +1069,22 @@ __global__ __launch_bounds__(kWave *(SRC == SRC_DUAL ? 2 : WPP), (CPL == 8 && LD
       }
     }
 
-    }  // (DUAL: the wavefront of a finished solve only keeps the barriers' count)
-
     // ---- accept / reject, trust region, next candidate: one lane
     PNEC_MARK("advance");
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     int t = -1;
-    if constexpr (DUAL) {
-      __syncthreads();   // both solves' sums are in their slabs
-      if (wave == 0) {
-        __builtin_amdgcn_s_setprio(3);
-        if (lane < 8) {   // lanes 0..3: solve 0, lanes 4..7: solve 1 -- one instruction stream for both steps
-          const int sv = lane >> 2;
-          if (ist_all[sv][kITerm] < 0) {
-            t = lm_advance<RESIDENT && kCostFirst>(slab_all[sv], ist_all[sv], unif_all[sv], o, inv_max_radius, inv_min_radius);
-            if ((lane & 3) == 0) ist_all[sv][kITerm] = t;
-          }
-        }
-        __builtin_amdgcn_s_setprio(0);
-      }
-      __syncthreads();   // the next candidates (or the verdicts) are published
-      // both wavefronts read both verdicts (written before the barrier): the loop ends for both in the same trip
-      const int t0_ = to_sgpr(ist_all[0][kITerm]), t1_ = to_sgpr(ist_all[1][kITerm]);
-      term = wave == 0 ? t0_ : t1_;
-      if (term >= 0) alive = false;
-      if (t0_ >= 0 && t1_ >= 0) break;
-      continue;
-    }
     // the chain below is latency-bound: let it win the issue arbitration against the pass of the
     // other wavefront on this SIMD, which has independent work to fill the gaps (+1.2 %)
     if constexpr (WPP == 1) {
       __builtin_amdgcn_s_setprio(3);
-#ifndef PNEC_ADVANCE_ROWS
-      if (lane < 4) t = lm_advance<RESIDENT && kCostFirst>(slab, ist, unif, o, inv_max_radius, inv_min_radius);  // one quad, identical work (see the sincos exchange)
-#else
-      t = lm_advance_rows(slab, ist, unif, gidx_all[0], o, inv_max_radius, inv_min_radius, lane);  // every lane: one component per lane
-#endif
+      if (lane < 4) t = lm_advance<RESIDENT>(slab, ist, unif, o, inv_max_radius, inv_min_radius);  // one quad, identical work (see the sincos exchange)
       term = to_sgpr(t);
       __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     } else {
       if (wave == 0) {
         __builtin_amdgcn_s_setprio(3);
-#ifndef PNEC_ADVANCE_ROWS
-        if (lane < 4) t = lm_advance<RESIDENT && kCostFirst>(slab, ist, unif, o, inv_max_radius, inv_min_radius);
-#else
-        t = lm_advance_rows(slab, ist, unif, gidx_all[0], o, inv_max_radius, inv_min_radius, lane);
-#endif
+        if (lane < 4) t = lm_advance<RESIDENT>(slab, ist, unif, o, inv_max_radius, inv_min_radius);
         if (lane == 0) ist[kITerm] = t;
         __builtin_amdgcn_s_setprio(0);
       }
@@ -1444,7 +1095,7 @@ __global__ __launch_bounds__(kWave *(SRC == SRC_DUAL ? 2 : WPP), (CPL == 8 && LD
   }
 
   PNEC_MARK("result");
-  if (DUAL ? (lane == 0 && exists) : threadIdx.x == 0) {
+  if (threadIdx.x == 0) {
     write_result(a, s, slab, ist[kIIter], term);
     if (a.work) {
       atomicAdd(a.work + 0, (unsigned long long)n_full_passes * (unsigned long long)n);
