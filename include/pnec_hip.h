@@ -20,6 +20,8 @@
  *   ceres::Solver::Options (default-constructed, pnec_ceres.cc:47)   pnec_hip_options
  *   pnec::common::CostFunction  src/common/common.cc:237-259    pnec_hip_cost_function
  *   pnec::common::UnscentedTransform / Unproject  common.cc:460-525   pnec_hip_unscented_transform
+ *   (no counterpart: what ceres::Covariance would give for the        pnec_hip_pose_covariance
+ *    problems of pnec_ceres.cc / nec_ceres.cc)
  *   PNEC::Eigensolver (no RANSAC) / WeightedEigensolver  pnec.cc:231-348   pnec_hip_nec_eigensolver /
  *                                                               pnec_hip_weighted_eigensolver
  *
@@ -45,7 +47,7 @@
 extern "C" {
 #endif
 
-#define PNEC_HIP_ABI_VERSION 7
+#define PNEC_HIP_ABI_VERSION 8
 #define PNEC_HIP_MAX_RANSAC_SAMPLE 16 /* largest Options::ransac_sample_size_ the RANSAC kernel is built for */
 
 typedef enum pnec_hip_status {
@@ -254,6 +256,58 @@ int pnec_hip_select_best(int64_t n_pairs, int32_t n_hyp, const double *cost, int
  * normalised inside) and t.  Only for TARGET-mode problems.  out [n_pairs]. */
 int pnec_hip_cost_function(pnec_hip_problem *p, const double *q, const double *t, double *out,
                            int space, void *stream);
+
+/* Pose covariance: the uncertainty of a relative pose, from one pass over the pair at a pose the caller passes in
+ * (usually pnec_hip_solve's out_q / out_t; a RANSAC, eigensolver or ground-truth pose works the same way).
+ *
+ * Definition.  With r_i the residuals of the problem's family at (q, t) and J their Jacobian, the Gauss-Newton
+ * information matrix is H = J'J.  The probabilistic residuals (TARGET, HOST, SYM) are whitened by the propagated
+ * variance, so at the minimum H^-1 is the posterior covariance of the pose (Laplace approximation; what
+ * ceres::Covariance returns for the reference's problem).  The NEC residual is NOT whitened: its out_cov is the
+ * covariance for unit residual variance and means something only after the caller multiplies it by the variance
+ * factor 2 out_cost / (n - 5).  The call never applies that factor.
+ *
+ * Poses.  q [n_pairs * n_hyp, 4] xyzw (normalised inside, as pnec_hip_cost_function does), t [n_pairs * n_hyp, 3]
+ * (any length > 0; used as a direction), slot s = pair * n_hyp + h is evaluated on pair s / n_hyp.  The spherical
+ * angles of t are those of AnglesFromVec (src/common/common.cc:103-116): theta = acos(t_z / |t|), phi = atan2(t_y,
+ * t_x), and phi = 0 where theta < 1e-10 or t_x = t_y = 0.  `reg` is the regularisation of the residual (the value
+ * given to pnec_hip_solve).
+ *
+ * Charts.  With b_theta = dt/dtheta = (cos th cos ph, cos th sin ph, -sin th) and e_phi = (-sin ph, cos ph, 0) -- an
+ * orthonormal basis of the tangent plane of the unit sphere at t -- the pass differentiates in
+ *     x = (tau_1, tau_2, omega_x, omega_y, omega_z):  t <- normalize(t + tau_1 b_theta + tau_2 e_phi),
+ *                                                     R <- Exp(omega) R   (LEFT perturbation, radians)
+ * which, unlike the reference's (theta, phi), is not singular for forward motion t ~ (0, 0, 1).
+ *
+ * Outputs, per slot; every pointer may be NULL (not wanted), not all of them:
+ *   out_info [15]   upper triangle, row by row ((0,0) (0,1) .. (0,4) (1,1) .. (4,4)), of J'J in the CERES TANGENT
+ *                   SPACE of the reference's problem: (theta, phi, delta_x, delta_y, delta_z) with the manifolds of
+ *                   pnec_ceres.cc -- t = (sin th cos ph, sin th sin ph, cos th), EigenQuaternionManifold's delta =
+ *                   omega / 2.  It is D H_x D with D = diag(1, sin theta, 2, 2, 2): exactly 0 in row / column phi at
+ *                   theta = 0.
+ *   out_cov  [36]   row-major symmetric 6x6 covariance of (omega_x, omega_y, omega_z, t_x, t_y, t_z): the rotation
+ *                   vector of a left perturbation R <- Exp(omega) R in radians, and the unit translation direction as
+ *                   a vector of R^3.  Sigma_6 = L H_x^-1 L', L = blockdiag(I_3, [b_theta e_phi]): rank 5, t spans its
+ *                   null space (the length of t is not observable).
+ *   out_grad [5]    J'r in the Ceres tangent space (first-order optimality at the passed pose).
+ *   out_cost [1]    1/2 sum r^2.
+ *   out_status [1]  pnec_hip_cov_status.  PNEC_HIP_COV_SINGULAR: fewer than 5 correspondences or a non-positive pivot
+ *                   in the factorisation -- out_cov is all NaN, the other outputs are written as usual;
+ *                   PNEC_HIP_COV_NONFINITE: a sum is Inf / NaN (NaN input) -- out_cov all NaN, the others hold what
+ *                   the arithmetic gave.  A slot's outputs depend on its own pair and pose only.
+ *
+ * All four problem modes; batches made by pnec_hip_problem_select(_view) and reshaped capacity batches included.
+ * `space` as in pnec_hip_cost_function: HOST pointers are staged and the call blocks, DEVICE pointers make the call
+ * asynchronous on `stream`.  NULL problem / q / t, n_hyp < 1 or all outputs NULL: PNEC_HIP_ERR_INVALID_ARGUMENT
+ * before any device is touched. */
+typedef enum pnec_hip_cov_status {
+  PNEC_HIP_COV_OK = 0,
+  PNEC_HIP_COV_SINGULAR = 1,
+  PNEC_HIP_COV_NONFINITE = 2
+} pnec_hip_cov_status;
+int pnec_hip_pose_covariance(pnec_hip_problem *p, const double *q, const double *t, int32_t n_hyp, double reg,
+                             double *out_info, double *out_cov, double *out_grad, double *out_cost,
+                             int32_t *out_status, int space, void *stream);
 
 /* PNEC::Eigensolver with use_ransac_ = false (src/rel_pose_estimation/pnec.cc:273-278) for every
  * pair: rotation by opengv-style eigenvalue minimisation (Kneip-Lynen; opengv is not in the

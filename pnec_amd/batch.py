@@ -7,7 +7,7 @@ torch is plumbing here (device memory, streams); all arithmetic is in libpnec_hi
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 
 import numpy as np
 
@@ -26,6 +26,16 @@ class SolveResult:
     cost: object        # [S]   1/2 sum r^2 at the returned point
     iterations: object  # [S]   int32
     status: object      # [S]   int32, capi.TERM_NAMES
+    # the solve that produced it (Batch.solve fills these in; covariance() needs them)
+    batch: object = field(default=None, repr=False, compare=False)
+    reg: float = field(default=1e-13, repr=False, compare=False)
+    n_hyp: int = field(default=1, repr=False, compare=False)
+
+    def covariance(self) -> "PoseCovariance":
+        """Batch.pose_covariance at this result's own poses, with the `reg` and `n_hyp` of the solve it came from."""
+        if self.batch is None:
+            raise ValueError("this SolveResult was not produced by Batch.solve: call Batch.pose_covariance(q, t)")
+        return self.batch.pose_covariance(self.q, self.t, reg=self.reg, n_hyp=self.n_hyp)
 
     def rotation_matrices(self):
         """[S,3,3] from q (numpy or torch, matching the stored arrays)."""
@@ -38,6 +48,71 @@ class SolveResult:
             xp.stack([2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], -1),
         ], -2)
         return R
+
+
+_TRI5 = tuple((a, b) for a in range(5) for b in range(a, 5))  # the ABI's packed order of a symmetric 5x5
+
+
+_FULL5 = tuple(min(a, b) * 5 - min(a, b) * (min(a, b) - 1) // 2 + abs(a - b) for a in range(5) for b in range(5))
+_full5_on = {}   # torch device -> _FULL5 as an index tensor there (made once: no upload per call)
+
+
+def expand_info(packed):
+    """[..., 15] packed upper triangles (pnec_hip_pose_covariance's out_info) -> [..., 5, 5] full symmetric matrices."""
+    if _is_torch(packed):
+        import torch
+        idx = _full5_on.get(packed.device)
+        if idx is None:
+            idx = _full5_on[packed.device] = torch.tensor(_FULL5, device=packed.device)
+        return packed.index_select(-1, idx).reshape(tuple(packed.shape[:-1]) + (5, 5))
+    packed = np.asarray(packed)
+    return packed[..., list(_FULL5)].reshape(packed.shape[:-1] + (5, 5))
+
+
+def chart_basis(t):
+    """(b_theta, e_phi, sin theta) of the translation direction t [3] as pnec_hip_pose_covariance defines them
+    (include/pnec_hip.h): the orthonormal basis of t's tangent plane the 6x6 covariance is lifted with."""
+    t = np.asarray(t, dtype=np.float64)
+    n = np.linalg.norm(t)
+    rho = np.hypot(t[0], t[1])
+    st, ct = (rho / n, t[2] / n) if n > 0 else (0.0, 1.0)
+    if rho == 0.0 or (st < 1e-10 and ct > 0.0):
+        cp, sp = 1.0, 0.0
+    else:
+        cp, sp = t[0] / rho, t[1] / rho
+    return np.array([ct * cp, ct * sp, -st]), np.array([-sp, cp, 0.0]), st
+
+
+def cov6_to_ceres_chart(cov6, t):
+    """Sigma_6 (omega, t) -> the 5x5 covariance of the Ceres tangent space (theta, phi, delta_xyz) at t: the inverse of
+    `info` where sin theta != 0.  theta = b_theta . dt, phi = e_phi . dt / sin theta, delta = omega / 2."""
+    bth, eph, st = chart_basis(t)
+    T = np.zeros((5, 6))
+    T[0, 3:] = bth
+    T[1, 3:] = eph / st
+    T[2:, :3] = 0.5 * np.eye(3)
+    return T @ np.asarray(cov6) @ T.T
+
+
+def ceres_chart_to_cov6(cov5, t):
+    """The inverse map: a 5x5 covariance of (theta, phi, delta_xyz) at t -> Sigma_6 (omega, t)."""
+    bth, eph, st = chart_basis(t)
+    Lm = np.zeros((6, 5))
+    Lm[3:, 0] = bth
+    Lm[3:, 1] = eph * st
+    Lm[:3, 2:] = 2.0 * np.eye(3)
+    return Lm @ np.asarray(cov5) @ Lm.T
+
+
+@dataclass
+class PoseCovariance:
+    """Per pose slot (pair-major, hypothesis-minor): pnec_hip_pose_covariance's outputs (include/pnec_hip.h has the
+    chart conventions).  NEC-mode batches: `cov` is for unit residual variance; scale it by 2 cost / (n - 5)."""
+    cov: object     # [S,6,6] covariance of (omega_xyz [rad, left perturbation], t_xyz [unit direction]); rank 5
+    info: object    # [S,5,5] J'J in the Ceres tangent space (theta, phi, delta_xyz), full symmetric
+    grad: object    # [S,5]   J'r in the same space
+    cost: object    # [S]     1/2 sum r^2
+    status: object  # [S]     int32, capi.COV_NAMES
 
 
 class Batch:
@@ -329,6 +404,7 @@ class Batch:
             self._h, p(init_q), p(init_t), int(n_hyp), p(hyp_t), float(reg),
             C.byref(options) if options is not None else None, p(out.q), p(out.t), p(out.cost),
             p(out.iterations), p(out.status), space, stream))
+        out.batch, out.reg, out.n_hyp = self, float(reg), int(n_hyp)
         return out
 
     def _front(self, weighted, init_q, init_t, reg, weighted_iterations):
@@ -494,6 +570,38 @@ class Batch:
         capi.check(self._lib.pnec_hip_cost_function(self._h, q.ctypes.data, t.ctypes.data,
                                                     out.ctypes.data, capi.MEM_HOST, None))
         return out
+
+
+    def pose_covariance(self, q, t, reg: float = 1e-13, n_hyp: int = 1) -> PoseCovariance:
+        """6x6 covariance, Ceres-chart information, gradient and cost of every pair at the poses passed in: q [S,4]
+        xyzw, t [S,3], S = n_pairs * n_hyp (pnec_hip_pose_covariance).  torch.cuda tensors in -> torch.cuda tensors out,
+        asynchronous on torch's current stream; numpy in -> numpy out."""
+        n_hyp = int(n_hyp)
+        if n_hyp < 1:
+            raise ValueError("n_hyp must be >= 1")
+        S = self.n_pairs * n_hyp
+        if _is_torch(q):
+            import torch
+            q = self._dev_tensor(q, "q", (S, 4))
+            t = self._dev_tensor(t, "t", (S, 3))
+            f64 = dict(dtype=torch.float64, device=q.device)
+            cov, info = torch.empty((S, 6, 6), **f64), torch.empty((S, 15), **f64)
+            grad, cost = torch.empty((S, 5), **f64), torch.empty((S,), **f64)
+            status = torch.empty((S,), dtype=torch.int32, device=q.device)
+            p = lambda a: a.data_ptr()
+            space, stream = capi.MEM_DEVICE, torch.cuda.current_stream(self.device).cuda_stream
+        else:
+            q = np.ascontiguousarray(q, dtype=np.float64)
+            t = np.ascontiguousarray(t, dtype=np.float64)
+            if q.shape != (S, 4) or t.shape != (S, 3):
+                raise ValueError("q must be [n_pairs*n_hyp,4] (xyzw), t [n_pairs*n_hyp,3]")
+            cov, info, grad, cost = np.empty((S, 6, 6)), np.empty((S, 15)), np.empty((S, 5)), np.empty(S)
+            status = np.empty(S, dtype=np.int32)
+            p = lambda a: a.ctypes.data
+            space, stream = capi.MEM_HOST, None
+        capi.check(self._lib.pnec_hip_pose_covariance(self._h, p(q), p(t), n_hyp, float(reg), p(info), p(cov), p(grad),
+                                                      p(cost), p(status), space, stream))
+        return PoseCovariance(cov, expand_info(info), grad, cost, status)
 
 
 def select_best(cost, n_hyp: int, device: int = 0):

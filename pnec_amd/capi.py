@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # PNEC_HIP_LIB: load an alternative build of the same ABI (kernel A/B experiments only)
 LIB_PATH = os.environ.get("PNEC_HIP_LIB") or os.path.join(_HERE, "libpnec_hip.so")
 
-ABI_VERSION = 7  # PNEC_HIP_ABI_VERSION of include/pnec_hip.h this binding was written against
+ABI_VERSION = 8  # PNEC_HIP_ABI_VERSION of include/pnec_hip.h this binding was written against
 MODE_NEC, MODE_TARGET, MODE_HOST, MODE_SYM = 0, 1, 2, 3
 MEM_HOST, MEM_DEVICE = 0, 1
 # pnec_hip_eigensolver_scheme: which iteration stands in for opengv's eigenvalue minimisation (include/pnec_hip.h)
@@ -31,6 +31,9 @@ TERM_NAMES = {
     6: "bad_initial_point",
 }
 TERM_MAX_ITERATIONS = 3  # PNEC_HIP_TERM_MAX_ITERATIONS
+# pnec_hip_cov_status (pnec_hip_pose_covariance's out_status)
+COV_OK, COV_SINGULAR, COV_NONFINITE = 0, 1, 2
+COV_NAMES = {COV_OK: "ok", COV_SINGULAR: "singular_information", COV_NONFINITE: "non_finite_sums"}
 NUM_COMPONENTS = {MODE_NEC: 6, MODE_TARGET: 12, MODE_HOST: 12, MODE_SYM: 18}
 
 # every symbol include/pnec_hip.h declares (tests check the library exports all of them)
@@ -59,6 +62,7 @@ SYMBOLS = [
     "pnec_hip_solve",
     "pnec_hip_select_best",
     "pnec_hip_cost_function",
+    "pnec_hip_pose_covariance",
     "pnec_hip_nec_eigensolver",
     "pnec_hip_ransac_eigensolver",
     "pnec_hip_problem_select",
@@ -204,6 +208,7 @@ def lib() -> C.CDLL:
                                  _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]
     L.pnec_hip_select_best.argtypes = [C.c_int64, C.c_int32, _vp, _vp, C.c_int, C.c_int, _vp]
     L.pnec_hip_cost_function.argtypes = [_vp, _vp, _vp, _vp, C.c_int, _vp]
+    L.pnec_hip_pose_covariance.argtypes = [_vp, _vp, _vp, C.c_int32, C.c_double, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]
     L.pnec_hip_describe_launch.argtypes = [_vp, C.POINTER(Options)] + [C.POINTER(C.c_int32)] * 5
     L.pnec_hip_unscented_transform.argtypes = [C.c_int64, _vp, _vp, _vp, C.c_double, C.c_int, _vp, _vp,
                                                C.c_int, C.c_int, _vp]

@@ -167,8 +167,20 @@ int main(int argc, char **argv) {
   const double e1 = pnec::common::RotationalDifference(sol.rotationMatrix(), Rgt);
   const double te = pnec::common::TranslationalDifference(sol.translation(), tgt);
   const double cost = pnec::common::CostFunction(b1, b2, covs, sol);
-  std::printf("n=%d inliers=%zu rot_err_init_deg=%.6f rot_err_deg=%.6f t_err_deg=%.6f cost=%.6f\n", n,
-              inliers.size(), e0, e1, te, cost);
+  // 1-sigma uncertainty of the solve from the correspondences it kept: sqrt(trace) of the rotation block (radians of
+  // a left perturbation) and of the translation block (the direction is a unit vector: radians too)
+  pnec::bearingVectors_t ib1, ib2;
+  std::vector<pnec::Matrix3d> icovs;
+  for (int i : inliers) {
+    ib1.push_back(b1[i]);
+    ib2.push_back(b2[i]);
+    icovs.push_back(covs[i]);
+  }
+  const pnec::Matrix6d S = pnec::common::PoseCovariance(ib1, ib2, icovs, sol);
+  const double kDeg = 180.0 / 3.14159265358979323846;
+  const double rot_sigma = std::sqrt(S(0, 0) + S(1, 1) + S(2, 2)) * kDeg, t_sigma = std::sqrt(S(3, 3) + S(4, 4) + S(5, 5)) * kDeg;
+  std::printf("n=%d inliers=%zu rot_err_init_deg=%.6f rot_err_deg=%.6f t_err_deg=%.6f cost=%.6f rot_sigma_deg=%.6f "
+              "t_sigma_deg=%.6f\n", n, inliers.size(), e0, e1, te, cost, rot_sigma, t_sigma);
   if (argc > 3 && std::strcmp(argv[2], "dump") == 0) {
     // everything a checker needs to repeat this call elsewhere: inputs, start pose, result, inliers
     // (text, %.17g: doubles round-trip exactly)

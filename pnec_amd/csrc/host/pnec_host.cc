@@ -219,6 +219,38 @@ double CostFunction(const bearingVectors_t &bvs_1, const bearingVectors_t &bvs_2
   return out;
 }
 
+namespace {
+Matrix6d PoseCovarianceImpl(int mode, const bearingVectors_t &bvs_1, const bearingVectors_t &bvs_2,
+                            const std::vector<Matrix3d> &covs, const std::vector<Matrix3d> *covs_host,
+                            const SE3d &camera_pose, double regularization) {
+  if (bvs_1.size() != bvs_2.size() || bvs_1.size() != covs.size() || (covs_host && covs_host->size() != covs.size()))
+    throw std::invalid_argument("bvs_1, bvs_2 and covs differ in size");
+  Matrix6d out;
+  if (bvs_1.empty()) {   // no information at all
+    for (double &v : out.m) v = std::nan("");
+    return out;
+  }
+  const std::vector<int64_t> offsets = {0, (int64_t)bvs_1.size()};
+  Problem prob(optimization::SolverOptions().device, mode, offsets);
+  Check(pnec_hip_problem_fill(prob.p, 0, 1, bvs_1[0].data(), bvs_2[0].data(), covs[0].data(),
+                              covs_host ? (*covs_host)[0].data() : nullptr, PNEC_HIP_MEM_HOST, nullptr));
+  const Quaterniond q(camera_pose.rotationMatrix());
+  // (symmetric: the ABI's row-major 6x6 is the column-major one)
+  Check(pnec_hip_pose_covariance(prob.p, q.coeffs(), camera_pose.translation().data(), 1, regularization, nullptr,
+                                 out.data(), nullptr, nullptr, nullptr, PNEC_HIP_MEM_HOST, nullptr));
+  return out;
+}
+}  // namespace
+
+Matrix6d PoseCovariance(const bearingVectors_t &bvs_1, const bearingVectors_t &bvs_2, const std::vector<Matrix3d> &covs,
+                        const SE3d &camera_pose, double regularization) {
+  return PoseCovarianceImpl(PNEC_HIP_MODE_TARGET, bvs_1, bvs_2, covs, nullptr, camera_pose, regularization);
+}
+Matrix6d PoseCovariance(const bearingVectors_t &bvs_1, const bearingVectors_t &bvs_2, const std::vector<Matrix3d> &covs_1,
+                        const std::vector<Matrix3d> &covs_2, const SE3d &camera_pose, double regularization) {
+  return PoseCovarianceImpl(PNEC_HIP_MODE_SYM, bvs_1, bvs_2, covs_2, &covs_1, camera_pose, regularization);
+}
+
 std::ostream &operator<<(std::ostream &os, const FrameTiming &ft) {
   const long fields[] = {(long)ft.id_,    ft.frame_loading_, ft.feature_creation_,      ft.nec_es_,
                          ft.it_es_,       ft.avg_it_es_,     ft.ceres_,

@@ -91,6 +91,18 @@ std::ostream &operator<<(std::ostream &os, const Timing &timing);
 double CostFunction(const bearingVectors_t &bvs_1, const bearingVectors_t &bvs_2,
                     const std::vector<Matrix3d> &covs, const SE3d &camera_pose);
 
+// Addition (the reference has no such function): the 6x6 covariance of camera_pose given the correspondences --
+// pnec_hip_pose_covariance for one pair, include/pnec_hip.h has the conventions: rows / columns (omega_x, omega_y,
+// omega_z, t_x, t_y, t_z), omega the rotation vector of a LEFT perturbation R <- Exp(omega) R in radians, t the unit
+// translation direction (rank 5: the length of t is not observable).  The inverse of the Gauss-Newton information of
+// the PNEC residual (pnec_residual.h:50-150, target-frame covariances) at the pose; what ceres::Covariance would
+// give for PNECCeres' problem.  Fewer than 5 correspondences or a singular information matrix: all NaN.
+Matrix6d PoseCovariance(const bearingVectors_t &bvs_1, const bearingVectors_t &bvs_2, const std::vector<Matrix3d> &covs,
+                        const SE3d &camera_pose, double regularization = 1e-13);
+// the symmetric residual (pnec_residual.h:111-150): covariances of both frames
+Matrix6d PoseCovariance(const bearingVectors_t &bvs_1, const bearingVectors_t &bvs_2, const std::vector<Matrix3d> &covs_1,
+                        const std::vector<Matrix3d> &covs_2, const SE3d &camera_pose, double regularization = 1e-13);
+
 }  // namespace common
 
 namespace optimization {

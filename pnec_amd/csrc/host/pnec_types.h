@@ -80,6 +80,16 @@ struct Matrix3d {
   double *data() { return m; }
 };
 
+// column-major 6x6 (element (r,c) at m[6*c + r]), like Eigen::Matrix<double, 6, 6>
+struct Matrix6d {
+  double m[36] = {};
+  double &operator()(int r, int c) { return m[6 * c + r]; }
+  double operator()(int r, int c) const { return m[6 * c + r]; }
+  static Matrix6d Zero() { return Matrix6d(); }
+  const double *data() const { return m; }
+  double *data() { return m; }
+};
+
 // storage x,y,z,w (Eigen::Quaterniond::coeffs()); constructor order w,x,y,z like Eigen
 struct Quaterniond {
   double c[4] = {0.0, 0.0, 0.0, 1.0};

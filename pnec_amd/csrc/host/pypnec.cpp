@@ -203,6 +203,16 @@ double cost_function(arr bvs1, arr bvs2, arr covs, arr pose) {
                                     ToCovariances(covs, "covs"), ToPose(pose));
 }
 
+py::array_t<double> pose_covariance(arr bvs1, arr bvs2, arr covs, arr pose, double regularization) {
+  const pnec::Matrix6d C = pnec::common::PoseCovariance(ToBearings(bvs1, "bvs_1"), ToBearings(bvs2, "bvs_2"),
+                                                        ToCovariances(covs, "covs"), ToPose(pose), regularization);
+  py::array_t<double> out({6, 6});
+  auto o = out.mutable_unchecked<2>();
+  for (int r = 0; r < 6; ++r)
+    for (int c = 0; c < 6; ++c) o(r, c) = C(r, c);
+  return out;
+}
+
 // PNEC::Solve for ONE frame pair through the overload asked for (pnec.cc:69-75, :77-124, :126-134,
 // :135-208): overload 0 = (bvs1, bvs2, covs, init), 1 = (+ inliers), 2 = (+ timing), 3 = (+ inliers,
 // timing).  Returns (pose 4x4, inliers or None, timing dict or None).
@@ -281,6 +291,10 @@ PYBIND11_MODULE(pypnec, m) {
   m.def("translational_difference", &translational_difference, py::arg("translation_1"), py::arg("translation_2"),
         py::arg("both_directions") = true, "pnec::common::TranslationalDifference (degrees)");
   m.def("cost_function", &cost_function, "pnec::common::CostFunction (device)");
+  m.def("pose_covariance", &pose_covariance, py::arg("bvs1"), py::arg("bvs2"), py::arg("covs"), py::arg("pose"),
+        py::arg("regularization") = 1e-13,
+        "pnec::common::PoseCovariance (addition; device): 6x6 covariance of (omega_xyz [left perturbation, rad], t_xyz "
+        "[unit direction]) at `pose` -- include/pnec_hip.h pnec_hip_pose_covariance");
   m.def("solve", &solve, py::arg("bvs1"), py::arg("bvs2"), py::arg("covs"), py::arg("init_pose"),
         py::arg("overload") = 1, py::arg("use_ransac") = true, py::arg("use_nec") = false,
         py::arg("use_ceres") = true, py::arg("weighted_iterations") = 10, py::arg("regularization") = 1e-13,

@@ -18,6 +18,7 @@
 
 #include "pnec_device.hpp"
 #include "pnec_front_shared.hpp"
+#include "pnec_pose_cov.hpp"
 #include "pnec_solve_kernel.hpp"
 #include "pnec_solve_group_kernel.hpp"
 
@@ -1776,6 +1777,67 @@ int pnec_hip_cost_function(pnec_hip_problem *p, const double *q, const double *t
   PNEC_HIP_TRY(hipGetLastError());
   if (space == PNEC_HIP_MEM_HOST) {
     PNEC_HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(double) * P, hipMemcpyDeviceToHost, stream));
+    PNEC_HIP_TRY(hipStreamSynchronize(stream));
+  }
+  return 0;
+}
+
+// J'J, its lifted inverse, J'r and the cost of every (pair, pose) slot: pnec_pose_cov.hip
+int pnec_hip_pose_covariance(pnec_hip_problem *p, const double *q, const double *t, int32_t n_hyp, double reg,
+                             double *out_info, double *out_cov, double *out_grad, double *out_cost,
+                             int32_t *out_status, int space, void *stream_) {
+  if (!p) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "pose_covariance: problem is NULL");
+  if (!q || !t) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "pose_covariance: q or t is NULL");
+  if (n_hyp < 1) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "pose_covariance: n_hyp must be >= 1");
+  if (!out_info && !out_cov && !out_grad && !out_cost && !out_status)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "pose_covariance: every output is NULL");
+  if (space != PNEC_HIP_MEM_DEVICE && space != PNEC_HIP_MEM_HOST)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "bad memory space");
+  const int64_t S = p->n_pairs * (int64_t)n_hyp;
+  if (S == 0) return 0;
+  if (S > 0x7fffffffLL) return fail(PNEC_HIP_ERR_UNSUPPORTED, "more than 2^31-1 poses in one call");
+  DeviceGuard guard(p->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  PoseCovArgs a;
+  a.data = p->d_data;
+  a.block_offset = p->d_block_offset;
+  a.count = p->d_count;
+  a.n_hyp = n_hyp;
+  a.reg = reg;
+  if (space == PNEC_HIP_MEM_DEVICE) {
+    a.q = q;
+    a.t = t;
+    a.out_info = out_info;
+    a.out_cov = out_cov;
+    a.out_grad = out_grad;
+    a.out_cost = out_cost;
+    a.out_status = out_status;
+  } else {
+    // stage: [q 4S | t 3S | cov 36S | info 15S | grad 5S | cost S], ints [status S]
+    if (int rc = ensure_stage(p, 64 * S, S)) return rc;
+    double *w = p->d_stage;
+    PNEC_HIP_TRY(hipMemcpyAsync(w, q, sizeof(double) * 4 * S, hipMemcpyHostToDevice, stream));
+    PNEC_HIP_TRY(hipMemcpyAsync(w + 4 * S, t, sizeof(double) * 3 * S, hipMemcpyHostToDevice, stream));
+    a.q = w;
+    a.t = w + 4 * S;
+    a.out_cov = out_cov ? w + 7 * S : nullptr;
+    a.out_info = out_info ? w + 43 * S : nullptr;
+    a.out_grad = out_grad ? w + 58 * S : nullptr;
+    a.out_cost = out_cost ? w + 63 * S : nullptr;
+    a.out_status = out_status ? p->d_stage_i : nullptr;
+  }
+  // n_max of a batch whose sizes still live on the device (select) is the source's: an upper bound, which is all the
+  // block size needs (the wavefronts a pair uses follow from its own count)
+  PNEC_HIP_TRY(launch_pose_covariance(p->mode, S, cov_waves(p->n_max), a, stream));
+  if (space == PNEC_HIP_MEM_HOST) {
+    const auto back = [&](void *dst, const void *src, size_t bytes) {
+      return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream) : hipSuccess;
+    };
+    PNEC_HIP_TRY(back(out_cov, a.out_cov, sizeof(double) * 36 * S));
+    PNEC_HIP_TRY(back(out_info, a.out_info, sizeof(double) * 15 * S));
+    PNEC_HIP_TRY(back(out_grad, a.out_grad, sizeof(double) * 5 * S));
+    PNEC_HIP_TRY(back(out_cost, a.out_cost, sizeof(double) * S));
+    PNEC_HIP_TRY(back(out_status, a.out_status, sizeof(int32_t) * S));
     PNEC_HIP_TRY(hipStreamSynchronize(stream));
   }
   return 0;
