@@ -22,6 +22,8 @@
  *   pnec::common::UnscentedTransform / Unproject  common.cc:460-525   pnec_hip_unscented_transform
  *   (no counterpart: what ceres::Covariance would give for the        pnec_hip_pose_covariance
  *    problems of pnec_ceres.cc / nec_ceres.cc)
+ *   (no counterpart: the per-residual values ceres::Problem::Evaluate  pnec_hip_residuals
+ *    would return for the problems of pnec_ceres.cc / nec_ceres.cc)
  *   PNEC::Eigensolver (no RANSAC) / WeightedEigensolver  pnec.cc:231-348   pnec_hip_nec_eigensolver /
  *                                                               pnec_hip_weighted_eigensolver
  *
@@ -308,6 +310,53 @@ typedef enum pnec_hip_cov_status {
 int pnec_hip_pose_covariance(pnec_hip_problem *p, const double *q, const double *t, int32_t n_hyp, double reg,
                              double *out_info, double *out_cov, double *out_grad, double *out_cost,
                              int32_t *out_status, int space, void *stream);
+
+/* Per-correspondence residuals and a chi-square inlier gate at a pose the caller passes in (added within ABI 8: a pure
+ * addition, PNEC_HIP_ABI_VERSION is unchanged).
+ *
+ * Definition.  r_i is the residual of the problem's family at (q, t), with the operations of the solve's cost pass in
+ * the same order, so it carries the bits the solve sums.  The probabilistic residuals (TARGET, HOST, SYM) are whitened:
+ * r_i = n_i / sqrt(den_i), n_i the normal epipolar error and den_i the variance propagated from the correspondence's
+ * covariance(s) plus `reg` (TARGET: g' Sigma g + reg).  Under the model r_i ~ N(0, 1), r_i^2 is a chi-square statistic
+ * with one degree of freedom, and |r_i| <= gate means "within `gate` sigmas of this pose".  For NEC r_i = n_i, den_i is
+ * exactly 1 and `gate` is in the residual's own units.
+ *
+ * What it is not.  The gate classifies AT the pose it is given: a pose already near the truth (the chain's result, a
+ * RANSAC pose, ground truth).  It is not a robust estimator: at a least-squares pose pulled away by gross outliers it
+ * rejects the clean correspondences.
+ *
+ * Poses: q [n_pairs * n_hyp, 4] xyzw, t [n_pairs * n_hyp, 3], slot s = pair * n_hyp + h, `reg` -- all exactly as in
+ * pnec_hip_pose_covariance.  `gate` >= 0 in sigmas; +inf is allowed (every finite residual passes).
+ *
+ * Outputs; every pointer may be NULL (not wanted), not all of them.
+ *  per correspondence, n_hyp * sum N entries each; the entry of (pair p, hypothesis h, correspondence i) is
+ *  n_hyp * offsets[p] + h * N_p + i, i in the batch's own correspondence order -- with n_hyp == 1 out_mask is what
+ *  pnec_hip_problem_select / _select_view take.  Nothing else is written:
+ *   out_residual  double   r_i, signed
+ *   out_variance  double   den_i as summed, before the solve's clamp: r_i = n_i / sqrt(max(den_i, 1e-300)), so a zero
+ *                          covariance with reg = 0 reports variance 0 and a finite (huge) residual
+ *   out_mask      uint8    1 iff r_i is finite and |r_i| <= gate
+ *  per slot [n_pairs * n_hyp], from a deterministic reduction (a slot's bits depend on its own pair and pose only):
+ *   out_chi2         sum r_i^2   (twice pnec_hip_pose_covariance's out_cost)
+ *   out_gated_chi2   sum of r_i^2 over the correspondences with mask 1
+ *   out_gated_count  int32, the number of those
+ *   out_max_abs      max |r_i|; NaN if any r_i is NaN; 0 for a pair without correspondences
+ *  The variance factor of a slot is out_chi2 / (N_p - 5).
+ *
+ * All four problem modes; batches made by pnec_hip_problem_select(_view) and reshaped capacity batches included.  For a
+ * batch made by select the positions follow THAT batch's offsets (pnec_hip_problem_offsets).  DEVICE space: the offsets
+ * are read on the device, nothing waits, and arrays sized for the source batch are always large enough.  HOST space: the
+ * call first resolves the batch's sizes, which waits for the stream that produced them.
+ * HOST space also stages the per-correspondence outputs on the device: the handle's staging buffer grows to
+ * 17 bytes * n_hyp * sum N (0.87 GB for 100 000 x 512) and, like every staging buffer of a handle, is kept until the handle
+ * is destroyed; a caller of that size should pass DEVICE pointers.
+ * `space` as in pnec_hip_pose_covariance: HOST pointers are staged and the call blocks, DEVICE pointers make the call
+ * asynchronous on `stream`.  NULL problem / q / t, n_hyp < 1, gate < 0 or NaN, all outputs NULL or a bad `space`:
+ * PNEC_HIP_ERR_INVALID_ARGUMENT before the handle is read or any device is touched. */
+int pnec_hip_residuals(pnec_hip_problem *p, const double *q, const double *t, int32_t n_hyp, double reg, double gate,
+                       double *out_residual, double *out_variance, uint8_t *out_mask,
+                       double *out_chi2, double *out_gated_chi2, int32_t *out_gated_count, double *out_max_abs,
+                       int space, void *stream);
 
 /* PNEC::Eigensolver with use_ransac_ = false (src/rel_pose_estimation/pnec.cc:273-278) for every
  * pair: rotation by opengv-style eigenvalue minimisation (Kneip-Lynen; opengv is not in the

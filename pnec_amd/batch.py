@@ -37,6 +37,12 @@ class SolveResult:
             raise ValueError("this SolveResult was not produced by Batch.solve: call Batch.pose_covariance(q, t)")
         return self.batch.pose_covariance(self.q, self.t, reg=self.reg, n_hyp=self.n_hyp)
 
+    def residuals(self, gate: float = 3.0) -> "ResidualReport":
+        """Batch.residuals at this result's own poses, with the `reg` and `n_hyp` of the solve it came from."""
+        if self.batch is None:
+            raise ValueError("this SolveResult was not produced by Batch.solve: call Batch.residuals(q, t)")
+        return self.batch.residuals(self.q, self.t, reg=self.reg, gate=gate, n_hyp=self.n_hyp)
+
     def rotation_matrices(self):
         """[S,3,3] from q (numpy or torch, matching the stored arrays)."""
         q = self.q
@@ -113,6 +119,42 @@ class PoseCovariance:
     grad: object    # [S,5]   J'r in the same space
     cost: object    # [S]     1/2 sum r^2
     status: object  # [S]     int32, capi.COV_NAMES
+
+
+def gate_sigma(confidence: float) -> float:
+    """The gate, in sigmas, that a share `confidence` of N(0, 1) residuals passes: the two-sided normal quantile
+    (gate_sigma(0.9973) is 3.0 to 3 digits)."""
+    from statistics import NormalDist
+    c = float(confidence)
+    if not 0.0 < c < 1.0:
+        raise ValueError("confidence must lie in (0, 1)")
+    return NormalDist().inv_cdf(0.5 * (1.0 + c))
+
+
+@dataclass
+class ResidualReport:
+    """pnec_hip_residuals' outputs (include/pnec_hip.h).  Per correspondence, [n_hyp * sum N]: the entry of (pair p,
+    hypothesis h, correspondence i) is n_hyp * offsets[p] + h * N_p + i; per slot (pair-major, hypothesis-minor), [S].
+    The gate classifies at the pose it was given -- one already near the truth; it is not a robust estimator."""
+    residual: object     # signed whitened residual r_i (NEC: the bare normal epipolar error)
+    variance: object     # the propagated variance r_i was whitened by (NEC: exactly 1)
+    mask: object         # uint8, 1 iff |r_i| <= gate; with n_hyp == 1 it is what Batch.select takes
+    chi2: object         # [S] sum r^2  (twice the cost)
+    gated_chi2: object   # [S] sum of r^2 over the mask
+    gated_count: object  # [S] int32
+    max_abs: object      # [S] max |r|  (NaN if a residual is NaN)
+    offsets: np.ndarray  # int64 [n_pairs+1], the batch's own
+    n_hyp: int = 1
+
+    def variance_factor(self, dof: int = 5):
+        """chi2 / (n - dof) per slot, NaN where n <= dof: ~1 when the covariances describe the data; what a NEC-mode
+        PoseCovariance.cov is to be multiplied by."""
+        n = np.repeat(np.diff(np.asarray(self.offsets, dtype=np.int64)), int(self.n_hyp)).astype(np.float64) - dof
+        n[n <= 0] = np.nan
+        if _is_torch(self.chi2):
+            import torch
+            return self.chi2 / torch.as_tensor(n, device=self.chi2.device)
+        return np.asarray(self.chi2, dtype=np.float64) / n
 
 
 class Batch:
@@ -602,6 +644,48 @@ class Batch:
         capi.check(self._lib.pnec_hip_pose_covariance(self._h, p(q), p(t), n_hyp, float(reg), p(info), p(cov), p(grad),
                                                       p(cost), p(status), space, stream))
         return PoseCovariance(cov, expand_info(info), grad, cost, status)
+
+
+    def residuals(self, q, t, reg: float = 1e-13, gate: float = 3.0, n_hyp: int = 1) -> ResidualReport:
+        """Whitened residual, propagated variance and chi-square gate verdict (|r| <= gate, in sigmas) of every
+        correspondence at the poses passed in, and the chi-square sums per slot: q [S,4] xyzw, t [S,3], S = n_pairs *
+        n_hyp (pnec_hip_residuals).  torch.cuda tensors in -> torch.cuda tensors out, asynchronous on torch's current
+        stream; numpy in -> numpy out.  With n_hyp == 1, `self.select(report.mask)` keeps the gated correspondences.
+        On a batch made by select() the call first reads that batch's offsets (it sizes the outputs from them and
+        returns them in the report), which waits once for the stream the selection ran on -- also with torch.cuda
+        inputs; the C call itself, given DEVICE pointers, does not wait."""
+        n_hyp = int(n_hyp)
+        if n_hyp < 1:
+            raise ValueError("n_hyp must be >= 1")
+        gate = float(gate)
+        if not gate >= 0.0:
+            raise ValueError("gate must be >= 0 (sigmas)")
+        S = self.n_pairs * n_hyp
+        offsets = self.offsets     # (a batch made by select: waits for its sizes)
+        M = int(offsets[-1]) * n_hyp
+        if _is_torch(q):
+            import torch
+            q = self._dev_tensor(q, "q", (S, 4))
+            t = self._dev_tensor(t, "t", (S, 3))
+            f64 = dict(dtype=torch.float64, device=q.device)
+            res, var = torch.empty((M,), **f64), torch.empty((M,), **f64)
+            mask = torch.empty((M,), dtype=torch.uint8, device=q.device)
+            chi2, gchi2, mx = torch.empty((S,), **f64), torch.empty((S,), **f64), torch.empty((S,), **f64)
+            cnt = torch.empty((S,), dtype=torch.int32, device=q.device)
+            p = lambda a: a.data_ptr()
+            space, stream = capi.MEM_DEVICE, torch.cuda.current_stream(self.device).cuda_stream
+        else:
+            q = np.ascontiguousarray(q, dtype=np.float64)
+            t = np.ascontiguousarray(t, dtype=np.float64)
+            if q.shape != (S, 4) or t.shape != (S, 3):
+                raise ValueError("q must be [n_pairs*n_hyp,4] (xyzw), t [n_pairs*n_hyp,3]")
+            res, var, mask = np.empty(M), np.empty(M), np.empty(M, dtype=np.uint8)
+            chi2, gchi2, mx, cnt = np.empty(S), np.empty(S), np.empty(S), np.empty(S, dtype=np.int32)
+            p = lambda a: a.ctypes.data
+            space, stream = capi.MEM_HOST, None
+        capi.check(self._lib.pnec_hip_residuals(self._h, p(q), p(t), n_hyp, float(reg), gate, p(res), p(var), p(mask),
+                                                p(chi2), p(gchi2), p(cnt), p(mx), space, stream))
+        return ResidualReport(res, var, mask, chi2, gchi2, cnt, mx, offsets, n_hyp)
 
 
 def select_best(cost, n_hyp: int, device: int = 0):

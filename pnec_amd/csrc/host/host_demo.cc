@@ -179,8 +179,15 @@ int main(int argc, char **argv) {
   const pnec::Matrix6d S = pnec::common::PoseCovariance(ib1, ib2, icovs, sol);
   const double kDeg = 180.0 / 3.14159265358979323846;
   const double rot_sigma = std::sqrt(S(0, 0) + S(1, 1) + S(2, 2)) * kDeg, t_sigma = std::sqrt(S(3, 3) + S(4, 4) + S(5, 5)) * kDeg;
+  // how the kept correspondences sit around the solve, in their own sigmas: the count within 3 sigma of the pose and the
+  // variance factor chi2 / (n - 5) (~1 when the covariances describe the data)
+  const size_t in3 = pnec::common::GateInliers(ib1, ib2, icovs, sol, 3.0).size();
+  double chi2 = 0.0;
+  for (double r : pnec::common::Residuals(ib1, ib2, icovs, sol)) chi2 += r * r;
+  const double var_factor = ib1.size() > 5 ? chi2 / (double)(ib1.size() - 5) : std::nan("");
   std::printf("n=%d inliers=%zu rot_err_init_deg=%.6f rot_err_deg=%.6f t_err_deg=%.6f cost=%.6f rot_sigma_deg=%.6f "
-              "t_sigma_deg=%.6f\n", n, inliers.size(), e0, e1, te, cost, rot_sigma, t_sigma);
+              "t_sigma_deg=%.6f within_3_sigma=%zu variance_factor=%.6f\n", n, inliers.size(), e0, e1, te, cost, rot_sigma,
+              t_sigma, in3, var_factor);
   if (argc > 3 && std::strcmp(argv[2], "dump") == 0) {
     // everything a checker needs to repeat this call elsewhere: inputs, start pose, result, inliers
     // (text, %.17g: doubles round-trip exactly)

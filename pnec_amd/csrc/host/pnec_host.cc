@@ -251,6 +251,61 @@ Matrix6d PoseCovariance(const bearingVectors_t &bvs_1, const bearingVectors_t &b
   return PoseCovarianceImpl(PNEC_HIP_MODE_SYM, bvs_1, bvs_2, covs_2, &covs_1, camera_pose, regularization);
 }
 
+namespace {
+// pnec_hip_residuals for one pair; the residuals and / or the gate's mask (either may be NULL)
+void ResidualsImpl(int mode, const bearingVectors_t &bvs_1, const bearingVectors_t &bvs_2,
+                   const std::vector<Matrix3d> &covs, const std::vector<Matrix3d> *covs_host, const SE3d &camera_pose,
+                   double gate, double regularization, std::vector<double> *residuals, std::vector<uint8_t> *mask) {
+  if (bvs_1.size() != bvs_2.size() || bvs_1.size() != covs.size() || (covs_host && covs_host->size() != covs.size()))
+    throw std::invalid_argument("bvs_1, bvs_2 and covs differ in size");
+  if (residuals) residuals->assign(bvs_1.size(), 0.0);
+  if (mask) mask->assign(bvs_1.size(), 0);
+  if (bvs_1.empty()) return;
+  const std::vector<int64_t> offsets = {0, (int64_t)bvs_1.size()};
+  Problem prob(optimization::SolverOptions().device, mode, offsets);
+  Check(pnec_hip_problem_fill(prob.p, 0, 1, bvs_1[0].data(), bvs_2[0].data(), covs[0].data(),
+                              covs_host ? (*covs_host)[0].data() : nullptr, PNEC_HIP_MEM_HOST, nullptr));
+  const Quaterniond q(camera_pose.rotationMatrix());
+  Check(pnec_hip_residuals(prob.p, q.coeffs(), camera_pose.translation().data(), 1, regularization, gate,
+                           residuals ? residuals->data() : nullptr, nullptr, mask ? mask->data() : nullptr, nullptr,
+                           nullptr, nullptr, nullptr, PNEC_HIP_MEM_HOST, nullptr));
+}
+std::vector<int> MaskToIndices(const std::vector<uint8_t> &mask) {
+  std::vector<int> out;
+  for (size_t i = 0; i < mask.size(); ++i)
+    if (mask[i]) out.push_back((int)i);
+  return out;
+}
+}  // namespace
+
+std::vector<double> Residuals(const bearingVectors_t &bvs_1, const bearingVectors_t &bvs_2,
+                              const std::vector<Matrix3d> &covs, const SE3d &camera_pose, double regularization) {
+  std::vector<double> r;
+  ResidualsImpl(PNEC_HIP_MODE_TARGET, bvs_1, bvs_2, covs, nullptr, camera_pose, 0.0, regularization, &r, nullptr);
+  return r;
+}
+std::vector<double> Residuals(const bearingVectors_t &bvs_1, const bearingVectors_t &bvs_2,
+                              const std::vector<Matrix3d> &covs_1, const std::vector<Matrix3d> &covs_2,
+                              const SE3d &camera_pose, double regularization) {
+  std::vector<double> r;
+  ResidualsImpl(PNEC_HIP_MODE_SYM, bvs_1, bvs_2, covs_2, &covs_1, camera_pose, 0.0, regularization, &r, nullptr);
+  return r;
+}
+std::vector<int> GateInliers(const bearingVectors_t &bvs_1, const bearingVectors_t &bvs_2,
+                             const std::vector<Matrix3d> &covs, const SE3d &camera_pose, double gate,
+                             double regularization) {
+  std::vector<uint8_t> m;
+  ResidualsImpl(PNEC_HIP_MODE_TARGET, bvs_1, bvs_2, covs, nullptr, camera_pose, gate, regularization, nullptr, &m);
+  return MaskToIndices(m);
+}
+std::vector<int> GateInliers(const bearingVectors_t &bvs_1, const bearingVectors_t &bvs_2,
+                             const std::vector<Matrix3d> &covs_1, const std::vector<Matrix3d> &covs_2,
+                             const SE3d &camera_pose, double gate, double regularization) {
+  std::vector<uint8_t> m;
+  ResidualsImpl(PNEC_HIP_MODE_SYM, bvs_1, bvs_2, covs_2, &covs_1, camera_pose, gate, regularization, nullptr, &m);
+  return MaskToIndices(m);
+}
+
 std::ostream &operator<<(std::ostream &os, const FrameTiming &ft) {
   const long fields[] = {(long)ft.id_,    ft.frame_loading_, ft.feature_creation_,      ft.nec_es_,
                          ft.it_es_,       ft.avg_it_es_,     ft.ceres_,

@@ -103,6 +103,25 @@ Matrix6d PoseCovariance(const bearingVectors_t &bvs_1, const bearingVectors_t &b
 Matrix6d PoseCovariance(const bearingVectors_t &bvs_1, const bearingVectors_t &bvs_2, const std::vector<Matrix3d> &covs_1,
                         const std::vector<Matrix3d> &covs_2, const SE3d &camera_pose, double regularization = 1e-13);
 
+// Addition (the reference returns a pose and no per-correspondence verdict): the whitened PNEC residual of every
+// correspondence at camera_pose -- pnec_hip_residuals for one pair; what ceres::Problem::Evaluate would return per
+// residual block for PNECCeres' problem.  Under the model each is N(0, 1).
+std::vector<double> Residuals(const bearingVectors_t &bvs_1, const bearingVectors_t &bvs_2,
+                              const std::vector<Matrix3d> &covs, const SE3d &camera_pose, double regularization = 1e-13);
+// the symmetric residual: covariances of both frames
+std::vector<double> Residuals(const bearingVectors_t &bvs_1, const bearingVectors_t &bvs_2,
+                              const std::vector<Matrix3d> &covs_1, const std::vector<Matrix3d> &covs_2,
+                              const SE3d &camera_pose, double regularization = 1e-13);
+// The indices of the correspondences within `gate` sigmas of camera_pose (|residual| <= gate), in the shape of the
+// `inliers` vector PNEC::Solve fills.  It classifies at a pose that is already near the truth (PNEC::Solve's result);
+// it is not a robust estimator.
+std::vector<int> GateInliers(const bearingVectors_t &bvs_1, const bearingVectors_t &bvs_2,
+                             const std::vector<Matrix3d> &covs, const SE3d &camera_pose, double gate = 3.0,
+                             double regularization = 1e-13);
+std::vector<int> GateInliers(const bearingVectors_t &bvs_1, const bearingVectors_t &bvs_2,
+                             const std::vector<Matrix3d> &covs_1, const std::vector<Matrix3d> &covs_2,
+                             const SE3d &camera_pose, double gate = 3.0, double regularization = 1e-13);
+
 }  // namespace common
 
 namespace optimization {

@@ -213,6 +213,31 @@ py::array_t<double> pose_covariance(arr bvs1, arr bvs2, arr covs, arr pose, doub
   return out;
 }
 
+// covs_host (optional): the covariances of frame 1 -> the symmetric residual's two-covariance overloads
+py::array_t<double> residuals(arr bvs1, arr bvs2, arr covs, arr pose, double regularization, py::object covs_host) {
+  const std::vector<double> r =
+      covs_host.is_none()
+          ? pnec::common::Residuals(ToBearings(bvs1, "bvs_1"), ToBearings(bvs2, "bvs_2"), ToCovariances(covs, "covs"),
+                                    ToPose(pose), regularization)
+          : pnec::common::Residuals(ToBearings(bvs1, "bvs_1"), ToBearings(bvs2, "bvs_2"),
+                                    ToCovariances(covs_host.cast<arr>(), "covs_host"), ToCovariances(covs, "covs"),
+                                    ToPose(pose), regularization);
+  py::array_t<double> out((py::ssize_t)r.size());
+  auto o = out.mutable_unchecked<1>();
+  for (size_t i = 0; i < r.size(); ++i) o((py::ssize_t)i) = r[i];
+  return out;
+}
+
+std::vector<int> gate_inliers(arr bvs1, arr bvs2, arr covs, arr pose, double gate, double regularization,
+                              py::object covs_host) {
+  if (covs_host.is_none())
+    return pnec::common::GateInliers(ToBearings(bvs1, "bvs_1"), ToBearings(bvs2, "bvs_2"), ToCovariances(covs, "covs"),
+                                     ToPose(pose), gate, regularization);
+  return pnec::common::GateInliers(ToBearings(bvs1, "bvs_1"), ToBearings(bvs2, "bvs_2"),
+                                   ToCovariances(covs_host.cast<arr>(), "covs_host"), ToCovariances(covs, "covs"),
+                                   ToPose(pose), gate, regularization);
+}
+
 // PNEC::Solve for ONE frame pair through the overload asked for (pnec.cc:69-75, :77-124, :126-134,
 // :135-208): overload 0 = (bvs1, bvs2, covs, init), 1 = (+ inliers), 2 = (+ timing), 3 = (+ inliers,
 // timing).  Returns (pose 4x4, inliers or None, timing dict or None).
@@ -295,6 +320,14 @@ PYBIND11_MODULE(pypnec, m) {
         py::arg("regularization") = 1e-13,
         "pnec::common::PoseCovariance (addition; device): 6x6 covariance of (omega_xyz [left perturbation, rad], t_xyz "
         "[unit direction]) at `pose` -- include/pnec_hip.h pnec_hip_pose_covariance");
+  m.def("residuals", &residuals, py::arg("bvs1"), py::arg("bvs2"), py::arg("covs"), py::arg("pose"),
+        py::arg("regularization") = 1e-13, py::arg("covs_host") = py::none(),
+        "pnec::common::Residuals (addition; device): the whitened PNEC residual of every correspondence at `pose` -- "
+        "include/pnec_hip.h pnec_hip_residuals.  covs: frame 2 (target); covs_host: frame 1, given -> the symmetric residual");
+  m.def("gate_inliers", &gate_inliers, py::arg("bvs1"), py::arg("bvs2"), py::arg("covs"), py::arg("pose"),
+        py::arg("gate") = 3.0, py::arg("regularization") = 1e-13, py::arg("covs_host") = py::none(),
+        "pnec::common::GateInliers (addition; device): indices of the correspondences with |residual| <= gate (sigmas) "
+        "at `pose`, a pose already near the truth");
   m.def("solve", &solve, py::arg("bvs1"), py::arg("bvs2"), py::arg("covs"), py::arg("init_pose"),
         py::arg("overload") = 1, py::arg("use_ransac") = true, py::arg("use_nec") = false,
         py::arg("use_ceres") = true, py::arg("weighted_iterations") = 10, py::arg("regularization") = 1e-13,

@@ -19,6 +19,7 @@
 #include "pnec_device.hpp"
 #include "pnec_front_shared.hpp"
 #include "pnec_pose_cov.hpp"
+#include "pnec_residuals.hpp"
 #include "pnec_solve_kernel.hpp"
 #include "pnec_solve_group_kernel.hpp"
 
@@ -1838,6 +1839,83 @@ int pnec_hip_pose_covariance(pnec_hip_problem *p, const double *q, const double 
     PNEC_HIP_TRY(back(out_grad, a.out_grad, sizeof(double) * 5 * S));
     PNEC_HIP_TRY(back(out_cost, a.out_cost, sizeof(double) * S));
     PNEC_HIP_TRY(back(out_status, a.out_status, sizeof(int32_t) * S));
+    PNEC_HIP_TRY(hipStreamSynchronize(stream));
+  }
+  return 0;
+}
+
+// r_i, its variance and the gate's verdict per correspondence, chi-square sums per (pair, pose) slot: pnec_residuals.hip
+int pnec_hip_residuals(pnec_hip_problem *p, const double *q, const double *t, int32_t n_hyp, double reg, double gate,
+                       double *out_residual, double *out_variance, uint8_t *out_mask, double *out_chi2,
+                       double *out_gated_chi2, int32_t *out_gated_count, double *out_max_abs, int space, void *stream_) {
+  if (!p) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "residuals: problem is NULL");
+  if (!q || !t) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "residuals: q or t is NULL");
+  if (n_hyp < 1) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "residuals: n_hyp must be >= 1");
+  if (!(gate >= 0.0)) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "residuals: gate must be >= 0 (sigmas; +inf allowed)");
+  if (!out_residual && !out_variance && !out_mask && !out_chi2 && !out_gated_chi2 && !out_gated_count && !out_max_abs)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "residuals: every output is NULL");
+  if (space != PNEC_HIP_MEM_DEVICE && space != PNEC_HIP_MEM_HOST)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "residuals: bad memory space");
+  const int64_t S = p->n_pairs * (int64_t)n_hyp;
+  if (S == 0) return 0;
+  if (S > 0x7fffffffLL) return fail(PNEC_HIP_ERR_UNSUPPORTED, "more than 2^31-1 poses in one call");
+  DeviceGuard guard(p->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  ResidualArgs a;
+  a.data = p->d_data;
+  a.block_offset = p->d_block_offset;
+  a.count = p->d_count;
+  a.offsets = p->d_offsets;
+  a.n_hyp = n_hyp;
+  a.reg = reg;
+  a.gate = gate;
+  int64_t M = 0;   // HOST space: entries of a per-correspondence array
+  uint8_t *d_mask = nullptr;
+  if (space == PNEC_HIP_MEM_DEVICE) {
+    // (a batch whose sizes still live on the device needs no host-side number here: the kernel reads its offsets)
+    a.q = q;
+    a.t = t;
+    a.out_residual = out_residual;
+    a.out_variance = out_variance;
+    a.out_mask = out_mask;
+    a.out_chi2 = out_chi2;
+    a.out_gated_chi2 = out_gated_chi2;
+    a.out_gated_count = out_gated_count;
+    a.out_max_abs = out_max_abs;
+  } else {
+    // the lengths of the caller's arrays are the batch's own totals: a batch made by select waits for its sizes here
+    if (int rc = materialize(p)) return rc;
+    M = p->n_corr * (int64_t)n_hyp;
+    // stage: [q 4S | t 3S | chi2 S | gated chi2 S | max S | residual M | variance M | mask M bytes], ints [count S]
+    if (int rc = ensure_stage(p, 10 * S + 2 * M + (M + 7) / 8, S)) return rc;
+    double *w = p->d_stage;
+    PNEC_HIP_TRY(hipMemcpyAsync(w, q, sizeof(double) * 4 * S, hipMemcpyHostToDevice, stream));
+    PNEC_HIP_TRY(hipMemcpyAsync(w + 4 * S, t, sizeof(double) * 3 * S, hipMemcpyHostToDevice, stream));
+    d_mask = reinterpret_cast<uint8_t *>(w + 10 * S + 2 * M);
+    a.q = w;
+    a.t = w + 4 * S;
+    a.out_chi2 = out_chi2 ? w + 7 * S : nullptr;
+    a.out_gated_chi2 = out_gated_chi2 ? w + 8 * S : nullptr;
+    a.out_max_abs = out_max_abs ? w + 9 * S : nullptr;
+    a.out_residual = out_residual ? w + 10 * S : nullptr;
+    a.out_variance = out_variance ? w + 10 * S + M : nullptr;
+    a.out_mask = out_mask ? d_mask : nullptr;
+    a.out_gated_count = out_gated_count ? p->d_stage_i : nullptr;
+  }
+  // n_max of a batch whose sizes still live on the device (select) is the source's: an upper bound, which is all the
+  // block size needs (the wavefronts a pair uses follow from its own count)
+  PNEC_HIP_TRY(launch_residuals(p->mode, S, cov_waves(p->n_max), a, stream));
+  if (space == PNEC_HIP_MEM_HOST) {
+    const auto back = [&](void *dst, const void *src, size_t bytes) {
+      return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream) : hipSuccess;
+    };
+    PNEC_HIP_TRY(back(out_residual, a.out_residual, sizeof(double) * M));
+    PNEC_HIP_TRY(back(out_variance, a.out_variance, sizeof(double) * M));
+    PNEC_HIP_TRY(back(out_mask, a.out_mask, (size_t)M));
+    PNEC_HIP_TRY(back(out_chi2, a.out_chi2, sizeof(double) * S));
+    PNEC_HIP_TRY(back(out_gated_chi2, a.out_gated_chi2, sizeof(double) * S));
+    PNEC_HIP_TRY(back(out_gated_count, a.out_gated_count, sizeof(int32_t) * S));
+    PNEC_HIP_TRY(back(out_max_abs, a.out_max_abs, sizeof(double) * S));
     PNEC_HIP_TRY(hipStreamSynchronize(stream));
   }
   return 0;
