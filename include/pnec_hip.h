@@ -192,7 +192,7 @@ int pnec_hip_problem_fill_keypoints(pnec_hip_problem *p, int64_t first_pair, int
                                     double kappa, int camera_model, int space, void *stream);
 
 /* The batch's SoA planes as stored in HBM (pair blocks of round_up(N_p, 64)-double planes; the layout in
- * the header of pnec_capi.hip / DESIGN.md): size in doubles, and a copy out (tests, debugging). */
+ * pnec_internal.hpp / DESIGN.md): size in doubles, and a copy out (tests, debugging). */
 int64_t pnec_hip_problem_payload_doubles(const pnec_hip_problem *p);
 int pnec_hip_problem_export_payload(const pnec_hip_problem *p, double *out, int space, void *stream);
 

@@ -1,4 +1,4 @@
-// pnec_frame.inl -- part of pnec_capi.hip (inside extern "C"): the per-frame handle of the WHOLE chain.
+// pnec_frame.hip -- the per-frame handle of the WHOLE chain.
 //
 // The reference's odometry calls PNEC::Solve once per frame pair (Frame2Frame::PNECAlign,
 // src/rel_pose_estimation/frame2frame.cc:122-141 -> pnec.cc:77-124).  A batch object per call -- allocate,
@@ -13,6 +13,20 @@
 //   * the batch's cached scratch, InlierExtraction target and side stream (they live as long as the batch);
 //   * one HIP stream; a frame is: memcpy in, ingest launch, pnec_hip_solve_pipeline in DEVICE space (the same
 //     launches, hence the same bits, as the batch call), one stream synchronisation, memcpy out.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <new>
+#include <string>
+
+#include "pnec_device.hpp"
+#include "pnec_internal.hpp"
+
+using namespace pnec_hip;
+
+extern "C" {
+
 struct pnec_hip_frame {
   int device = 0;
   int64_t max_corr = 0;
@@ -191,3 +205,5 @@ int pnec_hip_frame_solve(pnec_hip_frame *f, int64_t n, const double *bvs1, const
   if (out_inlier_mask && n > 0) std::memcpy(out_inlier_mask, h + f->o_mask, (size_t)n);
   return 0;
 }
+
+}  // extern "C"

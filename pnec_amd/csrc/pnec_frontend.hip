@@ -1017,7 +1017,7 @@ struct FrontScratch {
   int32_t *wo_order, *wo_count;
 };
 // per pair kFrontDoublesPerPair = 36 + 3 + 1 + 3 + 3 kEsMaxRounds doubles and kFrontIntsPerPair ints, and kFrontCounterInts
-// ints of counters behind those (pnec_front_shared.hpp; pnec_capi.hip allocates them -- until round 5 the counters sat
+// ints of counters behind those (pnec_front_shared.hpp; pnec_capi.hip ensure_front allocates them -- until round 5 the counters sat
 // in a fifth per-pair region, i.e. past the end of a one-pair batch's five ints)
 FrontScratch front_scratch(double *d, int32_t *i, int64_t P) {
   FrontScratch f;
@@ -3387,7 +3387,7 @@ template __global__ void probe_value_grad_kernel<false>(const double *, const do
 #endif
 
 // ------------------------------------------------------------------------------------------
-// host side: launchers called from pnec_capi.hip
+// host side: launchers called from the ABI layer (declared in pnec_internal.hpp)
 static std::mutex g_fib_mutex;
 static bool g_fib_ready[64] = {false};
 

@@ -1,4 +1,4 @@
-// pnec_multi.inl -- part of pnec_capi.hip (inside extern "C"): PNEC::Solve for a batch spread over several GPUs of one
+// pnec_multi.hip -- PNEC::Solve for a batch spread over several GPUs of one
 // node from ONE process.
 //
 // The reference's own fan-out is process-level (scripts/run_simulation.sh:52-67, scripts/parallel_kitti.sh:60-69: one
@@ -9,6 +9,19 @@
 // device, every thread writing its range of the caller's result arrays -- one process, so no collective is needed.
 // RANSAC draws are a function of (seed, GLOBAL pair index) (pnec_hip_pipeline_options.first_pair_id), so the results do
 // not depend on the device list: {0}, {0, 0} and {0, 1, ..., 7} give the same bits.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <functional>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "pnec_internal.hpp"
+
+using namespace pnec_hip;
+
+extern "C" {
 
 int pnec_hip_partition(int64_t n_pairs, const int64_t *offsets, int32_t n_parts, int64_t *bounds) {
   if (n_pairs < 0 || n_parts < 1 || !bounds || (n_pairs > 0 && !offsets))
@@ -254,3 +267,5 @@ int pnec_hip_solve_pipeline_multi(int32_t n_devices, const int32_t *devices, int
   pnec_hip_multi_destroy(m);
   return rc ? fail(rc, msg) : 0;
 }
+
+}  // extern "C"

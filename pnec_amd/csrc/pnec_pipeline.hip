@@ -1,4 +1,4 @@
-// pnec_pipeline.inl -- part of pnec_capi.hip (inside extern "C"): PNEC::Solve's whole chain for a batch,
+// pnec_pipeline.hip -- PNEC::Solve's whole chain for a batch,
 // device-resident from the first stage to the last (src/rel_pose_estimation/pnec.cc:77-124).
 //
 //   Eigensolver (+ RANSAC)  ->  InlierExtraction  ->  WeightedEigensolver + SCF  ->  CeresSolver
@@ -7,6 +7,19 @@
 // Every stage is a launch on the caller's stream reading the previous stage's output in HBM; the inlier
 // batch is compacted on the device into a cached batch of the same capacity, its sizes never visit the
 // host.  HOST-space calls add one upload of the start poses in front and one download + wait at the end.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+
+#include "pnec_front_shared.hpp"
+#include "pnec_internal.hpp"
+
+using namespace pnec_hip;
+
+extern "C" {
 
 void pnec_hip_default_pipeline_options(pnec_hip_pipeline_options *o) {
   if (!o) return;
@@ -357,3 +370,5 @@ int pnec_hip_solve_pipeline(pnec_hip_problem *p, const double *init_q, const dou
   }
   return 0;
 }
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// pnec_stream.inl -- part of pnec_capi.hip (inside extern "C"): the streaming handle.
+// pnec_streaming.hip -- the streaming handle (host side; its AoS-source kernels are built in pnec_stream_<family>.hip).
 //
 // The reference's odometry calls PNEC::Solve / PNECCeres::Optimize once per frame
 // (src/rel_pose_estimation/frame2frame.cc:122-141, src/pnec_vo.cc:220-261).  A batch object per call
@@ -14,6 +14,21 @@
 // Pairs too large for the register-resident geometries take the staged route through a capacity-shaped batch
 // owned by the handle (re-shaped to the submit's sizes, pack, solve into the slot: nothing allocated per submit
 // once the batch exists).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "pnec_internal.hpp"
+#include "pnec_solve_kernel.hpp"
+
+using namespace pnec_hip;
+
+extern "C" {
+
 struct pnec_hip_stream {
   int device = 0;
   int32_t max_corr = 0;   // correspondences per submit
@@ -366,3 +381,5 @@ int pnec_hip_stream_wait(pnec_hip_stream *s, int64_t ticket, double *out_q, doub
   sl->ticket = 0;
   return 0;
 }
+
+}  // extern "C"

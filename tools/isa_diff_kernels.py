@@ -21,6 +21,8 @@ def kernels(path):
             cur = m.group(1)
             out[cur] = []
             continue
+        if "file format" in l or l.startswith("Disassembly of section"):
+            cur = None  # the next code object's header (it names a temporary file) is not part of the last kernel
         if cur is None or not l.strip():
             continue
         t = l.split("//")[0].strip()
