@@ -24,6 +24,8 @@
  *    problems of pnec_ceres.cc / nec_ceres.cc)
  *   (no counterpart: the per-residual values ceres::Problem::Evaluate  pnec_hip_residuals
  *    would return for the problems of pnec_ceres.cc / nec_ceres.cc)
+ *   (no counterpart: the structure a pose implies and the sign of t,   pnec_hip_triangulate
+ *    which TranslationalDifference(..., both_directions = true) hides)
  *   PNEC::Eigensolver (no RANSAC) / WeightedEigensolver  pnec.cc:231-348   pnec_hip_nec_eigensolver /
  *                                                               pnec_hip_weighted_eigensolver
  *
@@ -357,6 +359,68 @@ int pnec_hip_residuals(pnec_hip_problem *p, const double *q, const double *t, in
                        double *out_residual, double *out_variance, uint8_t *out_mask,
                        double *out_chi2, double *out_gated_chi2, int32_t *out_gated_count, double *out_max_abs,
                        int space, void *stream);
+
+/* Triangulation at a pose the caller passes in: depths, points, parallax, depth variance and the cheirality vote that
+ * fixes the sign of t (added within ABI 8: a pure addition, PNEC_HIP_ABI_VERSION is unchanged).  Every energy the
+ * solvers minimise is even in t; this call is what decides between t and -t.
+ *
+ * Pose.  R (from q, normalised inside) maps frame-2 vectors into frame 1 and x1 = R x2 + t: camera 1 sits at the origin,
+ * camera 2 at t.  t is used as a DIRECTION exactly as in pnec_hip_residuals, so the baseline is 1 and every length
+ * below is in baselines; t = 0 is read as (0, 0, 1).  Poses: q [n_pairs * n_hyp, 4] xyzw, t [n_pairs * n_hyp, 3], slot
+ * s = pair * n_hyp + h.
+ *
+ * Midpoint triangulation, bearings not assumed unit.  With u = R f2:
+ *   a00 = f1.f1   a10 = f1.u   a11 = u.u   b0 = f1.t   b1 = u.t
+ *   D      = a00 a11 - a10^2                  (= sin^2 psi for unit bearings)
+ *   depth1 = (a11 b0 - a10 b1) / D            along f1, from camera 1
+ *   depth2 = (a10 b0 - a00 b1) / D            along u,  from camera 2
+ *   point  = 1/2 (depth1 f1 + t + depth2 u)   in frame 1
+ *   psi    = atan2(|f1 x u|, f1.u)            parallax, radians, in [0, pi]
+ *   front  = depth1 > 0 and depth2 > 0 (both finite)
+ *   back   = depth1 < 0 and depth2 < 0 (both finite)   -- "in front" under -t
+ * depth1, depth2 and point are linear in t: at -t they are the exact IEEE negations of their values at t, and front and
+ * back swap.
+ *
+ * Depth variance: the first-order propagation of the resident covariances to depth1.
+ *   d depth1 / d u  = ( 2 b0 u - b1 f1 - a10 t  -  depth1 (2 a00 u - 2 a10 f1) ) / D  =: gu
+ *   d depth1 / d f1 = ( a11 t - b1 u            -  depth1 (2 a11 f1 - 2 a10 u) ) / D  =: g1
+ *   TARGET: (R' gu)' Sigma2 (R' gu)       HOST: g1' Sigma1 g1       SYM: both summed       NEC: NaN
+ * Sigma2 is the covariance of f2 in frame 2, Sigma1 that of f1 in frame 1.  No regularisation is added.  Even in t.
+ *
+ * Degenerate inputs (the result is the same whatever else the pair holds).  D not a positive finite number (parallel
+ * rays, a zero bearing): depth1 = depth2 = +inf, point and variance NaN, psi as the atan2 gives it (0 for parallel
+ * rays), front 0, counted in neither vote.  A NaN in a bearing: every per-correspondence output NaN, front 0, counted in
+ * neither vote, left out of the parallax mean.  D is formed from two rounded products and a D at or below its own rounding
+ * error, 2^-49 a00 a11 (a parallax below 4.2e-8 rad, where no digit of a depth is left), is read as 0.
+ *
+ * Vote, always at t as given: n_front / n_back count the front / back correspondences; sign = +1 if n_front >= n_back
+ * (a tie, a pair without correspondences included), else -1; t_oriented = sign * t / |t|.
+ *
+ * flags: PNEC_HIP_TRI_ORIENT evaluates the per-correspondence outputs at t_oriented instead of t (out_front is then
+ * relative to t_oriented; the three vote outputs stay relative to t as given).
+ *
+ * Outputs; every pointer may be NULL (not wanted), not all of them.  M = n_hyp * sum N; the entry of (pair p,
+ * hypothesis h, correspondence i) is n_hyp * offsets[p] + h * N_p + i, the layout of pnec_hip_residuals -- with
+ * n_hyp == 1 out_front is what pnec_hip_problem_select / _select_view take.
+ *   out_point [M,3] row-major   out_depth1, out_depth2, out_parallax, out_depth1_var [M]   out_front uint8 [M]
+ *   out_n_front, out_n_back, out_sign int32 [S]   out_t_oriented [S,3] unit   out_parallax_mean [S]: the mean of psi
+ *   over the pair's correspondences that have one (0 if there is none)
+ * A slot's bits depend on its own pair and pose only (no atomics, fixed reduction order).
+ *
+ * All four problem modes; batches made by pnec_hip_problem_select(_view) and reshaped capacity batches included, with
+ * the positions following THAT batch's offsets.  DEVICE space: the offsets are read on the device, nothing waits, the
+ * call is asynchronous on `stream`.  HOST space: the call first resolves the batch's sizes (which waits for the stream
+ * that produced them), stages the outputs on the device and blocks: the handle's staging buffer grows to
+ * 57 bytes * n_hyp * sum N (2.9 GB for 100 000 x 512) and is kept until the handle is destroyed; a caller of that size
+ * should pass DEVICE pointers.
+ * A batch whose largest pair holds 4 GiB of planes or more (29 million correspondences in SYM mode): PNEC_HIP_ERR_UNSUPPORTED.
+ * NULL problem / q / t, n_hyp < 1, a flag bit other than PNEC_HIP_TRI_ORIENT, all outputs NULL or a bad `space`:
+ * PNEC_HIP_ERR_INVALID_ARGUMENT before the handle is read or any device is touched. */
+#define PNEC_HIP_TRI_ORIENT 1
+int pnec_hip_triangulate(pnec_hip_problem *p, const double *q, const double *t, int32_t n_hyp, int32_t flags,
+                         double *out_point, double *out_depth1, double *out_depth2, double *out_parallax,
+                         double *out_depth1_var, uint8_t *out_front, int32_t *out_n_front, int32_t *out_n_back,
+                         int32_t *out_sign, double *out_t_oriented, double *out_parallax_mean, int space, void *stream);
 
 /* PNEC::Eigensolver with use_ransac_ = false (src/rel_pose_estimation/pnec.cc:273-278) for every
  * pair: rotation by opengv-style eigenvalue minimisation (Kneip-Lynen; opengv is not in the

@@ -8,6 +8,6 @@ Layout:
   distributed.py   one-process-per-GPU sharding of independent pair batches + one RCCL gather
 """
 from . import capi  # noqa: F401
-from .batch import Batch, PoseCovariance, ResidualReport, SolveResult, gate_sigma, select_best  # noqa: F401
+from .batch import Batch, PoseCovariance, ResidualReport, SolveResult, Triangulation, gate_sigma, select_best  # noqa: F401
 
-__all__ = ["capi", "Batch", "PoseCovariance", "ResidualReport", "SolveResult", "gate_sigma", "select_best"]
+__all__ = ["capi", "Batch", "PoseCovariance", "ResidualReport", "SolveResult", "Triangulation", "gate_sigma", "select_best"]

@@ -43,6 +43,13 @@ class SolveResult:
             raise ValueError("this SolveResult was not produced by Batch.solve: call Batch.residuals(q, t)")
         return self.batch.residuals(self.q, self.t, reg=self.reg, gate=gate, n_hyp=self.n_hyp)
 
+    def triangulate(self, orient: bool = True) -> "Triangulation":
+        """Batch.triangulate at this result's own poses, with the `n_hyp` of the solve it came from: the structure the
+        solved pose implies and, with `orient`, the sign of t that puts it in front of both cameras."""
+        if self.batch is None:
+            raise ValueError("this SolveResult was not produced by Batch.solve: call Batch.triangulate(q, t)")
+        return self.batch.triangulate(self.q, self.t, n_hyp=self.n_hyp, orient=orient)
+
     def rotation_matrices(self):
         """[S,3,3] from q (numpy or torch, matching the stored arrays)."""
         q = self.q
@@ -155,6 +162,28 @@ class ResidualReport:
             import torch
             return self.chi2 / torch.as_tensor(n, device=self.chi2.device)
         return np.asarray(self.chi2, dtype=np.float64) / n
+
+
+@dataclass
+class Triangulation:
+    """pnec_hip_triangulate's outputs (include/pnec_hip.h has the definitions).  Per correspondence, [n_hyp * sum N], in
+    ResidualReport's layout: the entry of (pair p, hypothesis h, correspondence i) is n_hyp * offsets[p] + h * N_p + i;
+    per slot (pair-major, hypothesis-minor), [S].  Lengths are in baselines (t is a direction).  With `orient` the
+    per-correspondence fields are evaluated at `t` below (the oriented direction), otherwise at the t passed in; the
+    vote (n_front, n_back, sign) is always relative to the t passed in."""
+    point: object          # [M,3] midpoint of the two rays, frame 1; NaN for parallel rays
+    depth1: object         # [M] along f1 from camera 1; +inf for parallel rays
+    depth2: object         # [M] along R f2 from camera 2
+    parallax: object       # [M] angle between f1 and R f2, radians
+    depth1_var: object     # [M] first-order variance of depth1 from the batch's covariances (NEC: NaN)
+    front: object          # [M] uint8, 1 iff both depths are positive; with n_hyp == 1 it is what Batch.select takes
+    n_front: object        # [S] int32, correspondences in front of both cameras at the t passed in
+    n_back: object         # [S] int32, correspondences behind both (in front under -t)
+    sign: object           # [S] int32, +1 if n_front >= n_back else -1
+    t: object              # [S,3] sign * t / |t|
+    parallax_mean: object  # [S] mean parallax of the pair, 0 if it has no correspondence
+    offsets: np.ndarray = None  # int64 [n_pairs+1], the batch's own
+    n_hyp: int = 1
 
 
 class Batch:
@@ -686,6 +715,49 @@ class Batch:
         capi.check(self._lib.pnec_hip_residuals(self._h, p(q), p(t), n_hyp, float(reg), gate, p(res), p(var), p(mask),
                                                 p(chi2), p(gchi2), p(cnt), p(mx), space, stream))
         return ResidualReport(res, var, mask, chi2, gchi2, cnt, mx, offsets, n_hyp)
+
+    def triangulate(self, q, t, n_hyp: int = 1, orient: bool = True) -> Triangulation:
+        """Midpoint triangulation of every correspondence at the poses passed in, the cheirality vote per slot and the
+        translation direction with the sign that puts the structure in front of both cameras: q [S,4] xyzw, t [S,3],
+        S = n_pairs * n_hyp (pnec_hip_triangulate).  With `orient` the per-correspondence outputs are evaluated at the
+        oriented direction (PNEC_HIP_TRI_ORIENT).  torch.cuda tensors in -> torch.cuda tensors out, asynchronous on
+        torch's current stream; numpy in -> numpy out.  On a batch made by select() the call first reads that batch's
+        offsets, as Batch.residuals does."""
+        n_hyp = int(n_hyp)
+        if n_hyp < 1:
+            raise ValueError("n_hyp must be >= 1")
+        flags = capi.TRI_ORIENT if orient else 0
+        S = self.n_pairs * n_hyp
+        offsets = self.offsets     # (a batch made by select: waits for its sizes)
+        M = int(offsets[-1]) * n_hyp
+        if _is_torch(q):
+            import torch
+            q = self._dev_tensor(q, "q", (S, 4))
+            t = self._dev_tensor(t, "t", (S, 3))
+            f64 = dict(dtype=torch.float64, device=q.device)
+            i32 = dict(dtype=torch.int32, device=q.device)
+            point = torch.empty((M, 3), **f64)
+            d1, d2, psi, var = (torch.empty((M,), **f64) for _ in range(4))
+            front = torch.empty((M,), dtype=torch.uint8, device=q.device)
+            nf, nb, sign = (torch.empty((S,), **i32) for _ in range(3))
+            to, mean = torch.empty((S, 3), **f64), torch.empty((S,), **f64)
+            p = lambda a: a.data_ptr()
+            space, stream = capi.MEM_DEVICE, torch.cuda.current_stream(self.device).cuda_stream
+        else:
+            q = np.ascontiguousarray(q, dtype=np.float64)
+            t = np.ascontiguousarray(t, dtype=np.float64)
+            if q.shape != (S, 4) or t.shape != (S, 3):
+                raise ValueError("q must be [n_pairs*n_hyp,4] (xyzw), t [n_pairs*n_hyp,3]")
+            point = np.empty((M, 3))
+            d1, d2, psi, var = (np.empty(M) for _ in range(4))
+            front = np.empty(M, dtype=np.uint8)
+            nf, nb, sign = (np.empty(S, dtype=np.int32) for _ in range(3))
+            to, mean = np.empty((S, 3)), np.empty(S)
+            p = lambda a: a.ctypes.data
+            space, stream = capi.MEM_HOST, None
+        capi.check(self._lib.pnec_hip_triangulate(self._h, p(q), p(t), n_hyp, flags, p(point), p(d1), p(d2), p(psi),
+                                                  p(var), p(front), p(nf), p(nb), p(sign), p(to), p(mean), space, stream))
+        return Triangulation(point, d1, d2, psi, var, front, nf, nb, sign, to, mean, offsets, n_hyp)
 
 
 def select_best(cost, n_hyp: int, device: int = 0):

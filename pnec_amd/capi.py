@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("PNEC_HIP_LIB") or os.path.join(_HERE, "libpnec_hip.so
 ABI_VERSION = 8  # PNEC_HIP_ABI_VERSION of include/pnec_hip.h this binding was written against
 MODE_NEC, MODE_TARGET, MODE_HOST, MODE_SYM = 0, 1, 2, 3
 MEM_HOST, MEM_DEVICE = 0, 1
+TRI_ORIENT = 1   # pnec_hip_triangulate flags: per-correspondence outputs at the oriented translation
 # pnec_hip_eigensolver_scheme: which iteration stands in for opengv's eigenvalue minimisation (include/pnec_hip.h)
 ES_NEWTON, ES_DESCENT, ES_LM = 0, 1, 2
 # PNEC_HIP_RANSAC_* bits (pnec_hip_pipeline_options.ransac_flags, pnec_hip_problem_set_ransac_flags)
@@ -64,6 +65,7 @@ SYMBOLS = [
     "pnec_hip_cost_function",
     "pnec_hip_pose_covariance",
     "pnec_hip_residuals",
+    "pnec_hip_triangulate",
     "pnec_hip_nec_eigensolver",
     "pnec_hip_ransac_eigensolver",
     "pnec_hip_problem_select",
@@ -212,6 +214,7 @@ def lib() -> C.CDLL:
     L.pnec_hip_pose_covariance.argtypes = [_vp, _vp, _vp, C.c_int32, C.c_double, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]
     L.pnec_hip_residuals.argtypes = [_vp, _vp, _vp, C.c_int32, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                      C.c_int, _vp]
+    L.pnec_hip_triangulate.argtypes = [_vp, _vp, _vp, C.c_int32, C.c_int32] + [_vp] * 11 + [C.c_int, _vp]
     L.pnec_hip_describe_launch.argtypes = [_vp, C.POINTER(Options)] + [C.POINTER(C.c_int32)] * 5
     L.pnec_hip_unscented_transform.argtypes = [C.c_int64, _vp, _vp, _vp, C.c_double, C.c_int, _vp, _vp,
                                                C.c_int, C.c_int, _vp]

@@ -306,6 +306,44 @@ std::vector<int> GateInliers(const bearingVectors_t &bvs_1, const bearingVectors
   return MaskToIndices(m);
 }
 
+namespace {
+// pnec_hip_triangulate for one pair (a NEC-mode batch: bearings only) at the pose as given; any output may be NULL
+void TriangulateImpl(const bearingVectors_t &bvs_1, const bearingVectors_t &bvs_2, const SE3d &camera_pose,
+                     double *points, double *depths_1, double *depths_2, uint8_t *front, int32_t *sign) {
+  if (bvs_1.size() != bvs_2.size()) throw std::invalid_argument("bvs_1 and bvs_2 differ in size");
+  if (sign) *sign = 1;
+  if (bvs_1.empty()) return;
+  const std::vector<int64_t> offsets = {0, (int64_t)bvs_1.size()};
+  Problem prob(optimization::SolverOptions().device, PNEC_HIP_MODE_NEC, offsets);
+  Check(pnec_hip_problem_fill(prob.p, 0, 1, bvs_1[0].data(), bvs_2[0].data(), nullptr, nullptr, PNEC_HIP_MEM_HOST,
+                              nullptr));
+  const Quaterniond q(camera_pose.rotationMatrix());
+  Check(pnec_hip_triangulate(prob.p, q.coeffs(), camera_pose.translation().data(), 1, 0, points, depths_1, depths_2,
+                             nullptr, nullptr, front, nullptr, nullptr, sign, nullptr, nullptr, PNEC_HIP_MEM_HOST,
+                             nullptr));
+}
+}  // namespace
+
+std::vector<Vector3d> Triangulate(const bearingVectors_t &bvs_1, const bearingVectors_t &bvs_2, const SE3d &camera_pose,
+                                  std::vector<double> *depths_1, std::vector<double> *depths_2,
+                                  std::vector<uint8_t> *front) {
+  const size_t n = bvs_1.size();
+  std::vector<Vector3d> points(n);
+  if (depths_1) depths_1->assign(n, 0.0);
+  if (depths_2) depths_2->assign(n, 0.0);
+  if (front) front->assign(n, 0);
+  static_assert(sizeof(Vector3d) == 3 * sizeof(double), "Vector3d is three packed doubles");
+  TriangulateImpl(bvs_1, bvs_2, camera_pose, n ? points[0].data() : nullptr, depths_1 ? depths_1->data() : nullptr,
+                  depths_2 ? depths_2->data() : nullptr, front ? front->data() : nullptr, nullptr);
+  return points;
+}
+
+SE3d OrientTranslation(const bearingVectors_t &bvs_1, const bearingVectors_t &bvs_2, const SE3d &camera_pose) {
+  int32_t sign = 1;
+  TriangulateImpl(bvs_1, bvs_2, camera_pose, nullptr, nullptr, nullptr, nullptr, &sign);
+  return SE3d(camera_pose.rotationMatrix(), camera_pose.translation() * (double)sign);
+}
+
 std::ostream &operator<<(std::ostream &os, const FrameTiming &ft) {
   const long fields[] = {(long)ft.id_,    ft.frame_loading_, ft.feature_creation_,      ft.nec_es_,
                          ft.it_es_,       ft.avg_it_es_,     ft.ceres_,

@@ -122,6 +122,20 @@ std::vector<int> GateInliers(const bearingVectors_t &bvs_1, const bearingVectors
                              const std::vector<Matrix3d> &covs_1, const std::vector<Matrix3d> &covs_2,
                              const SE3d &camera_pose, double gate = 3.0, double regularization = 1e-13);
 
+// Addition (the reference scores a translation with TranslationalDifference(..., both_directions = true) and never
+// decides between t and -t): midpoint triangulation of every correspondence at camera_pose AS GIVEN --
+// pnec_hip_triangulate for one pair without PNEC_HIP_TRI_ORIENT, include/pnec_hip.h has the definitions.  Returns the
+// points in frame 1; lengths are in units of the baseline (the translation is used as a direction).  depths_1 along
+// bvs_1 from camera 1, depths_2 along R bvs_2 from camera 2, front[i] = 1 iff both depths are positive.  Parallel rays:
+// depths +inf, point NaN, front 0.
+std::vector<Vector3d> Triangulate(const bearingVectors_t &bvs_1, const bearingVectors_t &bvs_2, const SE3d &camera_pose,
+                                  std::vector<double> *depths_1 = nullptr, std::vector<double> *depths_2 = nullptr,
+                                  std::vector<uint8_t> *front = nullptr);
+// camera_pose with its translation multiplied by the cheirality vote's sign: -1 if more correspondences triangulate
+// behind both cameras than in front of both, else +1 (a tie, no correspondences included).  Rotation and the
+// translation's magnitude are untouched.
+SE3d OrientTranslation(const bearingVectors_t &bvs_1, const bearingVectors_t &bvs_2, const SE3d &camera_pose);
+
 }  // namespace common
 
 namespace optimization {

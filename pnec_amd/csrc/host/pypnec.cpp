@@ -238,6 +238,32 @@ std::vector<int> gate_inliers(arr bvs1, arr bvs2, arr covs, arr pose, double gat
                                    ToPose(pose), gate, regularization);
 }
 
+// (points [N,3], depth1 [N], depth2 [N], front [N] uint8) at `pose` as given, lengths in baselines
+py::tuple triangulate(arr bvs1, arr bvs2, arr pose) {
+  std::vector<double> d1, d2;
+  std::vector<uint8_t> front;
+  const std::vector<pnec::Vector3d> pts =
+      pnec::common::Triangulate(ToBearings(bvs1, "bvs_1"), ToBearings(bvs2, "bvs_2"), ToPose(pose), &d1, &d2, &front);
+  const py::ssize_t n = (py::ssize_t)pts.size();
+  py::array_t<double> P({n, (py::ssize_t)3}), D1(n), D2(n);
+  py::array_t<uint8_t> F(n);
+  auto p = P.mutable_unchecked<2>();
+  auto a = D1.mutable_unchecked<1>();
+  auto b = D2.mutable_unchecked<1>();
+  auto f = F.mutable_unchecked<1>();
+  for (py::ssize_t i = 0; i < n; ++i) {
+    for (int k = 0; k < 3; ++k) p(i, k) = pts[(size_t)i][k];
+    a(i) = d1[(size_t)i];
+    b(i) = d2[(size_t)i];
+    f(i) = front[(size_t)i];
+  }
+  return py::make_tuple(P, D1, D2, F);
+}
+
+arr orient_translation(arr bvs1, arr bvs2, arr pose) {
+  return FromPose(pnec::common::OrientTranslation(ToBearings(bvs1, "bvs_1"), ToBearings(bvs2, "bvs_2"), ToPose(pose)));
+}
+
 // PNEC::Solve for ONE frame pair through the overload asked for (pnec.cc:69-75, :77-124, :126-134,
 // :135-208): overload 0 = (bvs1, bvs2, covs, init), 1 = (+ inliers), 2 = (+ timing), 3 = (+ inliers,
 // timing).  Returns (pose 4x4, inliers or None, timing dict or None).
@@ -328,6 +354,12 @@ PYBIND11_MODULE(pypnec, m) {
         py::arg("gate") = 3.0, py::arg("regularization") = 1e-13, py::arg("covs_host") = py::none(),
         "pnec::common::GateInliers (addition; device): indices of the correspondences with |residual| <= gate (sigmas) "
         "at `pose`, a pose already near the truth");
+  m.def("triangulate", &triangulate, py::arg("bvs1"), py::arg("bvs2"), py::arg("pose"),
+        "pnec::common::Triangulate (addition; device): (points [N,3] in frame 1, depth1, depth2, front) by midpoint "
+        "triangulation at `pose` as given, lengths in baselines -- include/pnec_hip.h pnec_hip_triangulate");
+  m.def("orient_translation", &orient_translation, py::arg("bvs1"), py::arg("bvs2"), py::arg("pose"),
+        "pnec::common::OrientTranslation (addition; device): `pose` with its translation multiplied by the cheirality "
+        "vote's sign, so that the structure lies in front of both cameras");
   m.def("solve", &solve, py::arg("bvs1"), py::arg("bvs2"), py::arg("covs"), py::arg("init_pose"),
         py::arg("overload") = 1, py::arg("use_ransac") = true, py::arg("use_nec") = false,
         py::arg("use_ceres") = true, py::arg("weighted_iterations") = 10, py::arg("regularization") = 1e-13,

@@ -18,6 +18,7 @@
 #include "pnec_internal.hpp"
 #include "pnec_pose_cov.hpp"
 #include "pnec_residuals.hpp"
+#include "pnec_triangulate.hpp"
 #include "pnec_solve_kernel.hpp"
 #include "pnec_solve_group_kernel.hpp"
 
@@ -1110,6 +1111,80 @@ int pnec_hip_residuals(pnec_hip_problem *p, const double *q, const double *t, in
   // n_max of a batch whose sizes still live on the device (select) is the source's: an upper bound, which is all the
   // block size needs (the wavefronts a pair uses follow from its own count)
   PNEC_HIP_TRY(launch_residuals(p->mode, S, cov_waves(p->n_max), a, stream));
+  return space == PNEC_HIP_MEM_HOST ? stage.finish() : 0;
+}
+
+// depths, points, parallax and depth variance per correspondence, the cheirality vote per (pair, pose) slot:
+// pnec_triangulate.hip
+int pnec_hip_triangulate(pnec_hip_problem *p, const double *q, const double *t, int32_t n_hyp, int32_t flags,
+                         double *out_point, double *out_depth1, double *out_depth2, double *out_parallax,
+                         double *out_depth1_var, uint8_t *out_front, int32_t *out_n_front, int32_t *out_n_back,
+                         int32_t *out_sign, double *out_t_oriented, double *out_parallax_mean, int space, void *stream_) {
+  if (!p) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "triangulate: problem is NULL");
+  if (!q || !t) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "triangulate: q or t is NULL");
+  if (n_hyp < 1) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "triangulate: n_hyp must be >= 1");
+  if (flags & ~PNEC_HIP_TRI_ORIENT) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "triangulate: unknown bit in flags");
+  if (!out_point && !out_depth1 && !out_depth2 && !out_parallax && !out_depth1_var && !out_front && !out_n_front &&
+      !out_n_back && !out_sign && !out_t_oriented && !out_parallax_mean)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "triangulate: every output is NULL");
+  if (space != PNEC_HIP_MEM_DEVICE && space != PNEC_HIP_MEM_HOST)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "triangulate: bad memory space");
+  const int64_t S = p->n_pairs * (int64_t)n_hyp;
+  if (S == 0) return 0;
+  if (S > 0x7fffffffLL) return fail(PNEC_HIP_ERR_UNSUPPORTED, "more than 2^31-1 poses in one call");
+  // (the kernel addresses a pair's planes with 32-bit byte offsets)
+  if ((int64_t)num_components(p->mode) * (((int64_t)p->n_max + kWave - 1) & ~(int64_t)(kWave - 1)) * 8 > 0xffffffffLL)
+    return fail(PNEC_HIP_ERR_UNSUPPORTED, "triangulate: a pair of 4 GiB of planes or more");
+  DeviceGuard guard(p->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  HostStage stage(p, stream);
+  TriangulateArgs a;
+  a.data = p->d_data;
+  a.block_offset = p->d_block_offset;
+  a.count = p->d_count;
+  a.offsets = p->d_offsets;
+  a.n_hyp = n_hyp;
+  a.flags = flags;
+  if (space == PNEC_HIP_MEM_DEVICE) {
+    // (a batch whose sizes still live on the device needs no host-side number here: the kernel reads its offsets)
+    a.q = q;
+    a.t = t;
+    a.out_point = out_point;
+    a.out_depth1 = out_depth1;
+    a.out_depth2 = out_depth2;
+    a.out_parallax = out_parallax;
+    a.out_depth1_var = out_depth1_var;
+    a.out_front = out_front;
+    a.out_n_front = out_n_front;
+    a.out_n_back = out_n_back;
+    a.out_sign = out_sign;
+    a.out_t_oriented = out_t_oriented;
+    a.out_parallax_mean = out_parallax_mean;
+  } else {
+    // the lengths of the caller's arrays are the batch's own totals: a batch made by select waits for its sizes here
+    if (int rc = materialize(p)) return rc;
+    const int64_t M = p->n_corr * (int64_t)n_hyp;   // entries of a per-correspondence array
+    // stage: [q 4S | t 3S | t_oriented 3S | parallax mean S | point 3M | depth1 M | depth2 M | parallax M | variance M |
+    //         front M bytes], ints [n_front S | n_back S | sign S]
+    if (int rc = stage.reserve(11 * S + 7 * M + (M + 7) / 8, 3 * S)) return rc;
+    a.q = stage.up(q, 4 * S);
+    a.t = stage.up(t, 3 * S);
+    a.out_t_oriented = stage.out(out_t_oriented, 3 * S);
+    a.out_parallax_mean = stage.out(out_parallax_mean, S);
+    a.out_point = stage.out(out_point, 3 * M);
+    a.out_depth1 = stage.out(out_depth1, M);
+    a.out_depth2 = stage.out(out_depth2, M);
+    a.out_parallax = stage.out(out_parallax, M);
+    a.out_depth1_var = stage.out(out_depth1_var, M);
+    a.out_front = stage.out(out_front, M);
+    a.out_n_front = stage.out(out_n_front, S);
+    a.out_n_back = stage.out(out_n_back, S);
+    a.out_sign = stage.out(out_sign, S);
+    if (int rc = stage.status()) return rc;
+  }
+  // n_max of a batch whose sizes still live on the device (select) is the source's: an upper bound, which is all the
+  // block size needs (the wavefronts a pair uses follow from its own count)
+  PNEC_HIP_TRY(launch_triangulate(p->mode, S, cov_waves(p->n_max), a, stream));
   return space == PNEC_HIP_MEM_HOST ? stage.finish() : 0;
 }
 
