@@ -26,6 +26,8 @@
  *    would return for the problems of pnec_ceres.cc / nec_ceres.cc)
  *   (no counterpart: the structure a pose implies and the sign of t,   pnec_hip_triangulate
  *    which TranslationalDifference(..., both_directions = true) hides)
+ *   (no counterpart: the length of one pair's baseline in units of    pnec_hip_relative_scale
+ *    the previous pair's, from the tracks both see)
  *   PNEC::Eigensolver (no RANSAC) / WeightedEigensolver  pnec.cc:231-348   pnec_hip_nec_eigensolver /
  *                                                               pnec_hip_weighted_eigensolver
  *
@@ -421,6 +423,59 @@ int pnec_hip_triangulate(pnec_hip_problem *p, const double *q, const double *t, 
                          double *out_point, double *out_depth1, double *out_depth2, double *out_parallax,
                          double *out_depth1_var, uint8_t *out_front, int32_t *out_n_front, int32_t *out_n_back,
                          int32_t *out_sign, double *out_t_oriented, double *out_parallax_mean, int space, void *stream);
+
+/* Relative scale between consecutive pairs from linked tracks (added within ABI 8: a pure addition,
+ * PNEC_HIP_ABI_VERSION is unchanged).  Every pose carries t as a direction, so each pair is reconstructed with a
+ * baseline of 1; a track seen in three consecutive frames has a depth from the shared middle camera in both
+ * reconstructions, and the quotient of the two is the ratio of the baselines.
+ *
+ * `cur` holds the P pairs whose baseline is wanted, `prev` the pairs they are compared with: the same handle (a sequence
+ * stored as consecutive pairs of one batch) or another handle on the same device; the modes need not be equal, only the
+ * six bearing planes of either are read.  prev_pair int64 [P]: entry p is the pair of `prev` whose SECOND camera is pair
+ * p's FIRST camera, or -1 if there is none (a value at or above prev's number of pairs is read as -1).  link int32
+ * [sum N of cur], laid out by cur's own offsets: for correspondence i of pair p the index, within pair prev_pair[p] of
+ * `prev`, of the same physical track; an entry below 0 or at / above that pair's count is "not linked"; duplicates are
+ * allowed.  Poses: q_cur [P,4] / t_cur [P,3] one per pair of cur, q_prev / t_prev one per pair of prev, with the
+ * conventions of pnec_hip_triangulate (q xyzw normalised inside, t a direction, t = 0 read as (0, 0, 1)); there is no
+ * n_hyp.  The SIGN of t matters and this call does not vote: pass translations that put the structure in front, i.e.
+ * out_t_oriented of pnec_hip_triangulate.
+ *
+ * Per link, with c the midpoint system (pnec_hip_triangulate's) of the correspondence in the current pair and r that of
+ * the linked correspondence in the previous pair:
+ *   ratio = (r.depth2 * sqrt(r.a11)) / (c.depth1 * sqrt(c.a00))        = |baseline_cur| / |baseline_prev|
+ * (the depths multiply bearings that are not assumed unit: the square roots make both terms metric distances from the
+ * shared camera).  A link is USED iff both systems are `front` at the poses given, both pass the parallax gate and
+ * ratio is a positive finite number.  Parallax gate: min_parallax in radians, >= 0 and finite; 0 switches it off.  It
+ * compares sin^2 psi = D / (a00 a11) with sin^2(min_parallax), as D >= sin^2(min_parallax) * (a00 a11) with D formed
+ * from two rounded products as in pnec_hip_triangulate; and ONLY IF min_parallax > 0 it additionally requires a10 > 0
+ * (a parallax below 90 degrees, without which sin^2 does not order angles).  min_parallax >= pi/2 leaves no link.
+ *
+ * Outputs; every pointer may be NULL (not wanted), not all of them.
+ *   out_ratio double [sum N cur]   the value of a used link, NaN otherwise
+ *   out_used  uint8  [sum N cur]   1 for a used link, else 0
+ *   out_n_linked int32 [P]         links within range        out_n_used int32 [P]   links used (m below)
+ *   out_scale double [P,3]         with the m used ratios in ascending order x_0 <= ... <= x_(m-1): the elements of rank
+ *                                  (m-1)/4, (m-1)/2 and 3(m-1)/4 (integer division): lower quartile, lower median (THE
+ *                                  SCALE) and upper quartile, each an element of the set, never an interpolation; NaN
+ *                                  for m = 0.  log(q75 / q25) / 1.349 is a robust sigma of the scale's logarithm.
+ * The order statistics are exact: a most-significant-digit-first radix selection over the 64-bit patterns (positive
+ * finite doubles order as their patterns), no atomics on global memory, no sort.  A pair's outputs depend only on its
+ * own data, its linked pair's data and the two poses: not on the batch it sits in, on `space`, or on prev == cur.
+ * When out_ratio is NULL the ratios live in a workspace of 8 bytes * sum N that `cur` owns and keeps until it is
+ * destroyed; calls on one handle that overlap in time must therefore pass out_ratio.
+ *
+ * Batches made by pnec_hip_problem_select(_view) and reshaped capacity batches are accepted on either side, positions
+ * following each batch's own offsets and sizes.  DEVICE space: offsets and sizes are read on the device, nothing waits,
+ * the call is asynchronous on `stream`.  HOST space: the call first resolves cur's sizes, stages in cur's staging buffer
+ * (13 bytes per correspondence) and blocks.  A batch whose largest pair holds 4 GiB of planes or more:
+ * PNEC_HIP_ERR_UNSUPPORTED.
+ * NULL cur / prev / prev_pair / link / q_cur / t_cur / q_prev / t_prev, a negative, NaN or infinite min_parallax, all
+ * outputs NULL or a bad `space`: PNEC_HIP_ERR_INVALID_ARGUMENT before a handle is read or any device is touched; after
+ * that, two handles on different devices: PNEC_HIP_ERR_INVALID_ARGUMENT. */
+int pnec_hip_relative_scale(pnec_hip_problem *cur, pnec_hip_problem *prev, const int64_t *prev_pair, const int32_t *link,
+                            const double *q_cur, const double *t_cur, const double *q_prev, const double *t_prev,
+                            double min_parallax, double *out_ratio, uint8_t *out_used, double *out_scale,
+                            int32_t *out_n_linked, int32_t *out_n_used, int space, void *stream);
 
 /* PNEC::Eigensolver with use_ransac_ = false (src/rel_pose_estimation/pnec.cc:273-278) for every
  * pair: rotation by opengv-style eigenvalue minimisation (Kneip-Lynen; opengv is not in the

@@ -8,6 +8,9 @@ Layout:
   distributed.py   one-process-per-GPU sharding of independent pair batches + one RCCL gather
 """
 from . import capi  # noqa: F401
-from .batch import Batch, PoseCovariance, ResidualReport, SolveResult, Triangulation, gate_sigma, select_best  # noqa: F401
+from .batch import (Batch, PoseCovariance, RelativeScale, ResidualReport, SolveResult, Triangulation, gate_sigma,  # noqa: F401
+                    select_best)
+from .tracks import chain_scales  # noqa: F401
 
-__all__ = ["capi", "Batch", "PoseCovariance", "ResidualReport", "SolveResult", "Triangulation", "gate_sigma", "select_best"]
+__all__ = ["capi", "Batch", "PoseCovariance", "RelativeScale", "ResidualReport", "SolveResult", "Triangulation", "chain_scales",
+           "gate_sigma", "select_best"]

@@ -186,6 +186,32 @@ class Triangulation:
     n_hyp: int = 1
 
 
+@dataclass
+class RelativeScale:
+    """pnec_hip_relative_scale's outputs (include/pnec_hip.h has the definitions): the ratio of each pair's baseline to
+    its previous pair's, from the tracks the two pairs share.  Per pair [P]: `scale` (the lower median of the used
+    ratios -- an element of the set), `q25` / `q75` (lower / upper quartile), `n_linked`, `n_used`; NaN where no link was
+    used.  Per correspondence of the current batch [sum N], when asked for: `ratio` (NaN for a link that is not used) and
+    `used` (uint8)."""
+    scale: object          # [P] |baseline_cur| / |baseline_prev|
+    q25: object            # [P]
+    q75: object            # [P]
+    n_linked: object       # [P] int32, links within range
+    n_used: object         # [P] int32, links in front at both poses, past the parallax gate, with a positive finite ratio
+    ratio: object = None   # [sum N] or None (per_link=False)
+    used: object = None    # [sum N] uint8 or None
+    offsets: np.ndarray = None  # int64 [P+1], the current batch's own
+
+    def log_sigma(self):
+        """log(q75 / q25) / 1.349: a robust standard deviation of log(scale) (the interquartile range of a normal
+        distribution is 1.349 sigma).  numpy or torch, matching the stored arrays."""
+        if _is_torch(self.q75):
+            import torch
+            return torch.log(self.q75 / self.q25) / 1.349
+        with np.errstate(all="ignore"):
+            return np.log(np.asarray(self.q75) / np.asarray(self.q25)) / 1.349
+
+
 class Batch:
     """A batch of independent frame pairs in the solver's SoA layout (``pnec_hip_problem``)."""
 
@@ -758,6 +784,62 @@ class Batch:
         capi.check(self._lib.pnec_hip_triangulate(self._h, p(q), p(t), n_hyp, flags, p(point), p(d1), p(d2), p(psi),
                                                   p(var), p(front), p(nf), p(nb), p(sign), p(to), p(mean), space, stream))
         return Triangulation(point, d1, d2, psi, var, front, nf, nb, sign, to, mean, offsets, n_hyp)
+
+
+    def relative_scale(self, prev, prev_pair, link, q, t, q_prev, t_prev, min_parallax: float = 0.0,
+                       per_link: bool = True) -> RelativeScale:
+        """The ratio of every pair's baseline to that of its previous pair, from the tracks both see
+        (pnec_hip_relative_scale).  `prev` is the batch of previous pairs (may be `self`); prev_pair int64 [P] names, per
+        pair of this batch, the pair of `prev` whose second camera is this pair's first (-1: none); link int32 [sum N]
+        gives, per correspondence, the index of the same track within that previous pair (-1: not linked) --
+        pnec_amd.tracks.Tracks.links() builds both.  q [P,4] / t [P,3] are this batch's poses, q_prev / t_prev those of
+        `prev`; the translations must carry the sign that puts the structure in front (Triangulation.t).  min_parallax
+        (radians) leaves out links whose parallax in either pair is smaller.  per_link=False skips the two
+        per-correspondence outputs.  torch.cuda tensors in -> torch.cuda tensors out, asynchronous on torch's current
+        stream; numpy in -> numpy out."""
+        if not isinstance(prev, Batch):
+            raise TypeError("prev must be a Batch (it may be this one)")
+        min_parallax = float(min_parallax)
+        if not (min_parallax >= 0.0) or not np.isfinite(min_parallax):
+            raise ValueError("min_parallax must be >= 0 and finite (radians)")
+        P, Pp = self.n_pairs, prev.n_pairs
+        offsets = self.offsets     # (a batch made by select: waits for its sizes)
+        M = int(offsets[-1])
+        if _is_torch(q):
+            import torch
+            q = self._dev_tensor(q, "q", (P, 4))
+            t = self._dev_tensor(t, "t", (P, 3))
+            q_prev = self._dev_tensor(q_prev, "q_prev", (Pp, 4))
+            t_prev = self._dev_tensor(t_prev, "t_prev", (Pp, 3))
+            dev = q.device
+            as_dev = lambda a, dt: a.to(device=dev, dtype=dt).contiguous() if _is_torch(a) else \
+                torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=dev)
+            prev_pair, link = as_dev(prev_pair, torch.int64), as_dev(link, torch.int32)
+            f64 = dict(dtype=torch.float64, device=dev)
+            scale = torch.empty((P, 3), **f64)
+            nl, nu = (torch.empty((P,), dtype=torch.int32, device=dev) for _ in range(2))
+            ratio = torch.empty((M,), **f64) if per_link else None
+            used = torch.empty((M,), dtype=torch.uint8, device=dev) if per_link else None
+            p = lambda a: None if a is None else a.data_ptr()
+            space, stream = capi.MEM_DEVICE, torch.cuda.current_stream(self.device).cuda_stream
+        else:
+            q, t, q_prev, t_prev = (np.ascontiguousarray(a, dtype=np.float64) for a in (q, t, q_prev, t_prev))
+            if q.shape != (P, 4) or t.shape != (P, 3) or q_prev.shape != (Pp, 4) or t_prev.shape != (Pp, 3):
+                raise ValueError("q must be [n_pairs,4] (xyzw), t [n_pairs,3]; q_prev / t_prev one per pair of prev")
+            prev_pair = np.ascontiguousarray(prev_pair, dtype=np.int64)
+            link = np.ascontiguousarray(link, dtype=np.int32)
+            scale = np.empty((P, 3))
+            nl, nu = (np.empty(P, dtype=np.int32) for _ in range(2))
+            ratio = np.empty(M) if per_link else None
+            used = np.empty(M, dtype=np.uint8) if per_link else None
+            p = lambda a: None if a is None else a.ctypes.data
+            space, stream = capi.MEM_HOST, None
+        if tuple(prev_pair.shape) != (P,) or tuple(link.shape) != (M,):
+            raise ValueError("prev_pair must be [n_pairs], link [sum N] (one entry per correspondence of this batch)")
+        capi.check(self._lib.pnec_hip_relative_scale(self._h, prev._h, p(prev_pair), p(link), p(q), p(t), p(q_prev),
+                                                     p(t_prev), min_parallax, p(ratio), p(used), p(scale), p(nl), p(nu),
+                                                     space, stream))
+        return RelativeScale(scale[:, 1], scale[:, 0], scale[:, 2], nl, nu, ratio, used, offsets)
 
 
 def select_best(cost, n_hyp: int, device: int = 0):

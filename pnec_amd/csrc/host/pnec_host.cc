@@ -344,6 +344,40 @@ SE3d OrientTranslation(const bearingVectors_t &bvs_1, const bearingVectors_t &bv
   return SE3d(camera_pose.rotationMatrix(), camera_pose.translation() * (double)sign);
 }
 
+double RelativeScale(const bearingVectors_t &bvs_prev_1, const bearingVectors_t &bvs_prev_2, const SE3d &pose_prev,
+                     const bearingVectors_t &bvs_1, const bearingVectors_t &bvs_2, const SE3d &camera_pose,
+                     const std::vector<int> &link, double min_parallax, double *q25, double *q75, int *n_used,
+                     std::vector<double> *ratios) {
+  if (bvs_prev_1.size() != bvs_prev_2.size()) throw std::invalid_argument("bvs_prev_1 and bvs_prev_2 differ in size");
+  if (bvs_1.size() != bvs_2.size()) throw std::invalid_argument("bvs_1 and bvs_2 differ in size");
+  if (link.size() != bvs_1.size()) throw std::invalid_argument("link must have one entry per current correspondence");
+  const double nan = std::nan("");
+  const size_t n = bvs_1.size();
+  double scale[3] = {nan, nan, nan};
+  int32_t used = 0;
+  if (ratios) ratios->assign(n, nan);
+  if (n > 0 && !bvs_prev_1.empty()) {
+    const int device = optimization::SolverOptions().device;
+    Problem prev(device, PNEC_HIP_MODE_NEC, {0, (int64_t)bvs_prev_1.size()});
+    Problem cur(device, PNEC_HIP_MODE_NEC, {0, (int64_t)n});
+    Check(pnec_hip_problem_fill(prev.p, 0, 1, bvs_prev_1[0].data(), bvs_prev_2[0].data(), nullptr, nullptr,
+                                PNEC_HIP_MEM_HOST, nullptr));
+    Check(pnec_hip_problem_fill(cur.p, 0, 1, bvs_1[0].data(), bvs_2[0].data(), nullptr, nullptr, PNEC_HIP_MEM_HOST,
+                                nullptr));
+    const Quaterniond qc(camera_pose.rotationMatrix()), qp(pose_prev.rotationMatrix());
+    const int64_t prev_pair = 0;
+    const std::vector<int32_t> link32(link.begin(), link.end());
+    Check(pnec_hip_relative_scale(cur.p, prev.p, &prev_pair, link32.data(), qc.coeffs(),
+                                  camera_pose.translation().data(), qp.coeffs(), pose_prev.translation().data(),
+                                  min_parallax, ratios ? ratios->data() : nullptr, nullptr, scale, nullptr, &used,
+                                  PNEC_HIP_MEM_HOST, nullptr));
+  }
+  if (q25) *q25 = scale[0];
+  if (q75) *q75 = scale[2];
+  if (n_used) *n_used = (int)used;
+  return scale[1];
+}
+
 std::ostream &operator<<(std::ostream &os, const FrameTiming &ft) {
   const long fields[] = {(long)ft.id_,    ft.frame_loading_, ft.feature_creation_,      ft.nec_es_,
                          ft.it_es_,       ft.avg_it_es_,     ft.ceres_,

@@ -136,6 +136,19 @@ std::vector<Vector3d> Triangulate(const bearingVectors_t &bvs_1, const bearingVe
 // translation's magnitude are untouched.
 SE3d OrientTranslation(const bearingVectors_t &bvs_1, const bearingVectors_t &bvs_2, const SE3d &camera_pose);
 
+// Addition (every pose of the reference carries its translation as a direction; nothing in it relates the baseline of one
+// frame pair to the next): the length of camera_pose's baseline in units of pose_prev's, from the tracks the two pairs
+// share -- pnec_hip_relative_scale for one frame, include/pnec_hip.h has the definitions.  (bvs_prev_1, bvs_prev_2,
+// pose_prev) is the previous pair, whose SECOND camera is the first camera of (bvs_1, bvs_2, camera_pose); link[i] is
+// the index in the previous pair of the track of current correspondence i, -1 if it is not there.  Both translations
+// must carry the sign that puts the structure in front (OrientTranslation).  Returns the lower median of the used links'
+// ratios (NaN if none is used); q25 / q75 its lower / upper quartile, n_used the number of links used, ratios the
+// per-correspondence values (NaN where not used).  min_parallax (radians) leaves out links of smaller parallax.
+double RelativeScale(const bearingVectors_t &bvs_prev_1, const bearingVectors_t &bvs_prev_2, const SE3d &pose_prev,
+                     const bearingVectors_t &bvs_1, const bearingVectors_t &bvs_2, const SE3d &camera_pose,
+                     const std::vector<int> &link, double min_parallax = 0.0, double *q25 = nullptr,
+                     double *q75 = nullptr, int *n_used = nullptr, std::vector<double> *ratios = nullptr);
+
 }  // namespace common
 
 namespace optimization {

@@ -264,6 +264,21 @@ arr orient_translation(arr bvs1, arr bvs2, arr pose) {
   return FromPose(pnec::common::OrientTranslation(ToBearings(bvs1, "bvs_1"), ToBearings(bvs2, "bvs_2"), ToPose(pose)));
 }
 
+// (scale, q25, q75, n_used, ratio [N]) of one frame against the previous one
+py::tuple relative_scale(arr bvs_prev1, arr bvs_prev2, arr pose_prev, arr bvs1, arr bvs2, arr pose,
+                         const std::vector<int> &link, double min_parallax) {
+  double q25 = 0.0, q75 = 0.0;
+  int n_used = 0;
+  std::vector<double> ratios;
+  const double scale = pnec::common::RelativeScale(ToBearings(bvs_prev1, "bvs_prev_1"), ToBearings(bvs_prev2, "bvs_prev_2"),
+                                                   ToPose(pose_prev), ToBearings(bvs1, "bvs_1"), ToBearings(bvs2, "bvs_2"),
+                                                   ToPose(pose), link, min_parallax, &q25, &q75, &n_used, &ratios);
+  py::array_t<double> R((py::ssize_t)ratios.size());
+  auto r = R.mutable_unchecked<1>();
+  for (py::ssize_t i = 0; i < (py::ssize_t)ratios.size(); ++i) r(i) = ratios[(size_t)i];
+  return py::make_tuple(scale, q25, q75, n_used, R);
+}
+
 // PNEC::Solve for ONE frame pair through the overload asked for (pnec.cc:69-75, :77-124, :126-134,
 // :135-208): overload 0 = (bvs1, bvs2, covs, init), 1 = (+ inliers), 2 = (+ timing), 3 = (+ inliers,
 // timing).  Returns (pose 4x4, inliers or None, timing dict or None).
@@ -360,6 +375,11 @@ PYBIND11_MODULE(pypnec, m) {
   m.def("orient_translation", &orient_translation, py::arg("bvs1"), py::arg("bvs2"), py::arg("pose"),
         "pnec::common::OrientTranslation (addition; device): `pose` with its translation multiplied by the cheirality "
         "vote's sign, so that the structure lies in front of both cameras");
+  m.def("relative_scale", &relative_scale, py::arg("bvs_prev1"), py::arg("bvs_prev2"), py::arg("pose_prev"),
+        py::arg("bvs1"), py::arg("bvs2"), py::arg("pose"), py::arg("link"), py::arg("min_parallax") = 0.0,
+        "pnec::common::RelativeScale (addition; device): (scale, q25, q75, n_used, ratio [N]) -- the baseline of `pose` in "
+        "units of the baseline of `pose_prev` from the tracks `link` ties to the previous pair -- include/pnec_hip.h "
+        "pnec_hip_relative_scale");
   m.def("solve", &solve, py::arg("bvs1"), py::arg("bvs2"), py::arg("covs"), py::arg("init_pose"),
         py::arg("overload") = 1, py::arg("use_ransac") = true, py::arg("use_nec") = false,
         py::arg("use_ceres") = true, py::arg("weighted_iterations") = 10, py::arg("regularization") = 1e-13,

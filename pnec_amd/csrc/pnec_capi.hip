@@ -18,6 +18,7 @@
 #include "pnec_internal.hpp"
 #include "pnec_pose_cov.hpp"
 #include "pnec_residuals.hpp"
+#include "pnec_relative_scale.hpp"
 #include "pnec_triangulate.hpp"
 #include "pnec_solve_kernel.hpp"
 #include "pnec_solve_group_kernel.hpp"
@@ -585,6 +586,7 @@ int pnec_hip_problem_destroy(pnec_hip_problem *p) {
   }
   release(p->d_stage);
   release(p->d_stage_i);
+  release(p->d_ratio);
   release(p->d_front);
   release(p->d_front_i);
   release(p->d_hint_its);
@@ -1185,6 +1187,98 @@ int pnec_hip_triangulate(pnec_hip_problem *p, const double *q, const double *t, 
   // n_max of a batch whose sizes still live on the device (select) is the source's: an upper bound, which is all the
   // block size needs (the wavefronts a pair uses follow from its own count)
   PNEC_HIP_TRY(launch_triangulate(p->mode, S, cov_waves(p->n_max), a, stream));
+  return space == PNEC_HIP_MEM_HOST ? stage.finish() : 0;
+}
+
+// the ratio of every pair's baseline to its previous pair's from the tracks they share, and three exact order
+// statistics of it per pair: pnec_relative_scale.hip
+int pnec_hip_relative_scale(pnec_hip_problem *cur, pnec_hip_problem *prev, const int64_t *prev_pair, const int32_t *link,
+                            const double *q_cur, const double *t_cur, const double *q_prev, const double *t_prev,
+                            double min_parallax, double *out_ratio, uint8_t *out_used, double *out_scale,
+                            int32_t *out_n_linked, int32_t *out_n_used, int space, void *stream_) {
+  if (!cur || !prev) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "relative_scale: cur or prev problem is NULL");
+  if (!prev_pair || !link) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "relative_scale: prev_pair or link is NULL");
+  if (!q_cur || !t_cur || !q_prev || !t_prev)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "relative_scale: a pose pointer (q_cur, t_cur, q_prev, t_prev) is NULL");
+  if (!(min_parallax >= 0.0) || !std::isfinite(min_parallax))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "relative_scale: min_parallax must be >= 0 and finite (radians)");
+  if (!out_ratio && !out_used && !out_scale && !out_n_linked && !out_n_used)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "relative_scale: every output is NULL");
+  if (space != PNEC_HIP_MEM_DEVICE && space != PNEC_HIP_MEM_HOST)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "relative_scale: bad memory space");
+  if (cur->device != prev->device)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "relative_scale: cur and prev live on different devices");
+  const int64_t P = cur->n_pairs, Pp = prev->n_pairs;
+  if (P == 0) return 0;
+  if (P > 0x7fffffffLL) return fail(PNEC_HIP_ERR_UNSUPPORTED, "more than 2^31-1 pairs in one call");
+  // (the kernel addresses a pair's planes with 32-bit byte offsets, on either side)
+  for (const pnec_hip_problem *b : {(const pnec_hip_problem *)cur, (const pnec_hip_problem *)prev})
+    if ((int64_t)num_components(b->mode) * (((int64_t)b->n_max + kWave - 1) & ~(int64_t)(kWave - 1)) * 8 > 0xffffffffLL)
+      return fail(PNEC_HIP_ERR_UNSUPPORTED, "relative_scale: a pair of 4 GiB of planes or more");
+  DeviceGuard guard(cur->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  HostStage stage(cur, stream);
+  RelativeScaleArgs a;
+  a.data = cur->d_data;
+  a.block_offset = cur->d_block_offset;
+  a.count = cur->d_count;
+  a.offsets = cur->d_offsets;
+  a.prev_data = prev->d_data;
+  a.prev_block_offset = prev->d_block_offset;
+  a.prev_count = prev->d_count;
+  a.n_prev_pairs = Pp;
+  // sin^2 orders angles only below 90 degrees, which the gate's a10 > 0 enforces: from pi/2 on nothing passes
+  const double sn = std::sin(min_parallax);
+  a.sin2_min = min_parallax >= 1.5707963267948966 ? 2.0 : sn * sn;
+  a.gate_a10 = min_parallax > 0.0 ? 1 : 0;
+  if (space == PNEC_HIP_MEM_DEVICE) {
+    // (a batch whose sizes still live on the device needs no host-side number here: the kernel reads its offsets; n_corr
+    // of such a batch is the source's, an upper bound)
+    a.prev_pair = prev_pair;
+    a.link = link;
+    a.q = q_cur;
+    a.t = t_cur;
+    a.q_prev = q_prev;
+    a.t_prev = t_prev;
+    a.ratio = out_ratio;
+    if (!out_ratio) {
+      const int64_t need = std::max<int64_t>(cur->n_corr, 1);
+      if (need > cur->ratio_doubles) {
+        if (cur->d_ratio) (void)dev_free(cur->d_ratio);
+        cur->d_ratio = nullptr;
+        cur->ratio_doubles = 0;
+        PNEC_HIP_TRY(dev_alloc(&cur->d_ratio, sizeof(double) * (size_t)need));
+        cur->ratio_doubles = need;
+      }
+      a.ratio = cur->d_ratio;
+    }
+    a.out_used = out_used;
+    a.out_scale = out_scale;
+    a.out_n_linked = out_n_linked;
+    a.out_n_used = out_n_used;
+  } else {
+    // the lengths of the caller's arrays are the batch's own totals: a batch made by select waits for its sizes here
+    if (int rc = materialize(cur)) return rc;
+    const int64_t M = cur->n_corr;
+    // stage: [q 4P | t 3P | q_prev 4Pp | t_prev 3Pp | prev_pair P (int64) | scale 3P | ratio M | used M bytes],
+    //        ints [link M | n_linked P | n_used P]; the ratios are staged whether or not the caller wants them
+    if (int rc = stage.reserve(11 * P + 7 * Pp + M + (M + 7) / 8, M + 2 * P)) return rc;
+    a.q = stage.up(q_cur, 4 * P);
+    a.t = stage.up(t_cur, 3 * P);
+    a.q_prev = stage.up(q_prev, 4 * Pp);
+    a.t_prev = stage.up(t_prev, 3 * Pp);
+    a.prev_pair = stage.up(prev_pair, P);
+    a.out_scale = stage.out(out_scale, 3 * P);
+    a.ratio = stage.out(out_ratio, M, true);
+    a.out_used = stage.out(out_used, M);
+    a.link = stage.up(link, M);
+    a.out_n_linked = stage.out(out_n_linked, P);
+    a.out_n_used = stage.out(out_n_used, P);
+    if (int rc = stage.status()) return rc;
+  }
+  // n_max of a batch whose sizes still live on the device (select) is the source's: an upper bound, which is all the
+  // block size needs (the wavefronts a pair uses follow from its own count)
+  PNEC_HIP_TRY(launch_relative_scale(P, cov_waves(cur->n_max), a, stream));
   return space == PNEC_HIP_MEM_HOST ? stage.finish() : 0;
 }
 

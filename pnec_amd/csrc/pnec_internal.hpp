@@ -45,6 +45,9 @@ struct pnec_hip_problem {
   int64_t stage_doubles = 0;
   int32_t *d_stage_i = nullptr;
   int64_t stage_ints = 0;
+  // pnec_hip_relative_scale without out_ratio: the ratios between the pass and the selection (grown on demand, kept)
+  double *d_ratio = nullptr;
+  int64_t ratio_doubles = 0;
   // scratch of the front stages (sums, starts and results of the batched eigenvalue minimisation)
   double *d_front = nullptr;
   int32_t *d_front_i = nullptr;
@@ -175,6 +178,17 @@ class HostStage {
   const double *up(const double *host, int64_t n) {
     double *d = host ? take(d_next_, d_left_, n) : nullptr;
     if (d && n > 0 && err_ == hipSuccess) err_ = hipMemcpyAsync(d, host, sizeof(double) * n, hipMemcpyHostToDevice, stream_);
+    return d;
+  }
+  // the same for 64-bit integers (they live among the doubles) and 32-bit integers
+  const int64_t *up(const int64_t *host, int64_t n) {
+    int64_t *d = host ? reinterpret_cast<int64_t *>(take(d_next_, d_left_, n)) : nullptr;
+    if (d && n > 0 && err_ == hipSuccess) err_ = hipMemcpyAsync(d, host, sizeof(int64_t) * n, hipMemcpyHostToDevice, stream_);
+    return d;
+  }
+  const int32_t *up(const int32_t *host, int64_t n) {
+    int32_t *d = host ? take(i_next_, i_left_, n) : nullptr;
+    if (d && n > 0 && err_ == hipSuccess) err_ = hipMemcpyAsync(d, host, sizeof(int32_t) * n, hipMemcpyHostToDevice, stream_);
     return d;
   }
   // room for an output of n items that finish() copies to `host`; for a NULL `host`: nullptr, or with `keep` (the

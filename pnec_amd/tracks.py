@@ -77,6 +77,63 @@ class Tracks:
     def sizes(self) -> np.ndarray:
         return np.diff(self.offsets)
 
+    def links(self):
+        """(prev_pair int64 [P], link int32 [M]) for Batch.relative_scale with this file's pairs on both sides: pair k's
+        previous pair is k - 1 when both belong to the same `sequence` (one sequence if there is no `sequence`), else
+        -1 -- at the start of a sequence, and everywhere when the file carries no track ids.  link[offsets[k] + i] is the
+        row, within pair k - 1, whose frame-2 track id (`ids2`) equals the frame-1 track id (`ids1`) of row i of pair
+        k; -1 where the track is not in the previous pair (link_pairs)."""
+        off = np.asarray(self.offsets, dtype=np.int64)
+        P = len(off) - 1
+        prev_pair = np.full(P, -1, dtype=np.int64)
+        link = np.full(int(off[-1]), -1, dtype=np.int32)
+        if self.ids1 is None or self.ids2 is None:
+            return prev_pair, link
+        i1, i2 = np.asarray(self.ids1), np.asarray(self.ids2)
+        seq = None if self.sequence is None else np.asarray(self.sequence)
+        for k in range(1, P):
+            if seq is not None and seq[k] != seq[k - 1]:
+                continue
+            prev_pair[k] = k - 1
+            link[off[k]:off[k + 1]] = link_pairs(i2[off[k - 1]:off[k]], i1[off[k]:off[k + 1]])
+        return prev_pair, link
+
+
+def link_pairs(ids_prev, ids_cur) -> np.ndarray:
+    """int32 [len(ids_cur)]: for every track id of the current pair the row of the same id in the previous pair, -1
+    where the previous pair does not hold it.  A join on track ids in numpy.  An id listed more than once in `ids_prev`:
+    the FIRST row wins; an id listed more than once in `ids_cur` links every one of its rows (duplicate links are
+    allowed by pnec_hip_relative_scale)."""
+    ids_prev, ids_cur = np.asarray(ids_prev).ravel(), np.asarray(ids_cur).ravel()
+    link = np.full(len(ids_cur), -1, dtype=np.int32)
+    if len(ids_prev) == 0 or len(ids_cur) == 0:
+        return link
+    order = np.argsort(ids_prev, kind="stable")           # equal ids keep their order: the first row comes first
+    srt = ids_prev[order]
+    at = np.searchsorted(srt, ids_cur, side="left")
+    hit = at < len(srt)
+    hit[hit] = srt[at[hit]] == ids_cur[hit]
+    link[hit] = order[at[hit]].astype(np.int32)
+    return link
+
+
+def chain_scales(scale, prev_pair) -> np.ndarray:
+    """Each pair's baseline relative to the FIRST pair of its chain: 1 for a pair without a previous pair
+    (prev_pair < 0), else chain[prev_pair[p]] * scale[p] -- the cumulative product of RelativeScale.scale along
+    prev_pair.  A pair without an estimate (NaN) makes itself and everything after it in its chain NaN.  Pure numpy;
+    prev_pair[p] must lie before p (what Tracks.links() produces)."""
+    scale = np.asarray(scale.detach().cpu().numpy() if hasattr(scale, "detach") else scale, dtype=np.float64)
+    prev_pair = np.asarray(prev_pair.detach().cpu().numpy() if hasattr(prev_pair, "detach") else prev_pair, dtype=np.int64)
+    if scale.shape != prev_pair.shape or scale.ndim != 1:
+        raise ValueError("scale and prev_pair must both be [P]")
+    if (prev_pair >= np.arange(len(prev_pair))).any():
+        raise ValueError("prev_pair[p] must be smaller than p (a previous pair comes first)")
+    out = np.ones(len(scale))
+    for p in range(len(scale)):
+        if prev_pair[p] >= 0:
+            out[p] = out[prev_pair[p]] * scale[p]
+    return out
+
 
 def save_tracks(path: str, tr: Tracks) -> None:
     def host(a):
