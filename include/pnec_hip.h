@@ -259,7 +259,8 @@ int pnec_hip_select_best(int64_t n_pairs, int32_t n_hyp, const double *cost, int
 
 /* pnec::common::CostFunction (src/common/common.cc:237-259) for every pair: mean over the
  * pair's correspondences of n^2 / (g' Sigma g), no regularisation; pose given as q (xyzw,
- * normalised inside) and t.  Only for TARGET-mode problems.  out [n_pairs]. */
+ * normalised inside) and t.  Only for TARGET-mode problems.  out [n_pairs].  A pair without correspondences gets
+ * 0 / 0 = NaN (the mean of nothing), as the reference's function returns for empty input. */
 int pnec_hip_cost_function(pnec_hip_problem *p, const double *q, const double *t, double *out,
                            int space, void *stream);
 
@@ -684,7 +685,8 @@ int pnec_hip_frame_solve(pnec_hip_frame *f, int64_t n, const double *bvs1, const
  * column-major 3x3 whose top-left 2x2 is the image-plane covariance (omnidirectional: the
  * tangent-plane covariance rotated to the bearing), K_inv [9] column-major, kappa (1.0 in the
  * reference), camera_model 0 = Omnidirectional, 1 = Pinhole (enum CameraModel, common.h:62).
- * out_covs [n,9] bearing covariances; out_bvs [n,3] unit bearings or NULL. */
+ * out_covs [n,9] bearing covariances, exactly symmetric (mirror entries carry the same bits); out_bvs [n,3] unit
+ * bearings or NULL. */
 int pnec_hip_unscented_transform(int64_t n, const double *mu, const double *covs, const double *K_inv,
                                  double kappa, int camera_model, double *out_bvs, double *out_covs,
                                  int space, int device, void *stream);

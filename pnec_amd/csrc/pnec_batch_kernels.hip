@@ -156,6 +156,11 @@ __device__ __forceinline__ void unscented_core(const double (&m)[3], const doubl
 #pragma unroll
       for (int c = 0; c < 3; ++c) S[3 * c + r] += w * (tp[p][r] - mean[r]) * (tp[p][c] - mean[c]);
   }
+  // (w a_r) a_c and (w a_c) a_r round differently unless w is a power of two: both mirror entries get their mean, so that
+  // the matrix handed out is exactly symmetric.  The mean is what the ingest kernels' 0.5 * (S_rc + S_cr) stored anyway.
+  S[1] = S[3] = 0.5 * (S[1] + S[3]);
+  S[2] = S[6] = 0.5 * (S[2] + S[6]);
+  S[5] = S[7] = 0.5 * (S[5] + S[7]);
 #pragma unroll
   for (int k = 0; k < 3; ++k) bearing[k] = tp[0][k];  // normalised (K^-1) mu = Unproject
 }
