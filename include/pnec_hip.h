@@ -28,6 +28,9 @@
  *    which TranslationalDifference(..., both_directions = true) hides)
  *   (no counterpart: the length of one pair's baseline in units of    pnec_hip_relative_scale
  *    the previous pair's, from the tracks both see)
+ *   POpticalFlowPatch::setFromImage (Cov) + KLTPatchOpticalFlow's     pnec_hip_patch_covariance
+ *    scaling and rotation  include/features/tracking/pnec_patch.h:78-137,
+ *    klt_patch_optical_flow.h:244-252  (the covariance only: no tracking; double, not the reference's float)
  *   PNEC::Eigensolver (no RANSAC) / WeightedEigensolver  pnec.cc:231-348   pnec_hip_nec_eigensolver /
  *                                                               pnec_hip_weighted_eigensolver
  *
@@ -690,6 +693,78 @@ int pnec_hip_frame_solve(pnec_hip_frame *f, int64_t n, const double *bvs1, const
 int pnec_hip_unscented_transform(int64_t n, const double *mu, const double *covs, const double *K_inv,
                                  double kappa, int camera_model, double *out_bvs, double *out_covs,
                                  int space, int device, void *stream);
+
+/* Patch covariances: the 2x2 image covariance of keypoints from the image patches around them (added within ABI 8: a
+ * pure addition, PNEC_HIP_ABI_VERSION is unchanged) -- the cov2 / cov1 input of pnec_hip_problem_fill_keypoints, in its
+ * layout.  It is the quantity POpticalFlowPatch::setFromImage keeps as `Cov` (include/features/tracking/pnec_patch.h:
+ * 78-137: the top-left 2x2 block of the inverse of the patch's SE(2) Gauss-Newton Hessian) after KLTPatchOpticalFlow has
+ * divided it by uncertainty_scaling and rotated it by the tracked transform (klt_patch_optical_flow.h:244-252,375-382).
+ * This is NOT tracking: no KLT iteration, no pyramid, no detection; positions come from the caller's tracker.  Level 0
+ * only (the reference's min_level): for another level pass the downsampled image and the scaled positions.
+ * ALL ARITHMETIC IS DOUBLE.  The reference computes in float; its float bits are not reproduced and not claimed.
+ * [EXT] basalt's image.h / patterns.h are not in the reference tree: interpGrad, InBounds and Pattern52 below are
+ * restated from the published code, and what follows is this library's own definition.
+ *
+ * Input.
+ *   images      n_images images of height x width pixels, row-major, `pitch` ELEMENTS from one row to the next
+ *               (pitch >= width), image f starting at element f * height * pitch; the last row of the last image
+ *               need only hold `width` elements.  pixel_type: pnec_hip_pixel_type.
+ *   offsets     int64 [n_images + 1], non-decreasing, offsets[0] = 0, offsets[n_images] = n_points: keypoints
+ *               [offsets[f], offsets[f+1]) lie in image f (ragged; an image may have none).
+ *   pts         double [n_points, 2]: x = column, y = row, pixel centres at integers.
+ *   pattern     double [n_pattern, 2] offsets in pixels, 1 <= n_pattern <= PNEC_HIP_PATCH_MAX_POINTS (64).  The
+ *               reference's is Pattern52 [EXT]: 0.5 * raw, raw rows y = 7, 5 .. -7, x ascending in steps of 2 over
+ *               +-3, +-5, +-7, +-7, +-7, +-7, +-5, +-3 (52 points; pnec_amd.PATTERN52, pnec::features::Pattern52()).
+ *   scaling     > 0 (the reference's uncertainty_scaling is 10).
+ *   angle       double [n_points] or NULL: rotation of the tracked transform in radians, |angle| < 1e6.
+ *
+ * Per pattern point i: p = pos + pattern[i].  The point is VALID iff 2 <= p.x < width - 3 and 2 <= p.y < height - 3
+ * (InBounds(p, 2) for floating coordinates; a NaN coordinate is invalid).  With ix = floor(p.x), dx = p.x - ix,
+ * ddx = 1 - dx (the same in y) and B(u, v) = ((ddx ddy I(u,v) + ddx dy I(u,v+1)) + dx ddy I(u+1,v)) + dx dy I(u+1,v+1):
+ *   d_i = B(ix, iy),  gx_i = 0.5 (B(ix+1, iy) - B(ix-1, iy)),  gy_i = 0.5 (B(ix, iy+1) - B(ix, iy-1))
+ * -- twelve distinct pixels, all inside the image by the validity rule.
+ * Per keypoint (pnec_patch.h:101-135 term by term): n = number of valid points, S = sum d_i, G = sum g_i,
+ *   g'_i = n (g_i S - G d_i) / S^2 for a valid point, 0 for an invalid one;  r_i = -pat_y g'x_i + pat_x g'y_i;
+ *   J_i = (g'x_i, g'y_i, r_i);  H = sum J_i' J_i (3x3);  Sigma = (H^-1)[0:2, 0:2] / scaling, and with an angle
+ *   Sigma <- R(angle) Sigma R(angle)', R = [c -s; s c].
+ * H^-1 as pnec_hip_pose_covariance does it: the Cholesky factor of the Jacobi-scaled matrix diag(H)^-1/2 H diag(H)^-1/2.
+ * Order of every sum, fixed by the pattern's order alone: pattern point i belongs to position i mod 16; a position adds
+ * its points in ascending i; the 16 positions are then added pairwise: j with j^1, then with j^2, then with 7 - j inside
+ * each half, then with 15 - j.  No atomics: a keypoint's bits depend on its own image, position, pattern, scaling and
+ * angle only -- not on the call it sits in, nor on `space`.
+ *
+ * Outputs, per keypoint; every pointer may be NULL (not wanted), not all of them.
+ *   out_cov     double [n_points, 3]  Sigma as (xx, xy, yy): what pnec_hip_problem_fill_keypoints takes as cov2 / cov1
+ *   out_hessian double [n_points, 6]  H * scaling, upper triangle (00 01 02 11 12 22)
+ *   out_mean    double [n_points]     S / n
+ *   out_n_valid int32  [n_points]     n
+ *   out_status  int32  [n_points]     pnec_hip_patch_status: 0; PNEC_HIP_PATCH_EMPTY when n = 0 or S is not positive and
+ *               finite; PNEC_HIP_PATCH_SINGULAR on a non-positive pivot (a constant image, a ramp), a non-finite
+ *               inverse or n < 3 (H then has rank below 3, whatever sign rounding gives the last pivot).  In both error
+ *               cases out_cov is NaN and out_hessian holds what the arithmetic gave.
+ * DEVICE space: every pointer (images, offsets, pts, pattern, angle, outputs) is device memory of `device`, nothing
+ * waits, the call is asynchronous on `stream`, and an offsets array that breaks the rules above cannot make the kernel
+ * read outside the images (the image index is clamped).  HOST space: the arrays are staged, offsets are checked, the
+ * call blocks.  n_points = 0 returns at once.
+ * PNEC_HIP_ERR_INVALID_ARGUMENT: NULL images / offsets / pts / pattern, all outputs NULL, n_pattern outside 1..64, an
+ * unknown pixel_type, n_images < 1, width or height < 1, pitch < width, n_points < 0, scaling not positive and finite,
+ * a bad `space`; in HOST space also offsets that break the rules above. */
+#define PNEC_HIP_PATCH_MAX_POINTS 64
+typedef enum pnec_hip_pixel_type {
+  PNEC_HIP_PIXEL_U8 = 0,
+  PNEC_HIP_PIXEL_U16 = 1,
+  PNEC_HIP_PIXEL_F32 = 2
+} pnec_hip_pixel_type;
+typedef enum pnec_hip_patch_status {
+  PNEC_HIP_PATCH_OK = 0,
+  PNEC_HIP_PATCH_EMPTY = 1,
+  PNEC_HIP_PATCH_SINGULAR = 2
+} pnec_hip_patch_status;
+int pnec_hip_patch_covariance(const void *images, int pixel_type, int64_t n_images, int32_t height, int32_t width,
+                              int64_t pitch, const int64_t *offsets, int64_t n_points, const double *pts,
+                              const double *pattern, int32_t n_pattern, double scaling, const double *angle,
+                              double *out_cov, double *out_hessian, double *out_mean, int32_t *out_n_valid,
+                              int32_t *out_status, int space, int device, void *stream);
 
 /* Name and launch geometry the auto-tuner would pick for this problem (for logs / profiles). */
 int pnec_hip_describe_launch(const pnec_hip_problem *p, const pnec_hip_options *opt,

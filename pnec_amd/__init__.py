@@ -4,13 +4,15 @@ Layout:
   csrc/            HIP kernels + the C ABI (include/pnec_hip.h) + host C++ facade + pybind module
   capi.py          ctypes binding of libpnec_hip.so (no fallback: raises if the library is missing)
   batch.py         batches of frame pairs in HBM; numpy (host space) or torch.cuda (device space)
+  patches.py       2x2 keypoint covariances from image patches (the cov input of Batch.fill_keypoints)
   simulation.py    synthetic inputs following the reference simulator's distributions (harness)
   distributed.py   one-process-per-GPU sharding of independent pair batches + one RCCL gather
 """
 from . import capi  # noqa: F401
 from .batch import (Batch, PoseCovariance, RelativeScale, ResidualReport, SolveResult, Triangulation, gate_sigma,  # noqa: F401
                     select_best)
+from .patches import PATTERN52, PatchCovariance, patch_covariance  # noqa: F401
 from .tracks import chain_scales  # noqa: F401
 
-__all__ = ["capi", "Batch", "PoseCovariance", "RelativeScale", "ResidualReport", "SolveResult", "Triangulation", "chain_scales",
-           "gate_sigma", "select_best"]
+__all__ = ["capi", "Batch", "PATTERN52", "PatchCovariance", "PoseCovariance", "RelativeScale", "ResidualReport", "SolveResult",
+           "Triangulation", "chain_scales", "gate_sigma", "patch_covariance", "select_best"]

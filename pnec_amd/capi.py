@@ -67,6 +67,7 @@ SYMBOLS = [
     "pnec_hip_residuals",
     "pnec_hip_triangulate",
     "pnec_hip_relative_scale",
+    "pnec_hip_patch_covariance",
     "pnec_hip_nec_eigensolver",
     "pnec_hip_ransac_eigensolver",
     "pnec_hip_problem_select",
@@ -217,6 +218,8 @@ def lib() -> C.CDLL:
                                      C.c_int, _vp]
     L.pnec_hip_triangulate.argtypes = [_vp, _vp, _vp, C.c_int32, C.c_int32] + [_vp] * 11 + [C.c_int, _vp]
     L.pnec_hip_relative_scale.argtypes = [_vp] * 8 + [C.c_double] + [_vp] * 5 + [C.c_int, _vp]
+    L.pnec_hip_patch_covariance.argtypes = [_vp, C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_int64, _vp, C.c_int64, _vp, _vp,
+                                            C.c_int32, C.c_double] + [_vp] * 6 + [C.c_int, C.c_int, _vp]
     L.pnec_hip_describe_launch.argtypes = [_vp, C.POINTER(Options)] + [C.POINTER(C.c_int32)] * 5
     L.pnec_hip_unscented_transform.argtypes = [C.c_int64, _vp, _vp, _vp, C.c_double, C.c_int, _vp, _vp,
                                                C.c_int, C.c_int, _vp]

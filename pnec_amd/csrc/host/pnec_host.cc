@@ -412,6 +412,44 @@ bool Timing::Save(const std::string &path) const {
 
 }  // namespace common
 
+namespace features {
+
+const std::vector<std::array<double, 2>> &Pattern52() {
+  static const std::vector<std::array<double, 2>> pattern = [] {
+    std::vector<std::array<double, 2>> p;
+    const int half_width[8] = {3, 5, 7, 7, 7, 7, 5, 3};
+    for (int row = 0; row < 8; ++row)
+      for (int x = -half_width[row]; x <= half_width[row]; x += 2) p.push_back({0.5 * x, 0.5 * (7 - 2 * row)});
+    return p;
+  }();
+  return pattern;
+}
+
+std::vector<std::array<double, 3>> PatchCovariances(const void *image, pnec_hip_pixel_type pixel_type, int height,
+                                                    int width, int64_t pitch,
+                                                    const std::vector<std::array<double, 2>> &points, double scaling,
+                                                    const std::vector<double> *angles, std::vector<int> *status,
+                                                    const std::vector<std::array<double, 2>> *pattern) {
+  if (angles && angles->size() != points.size()) throw std::invalid_argument("angles must have one entry per keypoint");
+  const std::vector<std::array<double, 2>> &pat = pattern ? *pattern : Pattern52();
+  const size_t n = points.size();
+  const double nan = std::nan("");
+  std::vector<std::array<double, 3>> cov(n, std::array<double, 3>{nan, nan, nan});
+  std::vector<int32_t> st(n, PNEC_HIP_PATCH_EMPTY);
+  const int64_t offsets[2] = {0, (int64_t)n};
+  static_assert(sizeof(std::array<double, 2>) == 2 * sizeof(double) && sizeof(std::array<double, 3>) == 3 * sizeof(double),
+                "std::array<double, N> is N packed doubles");
+  if (n > 0)
+    Check(pnec_hip_patch_covariance(image, (int)pixel_type, 1, height, width, pitch > 0 ? pitch : width, offsets,
+                                    (int64_t)n, points[0].data(), pat.empty() ? nullptr : pat[0].data(), (int32_t)pat.size(),
+                                    scaling, angles ? angles->data() : nullptr, cov[0].data(), nullptr, nullptr, nullptr,
+                                    st.data(), PNEC_HIP_MEM_HOST, optimization::SolverOptions().device, nullptr));
+  if (status) status->assign(st.begin(), st.end());
+  return cov;
+}
+
+}  // namespace features
+
 // -------------------------------------------------------------------------------- optimization
 namespace optimization {
 

@@ -14,6 +14,7 @@
 // call; thousands of pairs per call is what the device is for.
 #pragma once
 
+#include <array>
 #include <cstdint>
 #include <ostream>
 #include <stdexcept>
@@ -150,6 +151,26 @@ double RelativeScale(const bearingVectors_t &bvs_prev_1, const bearingVectors_t 
                      double *q75 = nullptr, int *n_used = nullptr, std::vector<double> *ratios = nullptr);
 
 }  // namespace common
+
+// Addition (the reference computes these inside its KLT tracker, in float: POpticalFlowPatch::setFromImage,
+// include/features/tracking/pnec_patch.h:78-137, scaled and rotated by KLTPatchOpticalFlow; basalt's image.h /
+// patterns.h are not in its tree [EXT]): the 2x2 image covariance of keypoints from the patches around them --
+// pnec_hip_patch_covariance for one image, in double, include/pnec_hip.h has the definitions.  No tracking happens here.
+namespace features {
+// basalt's Pattern52: 52 offsets (x, y) in pixels, 0.5 * the raw integer pattern, rows from y = 3.5 down to -3.5
+const std::vector<std::array<double, 2>> &Pattern52();
+// One image of height x width pixels (`pitch` elements per row, 0 = width) of pixel_type, keypoints (x = column, y = row).
+// Returns (xx, xy, yy) per keypoint, what KeyPoint::img_covariance_ holds; NaN where status is not PNEC_HIP_PATCH_OK
+// (PNEC_HIP_PATCH_EMPTY: no pattern point inside the image or a patch without intensity; PNEC_HIP_PATCH_SINGULAR: a
+// constant patch or a ramp).  scaling is the reference's uncertainty_scaling; angles (one per keypoint, radians) rotate
+// the covariance as the tracked transform does.
+std::vector<std::array<double, 3>> PatchCovariances(const void *image, pnec_hip_pixel_type pixel_type, int height,
+                                                    int width, int64_t pitch,
+                                                    const std::vector<std::array<double, 2>> &points,
+                                                    double scaling = 10.0, const std::vector<double> *angles = nullptr,
+                                                    std::vector<int> *status = nullptr,
+                                                    const std::vector<std::array<double, 2>> *pattern = nullptr);
+}  // namespace features
 
 namespace optimization {
 

@@ -11,6 +11,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <array>
 #include <vector>
 
 #include "pnec_host.h"
@@ -279,6 +280,36 @@ py::tuple relative_scale(arr bvs_prev1, arr bvs_prev2, arr pose_prev, arr bvs1, 
   return py::make_tuple(scale, q25, q75, n_used, R);
 }
 
+// (cov [N,3] = xx, xy, yy; status [N]) of the keypoints `points` [N,2] (x = column, y = row) of one image
+py::tuple patch_covariance(py::array image, arr points, double scaling) {
+  if (image.ndim() != 2) throw std::invalid_argument("image must be [h,w]");
+  pnec_hip_pixel_type type;
+  if (image.dtype().is(py::dtype::of<uint8_t>())) type = PNEC_HIP_PIXEL_U8;
+  else if (image.dtype().is(py::dtype::of<uint16_t>())) type = PNEC_HIP_PIXEL_U16;
+  else if (image.dtype().is(py::dtype::of<float>())) type = PNEC_HIP_PIXEL_F32;
+  else throw std::invalid_argument("image must be uint8, uint16 or float32");
+  const py::ssize_t es = image.itemsize();
+  if (image.strides(1) != es || image.strides(0) % es != 0 || image.strides(0) < image.shape(1) * es)
+    throw std::invalid_argument("image rows must be contiguous (a row pitch is allowed)");
+  if (points.ndim() != 2 || points.shape(1) != 2) throw std::invalid_argument("points must be [N,2]");
+  const py::ssize_t n = points.shape(0);
+  std::vector<std::array<double, 2>> pts((size_t)n);
+  auto r = points.unchecked<2>();
+  for (py::ssize_t i = 0; i < n; ++i) pts[(size_t)i] = {r(i, 0), r(i, 1)};
+  std::vector<int> status;
+  const auto cov = pnec::features::PatchCovariances(image.data(), type, (int)image.shape(0), (int)image.shape(1),
+                                                    (int64_t)(image.strides(0) / es), pts, scaling, nullptr, &status);
+  py::array_t<double> C({n, (py::ssize_t)3});
+  py::array_t<int32_t> S(n);
+  auto c = C.mutable_unchecked<2>();
+  auto s = S.mutable_unchecked<1>();
+  for (py::ssize_t i = 0; i < n; ++i) {
+    for (int k = 0; k < 3; ++k) c(i, k) = cov[(size_t)i][(size_t)k];
+    s(i) = status[(size_t)i];
+  }
+  return py::make_tuple(C, S);
+}
+
 // PNEC::Solve for ONE frame pair through the overload asked for (pnec.cc:69-75, :77-124, :126-134,
 // :135-208): overload 0 = (bvs1, bvs2, covs, init), 1 = (+ inliers), 2 = (+ timing), 3 = (+ inliers,
 // timing).  Returns (pose 4x4, inliers or None, timing dict or None).
@@ -380,6 +411,10 @@ PYBIND11_MODULE(pypnec, m) {
         "pnec::common::RelativeScale (addition; device): (scale, q25, q75, n_used, ratio [N]) -- the baseline of `pose` in "
         "units of the baseline of `pose_prev` from the tracks `link` ties to the previous pair -- include/pnec_hip.h "
         "pnec_hip_relative_scale");
+  m.def("patch_covariance", &patch_covariance, py::arg("image"), py::arg("points"), py::arg("scaling") = 10.0,
+        "pnec::features::PatchCovariances (addition; device): (cov [N,3] as xx, xy, yy, status [N]) -- the 2x2 image "
+        "covariance of the keypoints `points` [N,2] of one uint8 / uint16 / float32 image from their Pattern52 patches, in "
+        "double; no tracking -- include/pnec_hip.h pnec_hip_patch_covariance");
   m.def("solve", &solve, py::arg("bvs1"), py::arg("bvs2"), py::arg("covs"), py::arg("init_pose"),
         py::arg("overload") = 1, py::arg("use_ransac") = true, py::arg("use_nec") = false,
         py::arg("use_ceres") = true, py::arg("weighted_iterations") = 10, py::arg("regularization") = 1e-13,

@@ -16,6 +16,7 @@
 #include "pnec_device.hpp"
 #include "pnec_front_shared.hpp"
 #include "pnec_internal.hpp"
+#include "pnec_patch_cov.hpp"
 #include "pnec_pose_cov.hpp"
 #include "pnec_residuals.hpp"
 #include "pnec_relative_scale.hpp"
@@ -1279,6 +1280,101 @@ int pnec_hip_relative_scale(pnec_hip_problem *cur, pnec_hip_problem *prev, const
   // n_max of a batch whose sizes still live on the device (select) is the source's: an upper bound, which is all the
   // block size needs (the wavefronts a pair uses follow from its own count)
   PNEC_HIP_TRY(launch_relative_scale(P, cov_waves(cur->n_max), a, stream));
+  return space == PNEC_HIP_MEM_HOST ? stage.finish() : 0;
+}
+
+// the 2x2 image covariance of keypoints from their image patches: pnec_patch_cov.hip.  No batch is involved; a HOST-space
+// call stages through HostStage in buffers of its own, which a handle-less holder owns for the call.
+namespace {
+struct StageHolder {
+  pnec_hip_problem p;
+  ~StageHolder() {
+    if (p.d_stage) (void)dev_free(p.d_stage);
+    if (p.d_stage_i) (void)dev_free(p.d_stage_i);
+  }
+};
+}  // namespace
+
+int pnec_hip_patch_covariance(const void *images, int pixel_type, int64_t n_images, int32_t height, int32_t width,
+                              int64_t pitch, const int64_t *offsets, int64_t n_points, const double *pts,
+                              const double *pattern, int32_t n_pattern, double scaling, const double *angle,
+                              double *out_cov, double *out_hessian, double *out_mean, int32_t *out_n_valid,
+                              int32_t *out_status, int space, int device, void *stream_) {
+  if (!images || !offsets || !pattern || (!pts && n_points > 0))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_covariance: images, offsets, pts or pattern is NULL");
+  if (!out_cov && !out_hessian && !out_mean && !out_n_valid && !out_status)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_covariance: every output is NULL");
+  if (n_pattern < 1 || n_pattern > PNEC_HIP_PATCH_MAX_POINTS)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_covariance: n_pattern must be 1 .. 64");
+  size_t elem = 0;
+  switch (pixel_type) {
+    case PNEC_HIP_PIXEL_U8: elem = 1; break;
+    case PNEC_HIP_PIXEL_U16: elem = 2; break;
+    case PNEC_HIP_PIXEL_F32: elem = 4; break;
+    default: return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_covariance: unknown pixel_type");
+  }
+  if (n_images < 1 || height < 1 || width < 1 || n_points < 0)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_covariance: n_images, height, width must be >= 1, n_points >= 0");
+  if (pitch < width) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_covariance: pitch (in elements) is below width");
+  if (!(scaling > 0.0) || !std::isfinite(scaling))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_covariance: scaling must be positive and finite");
+  if (space != PNEC_HIP_MEM_DEVICE && space != PNEC_HIP_MEM_HOST)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_covariance: bad memory space");
+  // (the pixels of all images, counted in elements: the last row of the last image need not be padded)
+  if (n_images > 0x7fffffffLL || (double)n_images * (double)height * (double)pitch * (double)elem > 9.0e18)
+    return fail(PNEC_HIP_ERR_UNSUPPORTED, "patch_covariance: the images do not fit a 64-bit byte count");
+  if (space == PNEC_HIP_MEM_HOST) {
+    bool ok = offsets[0] == 0 && offsets[n_images] == n_points;
+    for (int64_t f = 0; ok && f < n_images; ++f) ok = offsets[f] <= offsets[f + 1];
+    if (!ok)
+      return fail(PNEC_HIP_ERR_INVALID_ARGUMENT,
+                  "patch_covariance: offsets must be non-decreasing from 0 to n_points");
+  }
+  if (n_points == 0) return 0;
+  DeviceGuard guard(device);
+  if (!guard.ok) return fail(PNEC_HIP_ERR_HIP_RUNTIME, "hipSetDevice failed (no such device?)");
+  hipStream_t stream = (hipStream_t)stream_;
+  StageHolder holder;
+  holder.p.device = device;
+  HostStage stage(&holder.p, stream);
+  PatchCovArgs a;
+  a.w = width;
+  a.h = height;
+  a.pitch = pitch;
+  a.n_images = n_images;
+  a.n_points = n_points;
+  a.n_pattern = n_pattern;
+  a.scaling = scaling;
+  if (space == PNEC_HIP_MEM_DEVICE) {
+    a.images = images;
+    a.offsets = offsets;
+    a.pts = pts;
+    a.pattern = pattern;
+    a.angle = angle;
+    a.out_cov = out_cov;
+    a.out_hessian = out_hessian;
+    a.out_mean = out_mean;
+    a.out_n_valid = out_n_valid;
+    a.out_status = out_status;
+  } else {
+    const int64_t M = n_points;
+    const int64_t image_bytes = (int64_t)elem * ((n_images * (int64_t)height - 1) * pitch + width);
+    // stage: [pixels | offsets F+1 (int64) | pts 2M | pattern 2P | angle M | cov 3M | hessian 6M | mean M], ints
+    // [n_valid M | status M]
+    if (int rc = stage.reserve((image_bytes + 7) / 8 + (n_images + 1) + 13 * M + 2 * n_pattern, 2 * M)) return rc;
+    a.images = stage.up_bytes(images, image_bytes);
+    a.offsets = stage.up(offsets, n_images + 1);
+    a.pts = stage.up(pts, 2 * M);
+    a.pattern = stage.up(pattern, 2 * (int64_t)n_pattern);
+    a.angle = stage.up(angle, M);
+    a.out_cov = stage.out(out_cov, 3 * M);
+    a.out_hessian = stage.out(out_hessian, 6 * M);
+    a.out_mean = stage.out(out_mean, M);
+    a.out_n_valid = stage.out(out_n_valid, M);
+    a.out_status = stage.out(out_status, M);
+    if (int rc = stage.status()) return rc;
+  }
+  PNEC_HIP_TRY(launch_patch_covariance(pixel_type, a, stream));
   return space == PNEC_HIP_MEM_HOST ? stage.finish() : 0;
 }
 

@@ -191,6 +191,12 @@ class HostStage {
     if (d && n > 0 && err_ == hipSuccess) err_ = hipMemcpyAsync(d, host, sizeof(int32_t) * n, hipMemcpyHostToDevice, stream_);
     return d;
   }
+  // n bytes of anything (pixels): they live among the doubles, in whole doubles
+  const void *up_bytes(const void *host, int64_t n) {
+    void *d = host ? static_cast<void *>(take(d_next_, d_left_, (n + 7) / 8)) : nullptr;
+    if (d && n > 0 && err_ == hipSuccess) err_ = hipMemcpyAsync(d, host, (size_t)n, hipMemcpyHostToDevice, stream_);
+    return d;
+  }
   // room for an output of n items that finish() copies to `host`; for a NULL `host`: nullptr, or with `keep` (the
   // kernel writes the array whether or not the caller wants it) room that is not copied back
   double *out(double *host, int64_t n, bool keep = false) {
