@@ -89,10 +89,18 @@ def _covs_for(mode, S2):
     return S2, None
 
 
+# what the device's options and the oracle's do not share: the launch tuning, and the two fields each side
+# spells its own way (flags there, jacobian_mode here)
+NOT_SHARED = {"corr_per_lane", "waves_per_pair", "lds_corr_per_lane", "flags", "jacobian_mode", "reserved"}
+
+
 def _oracle_opts(oracle, hip_opts, jacobian_mode):
+    """the oracle's options with every field the two structs share copied from the device's"""
     o = oracle.default_options(jacobian_mode=jacobian_mode)
-    for name in ("max_num_iterations", "check_convergence", "function_tolerance",
-                 "gradient_tolerance", "parameter_tolerance", "jacobi_scaling"):
+    shared = [name for name, _ in oracle.Options._fields_
+              if name not in NOT_SHARED and any(name == f for f, _ in capi.Options._fields_)]
+    assert len(shared) == 13, shared    # a field added to one struct only is a decision to take here
+    for name in shared:
         setattr(o, name, getattr(hip_opts, name))
     return o
 

@@ -8,6 +8,7 @@ variant (the same algorithm the kernel runs) the bar is 1e-9 rad.
 """
 import math
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -15,6 +16,9 @@ import torch
 
 from pnec_amd import Batch, capi, select_best
 from pnec_amd import simulation as sim
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from test_lm_edges_gpu import _oracle_opts  # noqa: E402  (one helper: every field the two option structs share)
 
 pytestmark = pytest.mark.gpu
 
@@ -39,14 +43,6 @@ def _oracle_batch(oracle, mode, offsets, f1, f2, c2, c1, reg, q0, t0, opts, **kw
     c2_9 = None if c2 is None else oracle.covs_to_colmajor9(c2)
     c1_9 = None if c1 is None else oracle.covs_to_colmajor9(c1)
     return oracle.solve_batch(mode, offsets, f1, f2, c2_9, c1_9, reg, q0, t0, options=opts, **kw)
-
-
-def _oracle_opts(oracle, hip_opts, jacobian_mode):
-    o = oracle.default_options(jacobian_mode=jacobian_mode)
-    for name in ("max_num_iterations", "check_convergence", "function_tolerance",
-                 "gradient_tolerance", "parameter_tolerance", "jacobi_scaling"):
-        setattr(o, name, getattr(hip_opts, name))
-    return o
 
 
 def _quat_to_R(q):
