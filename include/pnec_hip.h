@@ -246,7 +246,10 @@ int pnec_hip_problem_ransac_flags(const pnec_hip_problem *p);
  *   reg                         regularisation (Options::regularization_, 1e-13 in the reference)
  *   out_q [S,4] normalised, out_t [S,3] unit, out_cost [S] (= 1/2 sum r^2 at the result),
  *   out_iterations [S], out_status [S] (pnec_hip_termination); S = n_pairs*n_hyp; any out may be NULL
- *   space: where init and out arrays live (HOST: blocking; DEVICE: async on stream).
+ *   space: where init and out arrays live (HOST: blocking; DEVICE: async on stream).  A HOST-space call runs on
+ *   `stream` too and returns after everything queued on THAT stream before it; made with stream = NULL it is not ordered
+ *   after work on a non-blocking stream.  A caller who filled the batch on a side stream synchronises that stream first
+ *   (or passes it).  The same holds for every call that takes `space`.
  * With n_hyp > 1 the hypotheses of a pair share its payload on chip: pairs of up to 512 correspondences run two
  * hypotheses per wavefront (both LM steps at once), larger ones one block per pair and group of 2 / 4 / 8 hypotheses (the
  * group's LM steps at the same time) -- the same bits as n_hyp separate calls, 1.2x .. 1.6x their rate.  */

@@ -68,6 +68,7 @@ _TRI5 = tuple((a, b) for a in range(5) for b in range(a, 5))  # the ABI's packed
 
 _FULL5 = tuple(min(a, b) * 5 - min(a, b) * (min(a, b) - 1) // 2 + abs(a - b) for a in range(5) for b in range(5))
 _full5_on = {}   # torch device -> _FULL5 as an index tensor there (made once: no upload per call)
+_kinv_on = {}    # (device, bytes of K_inv) -> its column-major image on that device (fill_keypoints: no upload per call)
 
 
 def expand_info(packed):
@@ -397,7 +398,8 @@ class Batch:
         """Fused ingest from keypoints (KeyPoint::Unproject, keypoints.cc:49-62): pixel positions [M,2] of
         both frames + image-plane covariances [M,2,2] (or [M,3] = xx, xy, yy) -> bearings and bearing
         covariances computed on the device straight into the SoA planes.  numpy -> HOST space,
-        torch.cuda -> DEVICE space."""
+        torch.cuda -> DEVICE space, asynchronous on torch's current stream: K_inv [3,3] is then a CUDA tensor, or a host
+        array that is uploaded the first time its value is seen (that one call waits for the stream)."""
         if n_pairs is None:
             n_pairs = self.n_pairs - first_pair
         m = int(self.offsets[first_pair + n_pairs] - self.offsets[first_pair])
@@ -428,8 +430,18 @@ class Batch:
             keep.append(a)
         if on_device:
             import torch
-            Kd = torch.as_tensor(np.asarray(K.cpu() if _is_torch(K) else K, dtype=np.float64).T.copy().reshape(9),
-                                 device=f"cuda:{self.device}")
+            # no host round trip per call (an upload from pageable memory waits for the stream): a CUDA K_inv is
+            # transposed where it is, a host one is uploaded once per value and device
+            if _is_torch(K) and K.is_cuda:
+                Kd = self._dev_tensor(K, "K_inv", (3, 3)).t().contiguous().reshape(9)
+            else:
+                K9 = np.asarray(K.cpu() if _is_torch(K) else K, dtype=np.float64).T.copy().reshape(9)
+                key = (self.device, K9.tobytes())
+                Kd = _kinv_on.get(key)
+                if Kd is None:
+                    if len(_kinv_on) >= 64:
+                        _kinv_on.clear()
+                    Kd = _kinv_on[key] = torch.as_tensor(K9, device=f"cuda:{self.device}")
             kp, stream, space = Kd.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream, capi.MEM_DEVICE
         else:
             Kd = np.ascontiguousarray(np.asarray(K, dtype=np.float64).T.reshape(9))
