@@ -21,9 +21,16 @@
 //   * everything that is one value per solve -- accept/reject, trust region, the 5x5 solve, the
 //     manifold update, the next pose's uniforms (lm_advance) -- runs in one quad on LDS-resident
 //     state (~80 doubles per wavefront): a ~500-instruction latency chain that the SIMD's other
-//     wavefront hides under its pass.  (Measured dead ends, DESIGN.md section 6: narrowing EXEC
+//     wavefront hides under its pass.  (Measured dead ends, DESIGN.md section 4: narrowing EXEC
 //     does not shorten the issue time of that chain, and sharing one chain between the
 //     wavefronts of a workgroup trades its issue slots for barrier stalls -- no gain.)
+//   * since EXEC does not matter, the one-wavefront (8, 1, 3) kernel runs that chain on FOUR quads: quad 0 makes the step, quads
+//     1 .. 3 the steps that would follow if it -- and then the next, and the next -- were rejected (same H, g, x and
+//     diagonal, the trust region shrunk by the rule's powers of two), parked in 3 x 24 doubles of LDS per wavefront; a
+//     rejected step is then SERVED from there instead of recomputed, bit for bit the same (lm_advance, NFB; the
+//     (8, 1, 3) geometry only: see where the kernel sets NFB);
+//   * the full pass of TARGET and NEC evaluates a correspondence with eval_corr_solve, eval_corr without six adds of
+//     a literal zero (same bits: see there).
 #pragma once
 
 #include <type_traits>
@@ -133,7 +140,14 @@ enum : int { kIIter = 0, kIFirst, kIReuseDiag, kINumInvalid, kIStepOk,
               kILast,  // the published candidate is evaluated at the iteration cap: its Jacobian can never be used
               kIPark,  // which table of sums (0 / 1) belongs to the current point
               kITerm,  // several wavefronts per solve: the termination code the advancing wavefront publishes
+              kISpec = kITerm,  // one resident wavefront per solve (where kITerm has no use): how many of the precomputed
+                                // fallback candidates have been served since they were computed (kNumFallbacks: none left)
               kINumI = 8 };
+// Fallback candidates of the one-wavefront resident kernels (lm_advance, "rejected steps from idle quads"): per wavefront
+// kNumFallbacks slots of kSpecSlot doubles, laid out like slab[kModel .. kPhiC] followed by the pass uniforms
+constexpr int kNumFallbacks = 3;
+enum : int { kSpModel = 0, kSpQc = 1, kSpThetaC = 5, kSpPhiC = 6, kSpValid = 7, kSpUnif = 8 /* 15 */, kSpecSlot = 24 };
+static_assert(kQc - kModel == kSpQc && kThetaC - kModel == kSpThetaC && kPhiC - kModel == kSpPhiC, "slot layout = slab layout");
 
 // Which (family, geometry) pairs are built: the payload must fit the 160 KB LDS and the
 // register budget of its occupancy target (<= 72 doubles of payload per lane at two wavefronts
@@ -141,7 +155,8 @@ enum : int { kIIter = 0, kIFirst, kIReuseDiag, kINumInvalid, kIStepOk,
 __host__ __device__ constexpr bool geometry_ok(int mode, int cpl, int wpp, int ldsk) {
   const int nc = num_components(mode);
   if (cpl == 12) return wpp == 1 && ldsk == 3 && nc <= 12;  // (8, 1, 3) + tail: the 6- and 12-plane payloads
-  const long lds = (long)wpp * (ldsk * nc * kWave * 8 + (kSlab + kUnif) * 8 + kINumI * 4) + (wpp > 1 ? 2L * wpp * kSumSlots * 8 : 0);
+  const long lds = (long)wpp * (ldsk * nc * kWave * 8 + (kSlab + kUnif) * 8 + kINumI * 4) + (wpp > 1 ? 2L * wpp * kSumSlots * 8 : 0) +
+                   (wpp == 1 ? kNumFallbacks * kSpecSlot * 8 : 0);
   if (lds > 160 * 1024) return false;
   if (cpl == 8 && ldsk == 0) return nc <= 18;
   return nc * (cpl - ldsk) <= 72;
@@ -296,6 +311,70 @@ __device__ __forceinline__ void load_resident_aos(const double *__restrict__ b1,
   }
 }
 
+// The solve kernels' own per-correspondence evaluation of the full pass.  HOST and SYM: eval_corr.  TARGET and NEC:
+// eval_corr's body without its six `+ ex/ey/ez`, `+ hx/hy/hz`, which for these families are the literal 0.0 -- the
+// compiler may not fold x + 0.0 (it turns -0.0 into +0.0) and emitted six FP64 adds per correspondence, 48 of the full
+// pass's 742 VALU instructions.  (It lives here, not in pnec_device.hpp: bench.py's FRONT_FLOP_MODEL_STAMP hashes that
+// file, and eval_corr's other users keep it as it is.)
+// Why no sum changes a bit: the adds only turned a -0.0 entry of J into +0.0.  J enters nothing but accumulate()'s
+// fma(J[a], r, acc) and fma(J[a], J[b], acc); every accumulator starts at +0.0 and is only ever added to, and
+// (+0.0) + (a product that is a zero of either sign) is +0.0 in round-to-nearest, so no accumulator ever holds -0.0:
+// a product that is +-0 leaves the accumulator's bits as they are whichever sign it has, and a product that is not
+// zero does not depend on the sign of a zero factor at all -- it has none.
+// Without the trailing add the compiler would be free to contract the other product of each cross-product component
+// into the FMA, so the six components are written out in the operand order of the code this replaces:
+// a * b - c * d  ->  p = c * d (rounded); fma(a, b, -p).
+template <int MODE>
+__device__ __forceinline__ void eval_corr_solve(const double (&d)[num_components(MODE)], const PassUniforms &U,
+                                                double reg, double &r, double (&J)[5]) {
+  if constexpr (MODE != PNEC_HIP_MODE_NEC && MODE != PNEC_HIP_MODE_TARGET) {
+    eval_corr<MODE>(d, U, reg, r, J);
+  } else {
+    const double f1x = d[0], f1y = d[1], f1z = d[2];
+    const double f2x = d[3], f2y = d[4], f2z = d[5];
+    const double *R = U.R;
+    // m = t x f1
+    const double mx = U.t[1] * f1z - U.t[2] * f1y;
+    const double my = U.t[2] * f1x - U.t[0] * f1z;
+    const double mz = U.t[0] * f1y - U.t[1] * f1x;
+    // g = R' m
+    const double gx = R[0] * mx + R[3] * my + R[6] * mz;
+    const double gy = R[1] * mx + R[4] * my + R[7] * mz;
+    const double gz = R[2] * mx + R[5] * my + R[8] * mz;
+    const double n = f2x * gx + f2y * gy + f2z * gz;
+    double wx, wy, wz;  // dr/dg
+    if constexpr (MODE == PNEC_HIP_MODE_NEC) {
+      r = n;
+      wx = f2x; wy = f2y; wz = f2z;
+    } else {
+      const double sgx = d[6] * gx + d[7] * gy + d[8] * gz;
+      const double sgy = d[7] * gx + d[9] * gy + d[10] * gz;
+      const double sgz = d[8] * gx + d[10] * gy + d[11] * gz;
+      const double den = gx * sgx + gy * sgy + gz * sgz + reg;
+      const double y = fast_rsqrt(fmax(den, kTinyDen));
+      r = n * y;
+      const double c = r * y;  // n / den
+      wx = y * (f2x - c * sgx);
+      wy = y * (f2y - c * sgy);
+      wz = y * (f2z - c * sgz);
+    }
+    // u = R w
+    const double ux = R[0] * wx + R[1] * wy + R[2] * wz;
+    const double uy = R[3] * wx + R[4] * wy + R[5] * wz;
+    const double uz = R[6] * wx + R[7] * wy + R[8] * wz;
+    // J_omega = u x m
+    J[2] = __builtin_fma(uy, mz, -(uz * my));
+    J[3] = __builtin_fma(uz, mx, -(ux * mz));
+    J[4] = __builtin_fma(ux, my, -(uy * mx));
+    // J_t = f1 x u, projected on the (theta, phi) chart
+    const double jx = __builtin_fma(f1y, uz, -(f1z * uy));
+    const double jy = __builtin_fma(f1z, ux, -(f1x * uz));
+    const double jz = __builtin_fma(f1x, uy, -(f1y * ux));
+    J[0] = U.bth[0] * jx + U.bth[1] * jy + U.bth[2] * jz;
+    J[1] = U.bph[0] * jx + U.bph[1] * jy;
+  }
+}
+
 // One fused pass of a wavefront over its resident correspondences: acc = this lane's partial
 // sums of r^2, J'r and J'J at the pose in U.
 // nslots = how many of the wavefront's slots hold at least one correspondence (wave-uniform; slot k
@@ -314,7 +393,7 @@ __device__ __forceinline__ void pass_resident(const double (&d)[REGK][num_compon
   auto eval_slot = [&](auto kc) {
     constexpr int k = decltype(kc)::value;
     double r, J[5];
-    eval_corr<MODE>(d[k], U, reg, r, J);
+    eval_corr_solve<MODE>(d[k], U, reg, r, J);
     accumulate(r, J, acc);
   };
   eval_slot(std::integral_constant<int, 0>{});
@@ -338,7 +417,7 @@ __device__ __forceinline__ void pass_resident(const double (&d)[REGK][num_compon
 #pragma unroll
     for (int c = 0; c < NC; ++c) e[c] = lds[(k * NC + c) * kWave + lane];
     double r, J[5];
-    eval_corr<MODE>(e, U, reg, r, J);
+    eval_corr_solve<MODE>(e, U, reg, r, J);
     accumulate(r, J, acc);
   }
 }
@@ -448,9 +527,40 @@ __device__ __forceinline__ void write_result(const SolveArgs &a, int64_t s, cons
 // register-resident kernels run with COST_FIRST; the streaming fallback (whose passes are always full) without.
 // Always speculating measured 33.7-34.5 against 36.6-36.75 M solves/s on one box (NOTES/rounds-1-4.md), and running
 // this step across the lanes of a row instead of one quad measured 2 % slower (NOTES/rounds-1-4.md, lane-parallel LM step).
-template <bool COST_FIRST>
+//
+// NFB > 0 (the one-wavefront resident (8, 1, 3) kernel: NFB = kNumFallbacks = 3): REJECTED STEPS FROM IDLE QUADS.  After a rejected
+// step the next candidate solves (H + D'/r) p = -g with the same H, g, x and D' (reuse_diagonal) and only another
+// radius, and the radii of a chain of rejections are known in advance: r *= dec, dec *= 2, k times.  On the
+// benchmark's batch 42 % of the steps are rejected, in chains (83 % of the steps after a rejected one); each used to pay
+// the whole chain below (26 LDS loads, the 5x5 Cholesky, two triangular solves, the manifold update, the sine /
+// cosine, the uniforms) on 4 active lanes while the other quads idled through the same instructions.  So the caller
+// runs this function on the lanes of FOUR quads (lane < 16).  All do the identical work up to the step; from
+// dr = diag * inv_radius on, quad k = 1 .. 3 uses the inverse radius the k-th consecutive rejection would produce and
+// leaves its candidate, model change and pass uniforms in slot k - 1 of `spec`, with a flag: valid when its step is
+// valid, its inverse radius is within inv_min_radius and quad 0 published its candidate at the first attempt.  Quad 0
+// publishes what it always did.  The next call, when its verdict is a rejection, the next slot is valid and the cap
+// is not reached, SERVES that slot: a handful of loads and stores instead of the chain.
+//   Bit for bit the slow path's result: the served candidate was made by the same instructions (the very same: the
+// quads share the instruction stream) on the same H, g, x (the current point's table and slab[kQ ..], which a rejection
+// does not touch) and the same diag (slab[kDiag] is what quad 0 stored or re-read), with the same inverse radius:
+// the slow path's inv_radius * dec, dec * 2 repeated is what quad k applies, and products of powers of two are exact
+// anyway.  A slot is only served while the state it was computed from is the state: every call that publishes
+// recomputes all slots and zeroes ist[kISpec]; a call that neither publishes nor serves either ends the solve or
+// (accepted on its cost alone) is followed by the accepting call, which publishes.
+//   What a served step must leave exactly as the slow path does: slab[kInvRadius], slab[kDec], slab[kModel],
+// slab[kQc ..], slab[kThetaC], slab[kPhiC], unif[0 .. 14]; ist[kIIter] + 1, ist[kIStepOk] = 0, ist[kINumInvalid] = 0,
+// ist[kIReuseDiag] = 1, ist[kIFirst] = 0, ist[kILast] by the rule below; ist[kIPark], the current point, its cost, its
+// table and slab[kDiag] untouched.  Everything else (an invalid step, the minimum radius, an exhausted or invalid
+// slot, an accepted step, which needs the new H) takes the slow path, which refills the slots.
+// NFB = 0 (group, pair-hypothesis, multi-wavefront and streaming callers): the function as it always was, on one quad.
+template <bool COST_FIRST, int NFB = 0>
 __device__ __forceinline__ int lm_advance(double *slab, int *ist, double *unif, const pnec_hip_options &o,
-                                          double inv_max_radius, double inv_min_radius) {
+                                          double inv_max_radius, double inv_min_radius,
+                                          [[maybe_unused]] double *spec = nullptr /* [NFB][kSpecSlot] */) {
+  static_assert(NFB == 0 || NFB == kNumFallbacks, "one quad per fallback: lanes 4 .. 15");
+  [[maybe_unused]] const int quad = NFB > 0 ? (int)((threadIdx.x >> 2) & 3) : 0;  // 0: the primary step
+  [[maybe_unused]] int served = 0;
+  if constexpr (NFB > 0) served = ist[kISpec];
   int iteration = ist[kIIter], reuse_diagonal = ist[kIReuseDiag];
   int num_invalid = ist[kINumInvalid], step_ok = ist[kIStepOk];
   const int first = ist[kIFirst];
@@ -533,6 +643,31 @@ __device__ __forceinline__ int lm_advance(double *slab, int *ist, double *unif, 
     ist[kILast] = 0;
     return -1;
   }
+  if constexpr (NFB > 0) {
+    if (term < 0 && !last && !accept && served < NFB && iteration < o.max_num_iterations) {
+      const double *slot = spec + served * kSpecSlot;
+      if (slot[kSpValid] != 0.0) {
+        // serve the precomputed candidate of this rejection (see the head comment for what must be left as the slow path leaves it)
+        inv_radius = inv_radius * dec;
+        dec = 2.0 * dec;
+        ++iteration;
+#pragma unroll
+        for (int k = 0; k < kSpValid; ++k) slab[kModel + k] = slot[k];  // model change, candidate q, theta, phi
+#pragma unroll
+        for (int i = 0; i < 15; ++i) unif[i] = slot[kSpUnif + i];
+        slab[kInvRadius] = inv_radius;
+        slab[kDec] = dec;
+        ist[kILast] = iteration >= o.max_num_iterations ? 1 : (COST_FIRST ? 2 : 0);
+        ist[kISpec] = served + 1;
+        ist[kIIter] = iteration;
+        ist[kIFirst] = 0;
+        ist[kIReuseDiag] = 1;
+        ist[kINumInvalid] = 0;
+        ist[kIStepOk] = 0;
+        return -1;
+      }
+    }
+  }
   if (term < 0 && last) {
     // at the iteration cap the solve ends here whatever the verdict on the step (Ceres checks
     // max_num_iterations before anything that would read the new Jacobian)
@@ -601,6 +736,9 @@ __device__ __forceinline__ int lm_advance(double *slab, int *ist, double *unif, 
     }
 
     // ---- FinalizeIterationAndCheckIfMinimizerCanContinue + the next trust-region step
+    // NFB > 0: all four quads arrive here together and stay together up to the ballot of the first attempt -- every
+    // branch up to there depends on shared LDS state and the options only.  Nothing that depends on `quad` may be added
+    // before that ballot.  A retry (retry == true) is quad 0's alone: quads 1 .. 3 have left the loop by then.
     for (bool retry = false;; retry = true) {
       if (iteration >= o.max_num_iterations) { term = PNEC_HIP_TERM_MAX_ITERATIONS; break; }
       if (retry) {
@@ -629,10 +767,21 @@ __device__ __forceinline__ int lm_advance(double *slab, int *ist, double *unif, 
           slab[kDiag + i] = diag[i];
         }
       }
+      // the inverse radius this quad solves with: quad k's is the one the k-th consecutive rejection of the step
+      // quad 0 is computing would produce (quad 0: inv_radius itself, untouched)
+      double ir = inv_radius;
+      if constexpr (NFB > 0) {
+        double fd = dec;
+#pragma unroll
+        for (int k = 0; k < NFB; ++k) {
+          ir = k < quad ? ir * fd : ir;
+          fd = 2.0 * fd;
+        }
+      }
       double dr[5], y[5], step[5];
 #pragma unroll
       for (int i = 0; i < 5; ++i) {
-        dr[i] = diag[i] * inv_radius;
+        dr[i] = diag[i] * ir;
         H[tri(i, i)] += dr[i];
       }
       bool valid = chol_solve5(H, g, y);
@@ -647,7 +796,17 @@ __device__ __forceinline__ int lm_advance(double *slab, int *ist, double *unif, 
       }
       const double model_change = 0.5 * (sd - sg);
       valid = valid && (model_change > 0.0);
-      if (!valid) {
+      if constexpr (NFB > 0) {
+        // (all four quads are here at the first attempt: what precedes it is identical in all of them)
+        const bool primary_ok = (__builtin_amdgcn_ballot_w64(valid) & 1ull) != 0ull;
+        if (quad > 0) {
+          // a fallback never retries: it is there, or it is not
+          const bool ok = valid && primary_ok && !(ir > inv_min_radius);
+          spec[(quad - 1) * kSpecSlot + kSpValid] = ok ? 1.0 : 0.0;
+          if (!ok) break;
+        }
+      }
+      if ((NFB == 0 || quad == 0) && !valid) {
         if (++num_invalid >= o.max_num_consecutive_invalid_steps) { term = PNEC_HIP_TERM_INVALID_STEPS; break; }
         // [EXT, recalled] TrustRegionMinimizer::HandleInvalidStep -> LevenbergMarquardtStrategy::StepIsInvalid():
         // radius *= 0.5, reuse_diagonal = true -- NOT the rejected-step rule: decrease_factor stays as it is
@@ -680,19 +839,33 @@ __device__ __forceinline__ int lm_advance(double *slab, int *ist, double *unif, 
       qc[1] = aw * x[1] - ax * x[2] + ay * x[3] + az * x[0];
       qc[2] = aw * x[2] + ax * x[1] - ay * x[0] + az * x[3];
       qc[3] = aw * x[3] - ax * x[0] - ay * x[1] - az * x[2];
-      pose_uniforms_sc(st, ct, sp, cp, qc, unif);
+      // quad 0 publishes; quad k > 0 leaves the same in its slot (kSp* = the slab's layout from kModel on)
+      double *cand_out = slab + kModel, *unif_out = unif;
+      if constexpr (NFB > 0) {
+        if (quad > 0) {
+          cand_out = spec + (quad - 1) * kSpecSlot;
+          unif_out = cand_out + kSpUnif;
+        }
+      }
+      pose_uniforms_sc(st, ct, sp, cp, qc, unif_out);
 #pragma unroll
-      for (int k = 0; k < 4; ++k) slab[kQc + k] = qc[k];
-      slab[kThetaC] = thc;
-      slab[kPhiC] = phc;
-      slab[kModel] = model_change;
+      for (int k = 0; k < 4; ++k) cand_out[kSpQc + k] = qc[k];
+      cand_out[kSpThetaC] = thc;
+      cand_out[kSpPhiC] = phc;
+      cand_out[kSpModel] = model_change;
       // the next pass: cost-only at the cap; cost-only too when the step just decided was rejected, or when the model
       // promises less than the cost can resolve (a decrease below ~4e-15 of the cost is inside the rounding of a sum of
       // 512 squares: on the benchmark's batch 65 % of such steps end rejected even right after an accepted one, and
       // every step that promises more than 1e-14 is accepted -- histogram from the CPU checker)
       const double cost_now = accept ? cost_c : cost;
-      ist[kILast] = iteration >= o.max_num_iterations ? 1 : ((COST_FIRST && (!accept || model_change <= 4.0e-15 * cost_now)) ? 2 : 0);
+      if (NFB == 0 || quad == 0) {
+        ist[kILast] = iteration >= o.max_num_iterations ? 1 : ((COST_FIRST && (!accept || model_change <= 4.0e-15 * cost_now)) ? 2 : 0);
+        if constexpr (NFB > 0) ist[kISpec] = 0;  // the slots are those of this step
+      }
       break;
+    }
+    if constexpr (NFB > 0) {
+      if (quad > 0) return -1;  // the solve's state is quad 0's to store: it may have retried
     }
     slab[kInvRadius] = inv_radius;
     slab[kDec] = dec;
@@ -813,6 +986,13 @@ __global__ __launch_bounds__(kWave *WPP, (CPL == 8 && LDSK == 0) ? 1 : 2) void l
   __shared__ double slab_all[WPP][kSlab];
   __shared__ double unif_all[WPP][kUnif];
   __shared__ int ist_all[WPP][kINumI];
+  // (8, 1, 3), one resident wavefront per 512-correspondence solve: rejected steps are served from candidates its idle
+  // quads computed (lm_advance).  The geometry it was measured on, and only that one (NOTES/lm-step-speculation.md):
+  // the (12, 1, 3) tail form has a full register file (256 VGPRs; the few values the fallbacks keep live across the
+  // step put it into scratch), (8, 1, 0) lives on AGPR parking, and on the small rungs (1..4, 1, 0) the fallbacks cost
+  // registers ((2, 1, 0): three -> two wavefronts per SIMD) for a gain nobody has measured.
+  constexpr int NFB = (WPP == 1 && RESIDENT && CPL == 8 && LDSK == 3) ? kNumFallbacks : 0;
+  [[maybe_unused]] __shared__ double spec_all[NFB > 0 ? WPP : 1][NFB > 0 ? NFB * kSpecSlot : 1];
   [[maybe_unused]] __shared__ double xw[2][WPP > 1 ? WPP : 1][kSumSlots];
   [[maybe_unused]] __shared__ double nunif[RESIDENT ? 1 : kNumPoses][12];   // numeric Jacobian: R | t of the perturbed poses
   [[maybe_unused]] __shared__ double ninv2h[8];
@@ -888,6 +1068,7 @@ __global__ __launch_bounds__(kWave *WPP, (CPL == 8 && LDSK == 0) ? 1 : 2) void l
     ist[kIStepOk] = 1;
     ist[kILast] = o.max_num_iterations <= 0 ? 1 : 0;
     ist[kIPark] = 0;
+    if constexpr (WPP == 1) ist[kISpec] = kNumFallbacks;  // no fallback candidate yet (the slot is kITerm when WPP > 1)
   }
   const double inv_max_radius = a.inv_max_radius, inv_min_radius = a.inv_min_radius;  // kernel arguments: scalar
   // the LDS slots arrive by DMA (vmcnt-tracked): they must have landed before the first pass reads them
@@ -981,7 +1162,7 @@ __global__ __launch_bounds__(kWave *WPP, (CPL == 8 && LDSK == 0) ? 1 : 2) void l
             for (int c = 0; c < NC; ++c) e[c] = base[(int64_t)c * stride + idx];
             double r, J[5];
             if (numeric) eval_corr_numeric<MODE>(e, U, nunif, ninv2h, slab + kQc, reg, r, J);
-            else eval_corr<MODE>(e, U, reg, r, J);
+            else eval_corr_solve<MODE>(e, U, reg, r, J);
             accumulate(r, J, acc);
           }
         }
@@ -1011,7 +1192,7 @@ __global__ __launch_bounds__(kWave *WPP, (CPL == 8 && LDSK == 0) ? 1 : 2) void l
               double e[NC];
               load_planes_saddr<NC, (int)imm>(e, tb, plane_bytes, voff, in);
               double r, J[5];
-              eval_corr<MODE>(e, U, reg, r, J);
+              eval_corr_solve<MODE>(e, U, reg, r, J);
               accumulate(r, J, acc);
             };
             // (one correspondence in flight at a time: the scheduler must not hoist the later slots' loads -- there
@@ -1077,7 +1258,9 @@ __global__ __launch_bounds__(kWave *WPP, (CPL == 8 && LDSK == 0) ? 1 : 2) void l
     // other wavefront on this SIMD, which has independent work to fill the gaps (+1.2 %)
     if constexpr (WPP == 1) {
       __builtin_amdgcn_s_setprio(3);
-      if (lane < 4) t = lm_advance<RESIDENT>(slab, ist, unif, o, inv_max_radius, inv_min_radius);  // one quad, identical work (see the sincos exchange)
+      // one quad, identical work in its lanes (see the sincos exchange); with fallbacks, four quads: the step and the
+      // three that would follow its rejection
+      if (lane < 4 * (1 + NFB)) t = lm_advance<RESIDENT, NFB>(slab, ist, unif, o, inv_max_radius, inv_min_radius, spec_all[NFB > 0 ? wave : 0]);
       term = to_sgpr(t);
       __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
