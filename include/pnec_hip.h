@@ -31,6 +31,9 @@
  *   POpticalFlowPatch::setFromImage (Cov) + KLTPatchOpticalFlow's     pnec_hip_patch_covariance
  *    scaling and rotation  include/features/tracking/pnec_patch.h:78-137,
  *    klt_patch_optical_flow.h:244-252  (the covariance only: no tracking; double, not the reference's float)
+ *   KLTPatchOpticalFlow::trackPoints / trackPoint / trackPointAtLevel  pnec_hip_patch_track,
+ *    klt_patch_optical_flow.h:195-342 + POpticalFlowPatch::residual     pnec_hip_image_pyramid_level
+ *    pnec_patch.h:139-170  (the iteration and the pyramid: no detection, no ids; double, not the reference's float)
  *   PNEC::Eigensolver (no RANSAC) / WeightedEigensolver  pnec.cc:231-348   pnec_hip_nec_eigensolver /
  *                                                               pnec_hip_weighted_eigensolver
  *
@@ -702,7 +705,8 @@ int pnec_hip_unscented_transform(int64_t n, const double *mu, const double *covs
  * layout.  It is the quantity POpticalFlowPatch::setFromImage keeps as `Cov` (include/features/tracking/pnec_patch.h:
  * 78-137: the top-left 2x2 block of the inverse of the patch's SE(2) Gauss-Newton Hessian) after KLTPatchOpticalFlow has
  * divided it by uncertainty_scaling and rotated it by the tracked transform (klt_patch_optical_flow.h:244-252,375-382).
- * This is NOT tracking: no KLT iteration, no pyramid, no detection; positions come from the caller's tracker.  Level 0
+ * This is NOT tracking: no KLT iteration, no pyramid, no detection; positions come from the caller's tracker, or from
+ * pnec_hip_patch_track below, which is.  Level 0
  * only (the reference's min_level): for another level pass the downsampled image and the scaled positions.
  * ALL ARITHMETIC IS DOUBLE.  The reference computes in float; its float bits are not reproduced and not claimed.
  * [EXT] basalt's image.h / patterns.h are not in the reference tree: interpGrad, InBounds and Pattern52 below are
@@ -768,6 +772,108 @@ int pnec_hip_patch_covariance(const void *images, int pixel_type, int64_t n_imag
                               const double *pattern, int32_t n_pattern, double scaling, const double *angle,
                               double *out_cov, double *out_hessian, double *out_mean, int32_t *out_n_valid,
                               int32_t *out_status, int space, int device, void *stream);
+
+/* Patch tracking: the pyramidal SE(2) KLT iteration of KLTPatchOpticalFlow with its forward-backward check, and the
+ * halving step of the image pyramid it runs on (added within ABI 8: pure additions, PNEC_HIP_ABI_VERSION is unchanged).
+ * This is the producer of pnec_hip_patch_covariance's positions and of its `angle`: trackPoints / trackPoint /
+ * trackPointAtLevel (include/features/tracking/klt_patch_optical_flow.h:195-342) and POpticalFlowPatch::residual
+ * (pnec_patch.h:139-170) on top of setFromImage as restated above.  FAST detection, the grid, keypoint ids, the view
+ * graph and stereo filtering are NOT here.  ALL ARITHMETIC IS DOUBLE; the reference's float bits are not reproduced and
+ * not claimed.  [EXT] basalt's image.h (interp, InBounds), image_pyr.h (the pyramid) and Sophus (SE2::exp) are not in the
+ * reference tree: they are restated from the published code, and what follows is this library's own definition.
+ *
+ * --- pnec_hip_image_pyramid_level: one halving step.
+ * in: n_images images of height x width pixels in pnec_hip_patch_covariance's layout (pitch_in elements per row); out:
+ * n_images images of (height / 2) x (width / 2) pixels (floor), pitch_out elements per row, image f at element
+ * f * (height / 2) * pitch_out.  height, width >= 4.  With k = [1 4 6 4 1] and r(i, n) the reflection about the border
+ * pixels that does not repeat them (-1 -> 1, -2 -> 2, n -> n - 2, n + 1 -> n - 3):
+ *   out(x, y) = sum_j k_j ( sum_i k_i I(r(2x + i - 2, width), r(2y + j - 2, height)) ) / 256,   i, j = 0 .. 4,
+ * the inner sum first, both sums in ascending index.  U8 and U16 in integer arithmetic, (sum + 128) >> 8; F32 sums in
+ * double (every product is exact, so a fused multiply-add gives the same bits), divides by 256 and rounds once to float.
+ * DEVICE space: asynchronous on `stream`; HOST space: staged, the call blocks.
+ * PNEC_HIP_ERR_INVALID_ARGUMENT: NULL in / out, an unknown pixel_type, n_images < 1, height or width < 4, a pitch below
+ * its width, a bad `space`.
+ *
+ * --- pnec_hip_patch_track.
+ * Input.
+ *   tmpl, prev, next   three pyramids: where the patches are built, and the two images of the track (forward in `next`,
+ *               backward in `prev`).  Each is a HOST array of n_levels pointers, 1 <= n_levels <=
+ *               PNEC_HIP_TRACK_MAX_LEVELS (8), with a HOST array of n_levels pitches in elements; the buffers the
+ *               pointers name live in `space`.  Level l holds n_images images of (height >> l) x (width >> l) pixels in
+ *               pnec_hip_patch_covariance's layout; the smallest level must still be 4 pixels in each direction.  prev
+ *               (and prev_pitch) may be NULL, meaning tmpl.
+ *   offsets     as in pnec_hip_patch_covariance.
+ *   tmpl_pts    double [n_points, 2]: where the patch is built, in level-0 pixels; level l uses tmpl_pts / 2^l
+ *               (klt_patch_optical_flow.h:365-368).
+ *   init_pts, init_angle   double [n_points, 2] / [n_points]: the transform in `prev` (translation in level-0 pixels,
+ *               rotation in radians, |angle| < 1e6); NULL means tmpl_pts / 0.
+ *   shift_x, shift_y   the reference's `offset`, added to the start of the forward track.
+ *   pattern, n_pattern, scaling   as in pnec_hip_patch_covariance.
+ *   max_iterations   1 .. 255 per level (the reference's configurations use 40, with 4 + 1 levels).
+ *   max_recovered_dist2   >= 0, in square pixels (the reference's 0.04).
+ *   flags       PNEC_HIP_TRACK_NO_BACKWARD: the forward track alone.
+ *
+ * The template of a keypoint at level l is pnec_hip_patch_covariance's patch of tmpl's level l at q = tmpl_pts / 2^l,
+ * sums and order as stated there: validity t_i, d_i, n1, S1, g'_i, J_i, H.  In addition data_i = (n1 d_i) / S1 and
+ * K_i = H^-1 J_i' with the FULL 3x3 inverse from the same Cholesky factor of the Jacobi-scaled H; K_i = 0 for a point
+ * that is not valid.  A template that pnec_hip_patch_covariance would call EMPTY or SINGULAR (or whose inverse is not
+ * finite in all entries) is BAD.
+ * One iteration at level l (size w_l x h_l) from the transform (t, theta), t in that level's pixels:
+ *   p_i = (c pat_x - s pat_y + t_x, s pat_x + c pat_y + t_y), (c, s) = (cos, sin) theta; p_i is valid by the rule above
+ *   v_i = B(floor p_i) as above (four pixels) for a valid point, 0 otherwise;  n2 = number valid;  S2 = sum v_i
+ *   r_i = (n2 v_i) / S2 - data_i where t_i and p_i is valid, 0 otherwise;  m = the number of such points
+ *   the track is LOST, the transform unchanged, if m <= n_pattern / 2 (integer division) or S2 is not positive and finite
+ *   inc = -sum_i K_i r_i;   d = inc_2;   a = sin d / d, b = (1 - cos d) / d, for |d| < 1e-10 a = 1 - d^2 / 6, b = d / 2
+ *   u = (a inc_0 - b inc_1, b inc_0 + a inc_1);   t += (c u_x - s u_y, s u_x + c u_y);   theta += d       [T <- T exp(inc)]
+ *   the track is LOST, the transform updated, if not (2 <= t_x < w_l - 3 and 2 <= t_y < h_l - 3) or |d| or |theta| has
+ *   reached 1e6 (the domain of the library's sine and cosine; no reference track comes near it).
+ * Every sum over the pattern runs in pnec_hip_patch_covariance's order.
+ * One direction: for l = n_levels - 1 .. 0: if the template of level l is BAD, stop with BAD_TEMPLATE at level l;
+ * t /= 2^l; max_iterations iterations (there is no convergence test: the reference has none); t *= 2^l -- also after a
+ * loss at that level, which ends the direction.
+ * Per keypoint: forward from (init_pts + shift, init_angle) in `next`; its result is the OUTPUT transform.  Unless
+ * NO_BACKWARD: backward from (output - shift, output angle) in `prev` with the same templates, then
+ * dist2 = (init_x - rec_x)^2 + (init_y - rec_y)^2 and the track is RECOVERED_TOO_FAR unless dist2 < max_recovered_dist2
+ * (strict, klt_patch_optical_flow.h:238-242).  The first event in this order decides the status.
+ *
+ * Outputs, per keypoint; every pointer may be NULL (not wanted), not all of them.
+ *   out_pts     double [n_points, 2]  the output transform's translation: where the forward track stood last, also when
+ *   out_angle   double [n_points]     lost (a track lost backward keeps its forward result) -- and its rotation
+ *   out_cov     double [n_points, 3]  R(out_angle) Sigma_0 R' / scaling of the level-0 template; NaN unless the status
+ *               is OK.  Bit for bit what pnec_hip_patch_covariance(tmpl level 0, tmpl_pts, angle = out_angle) returns.
+ *   out_dist2   double [n_points]     dist2; NaN when the backward track was not run to its end
+ *   out_status  int32  [n_points]     pnec_hip_track_status
+ *   out_lost_level int32 [n_points]   the level of BAD_TEMPLATE, LOST_FORWARD or LOST_BACKWARD; -1 otherwise
+ * A keypoint's bits depend on its own images, positions, pattern and parameters only -- not on the call it sits in, nor
+ * on `space`, nor on the pixel type the same values are stored in.
+ * DEVICE space: the level buffers and every array but the pointer and pitch arrays are device memory of `device`,
+ * nothing waits, the call is asynchronous on `stream` (the pointer and pitch arrays are read before it returns), and
+ * the image index is clamped as in pnec_hip_patch_covariance.  HOST space: everything is staged, offsets are checked,
+ * the call blocks.  n_points = 0 returns at once.
+ * PNEC_HIP_ERR_INVALID_ARGUMENT: NULL tmpl / next / a pitch array / a level pointer / offsets / tmpl_pts / pattern, all
+ * outputs NULL, n_levels outside 1..8, max_iterations outside 1..255, n_pattern outside 1..64, an unknown pixel_type or
+ * flag, n_images < 1, n_points < 0, a level smaller than 4 pixels, a pitch below its level's width, max_recovered_dist2
+ * negative or NaN, shift or scaling not finite (scaling not positive), a bad `space`; in HOST space also bad offsets. */
+#define PNEC_HIP_TRACK_MAX_LEVELS 8
+#define PNEC_HIP_TRACK_NO_BACKWARD 1u
+typedef enum pnec_hip_track_status {
+  PNEC_HIP_TRACK_OK = 0,
+  PNEC_HIP_TRACK_BAD_TEMPLATE = 1,
+  PNEC_HIP_TRACK_LOST_FORWARD = 2,
+  PNEC_HIP_TRACK_LOST_BACKWARD = 3,
+  PNEC_HIP_TRACK_RECOVERED_TOO_FAR = 4
+} pnec_hip_track_status;
+int pnec_hip_image_pyramid_level(const void *in, void *out, int pixel_type, int64_t n_images, int32_t height,
+                                 int32_t width, int64_t pitch_in, int64_t pitch_out, int space, int device,
+                                 void *stream);
+int pnec_hip_patch_track(const void *const *tmpl, const int64_t *tmpl_pitch, const void *const *prev,
+                         const int64_t *prev_pitch, const void *const *next, const int64_t *next_pitch,
+                         int32_t n_levels, int pixel_type, int64_t n_images, int32_t height, int32_t width,
+                         const int64_t *offsets, int64_t n_points, const double *tmpl_pts, const double *init_pts,
+                         const double *init_angle, double shift_x, double shift_y, const double *pattern,
+                         int32_t n_pattern, int32_t max_iterations, double max_recovered_dist2, uint32_t flags,
+                         double scaling, double *out_pts, double *out_angle, double *out_cov, double *out_dist2,
+                         int32_t *out_status, int32_t *out_lost_level, int space, int device, void *stream);
 
 /* Name and launch geometry the auto-tuner would pick for this problem (for logs / profiles). */
 int pnec_hip_describe_launch(const pnec_hip_problem *p, const pnec_hip_options *opt,

@@ -68,6 +68,8 @@ SYMBOLS = [
     "pnec_hip_triangulate",
     "pnec_hip_relative_scale",
     "pnec_hip_patch_covariance",
+    "pnec_hip_image_pyramid_level",
+    "pnec_hip_patch_track",
     "pnec_hip_nec_eigensolver",
     "pnec_hip_ransac_eigensolver",
     "pnec_hip_problem_select",
@@ -220,6 +222,11 @@ def lib() -> C.CDLL:
     L.pnec_hip_relative_scale.argtypes = [_vp] * 8 + [C.c_double] + [_vp] * 5 + [C.c_int, _vp]
     L.pnec_hip_patch_covariance.argtypes = [_vp, C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_int64, _vp, C.c_int64, _vp, _vp,
                                             C.c_int32, C.c_double] + [_vp] * 6 + [C.c_int, C.c_int, _vp]
+    L.pnec_hip_image_pyramid_level.argtypes = [_vp, _vp, C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                               C.c_int, C.c_int, _vp]
+    L.pnec_hip_patch_track.argtypes = [_vp] * 6 + [C.c_int32, C.c_int, C.c_int64, C.c_int32, C.c_int32, _vp, C.c_int64,
+                                                   _vp, _vp, _vp, C.c_double, C.c_double, _vp, C.c_int32, C.c_int32,
+                                                   C.c_double, C.c_uint32, C.c_double] + [_vp] * 6 + [C.c_int, C.c_int, _vp]
     L.pnec_hip_describe_launch.argtypes = [_vp, C.POINTER(Options)] + [C.POINTER(C.c_int32)] * 5
     L.pnec_hip_unscented_transform.argtypes = [C.c_int64, _vp, _vp, _vp, C.c_double, C.c_int, _vp, _vp,
                                                C.c_int, C.c_int, _vp]

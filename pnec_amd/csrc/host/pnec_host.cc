@@ -448,6 +448,81 @@ std::vector<std::array<double, 3>> PatchCovariances(const void *image, pnec_hip_
   return cov;
 }
 
+static size_t PixelBytes(pnec_hip_pixel_type t) { return t == PNEC_HIP_PIXEL_U8 ? 1 : (t == PNEC_HIP_PIXEL_U16 ? 2 : 4); }
+
+Pyramid ImagePyramid(const void *image, pnec_hip_pixel_type pixel_type, int height, int width, int64_t pitch, int levels) {
+  if (!image) throw std::invalid_argument("image is NULL");
+  if (levels < 1 || levels > PNEC_HIP_TRACK_MAX_LEVELS) throw std::invalid_argument("levels must be 1 .. 8");
+  if (pixel_type != PNEC_HIP_PIXEL_U8 && pixel_type != PNEC_HIP_PIXEL_U16 && pixel_type != PNEC_HIP_PIXEL_F32)
+    throw std::invalid_argument("unknown pixel type");
+  if (height < 1 || width < 1 || (pitch > 0 && pitch < width)) throw std::invalid_argument("bad image shape");
+  const size_t es = PixelBytes(pixel_type);
+  const int64_t in_pitch = pitch > 0 ? pitch : width;
+  Pyramid p;
+  p.pixel_type = pixel_type;
+  p.height = height;
+  p.width = width;
+  p.levels.resize((size_t)levels);
+  p.levels[0].resize((size_t)height * (size_t)width * es);
+  for (int y = 0; y < height; ++y)
+    std::memcpy(p.levels[0].data() + (size_t)y * (size_t)width * es,
+                static_cast<const unsigned char *>(image) + (size_t)y * (size_t)in_pitch * es, (size_t)width * es);
+  for (int l = 1; l < levels; ++l) {
+    const int h = height >> (l - 1), w = width >> (l - 1);
+    p.levels[(size_t)l].resize((size_t)(h / 2) * (size_t)(w / 2) * es);
+    Check(pnec_hip_image_pyramid_level(p.levels[(size_t)l - 1].data(), p.levels[(size_t)l].data(), (int)pixel_type, 1, h, w,
+                                       w, w / 2, PNEC_HIP_MEM_HOST, optimization::SolverOptions().device, nullptr));
+  }
+  return p;
+}
+
+PatchTracks TrackPatches(const Pyramid &tmpl, const Pyramid &next, const std::vector<std::array<double, 2>> &points,
+                         const TrackOptions &options, const Pyramid *prev,
+                         const std::vector<std::array<double, 2>> *init_points, const std::vector<double> *init_angles,
+                         const std::vector<std::array<double, 2>> *pattern) {
+  const size_t n = points.size(), L = tmpl.levels.size();
+  if (L < 1 || L > PNEC_HIP_TRACK_MAX_LEVELS) throw std::invalid_argument("a pyramid must have 1 .. 8 levels");
+  for (const Pyramid *p : {&next, prev})
+    if (p && (p->levels.size() != L || p->height != tmpl.height || p->width != tmpl.width || p->pixel_type != tmpl.pixel_type))
+      throw std::invalid_argument("the pyramids must have the same levels, size and pixel type");
+  if ((init_points && init_points->size() != n) || (init_angles && init_angles->size() != n))
+    throw std::invalid_argument("init_points / init_angles must have one entry per keypoint");
+  const std::vector<std::array<double, 2>> &pat = pattern ? *pattern : Pattern52();
+  const double nan = std::nan("");
+  PatchTracks out;
+  out.points.assign(n, std::array<double, 2>{nan, nan});
+  out.angles.assign(n, nan);
+  out.covariances.assign(n, std::array<double, 3>{nan, nan, nan});
+  out.dist2.assign(n, nan);
+  std::vector<int32_t> st(n, PNEC_HIP_TRACK_BAD_TEMPLATE), lv(n, -1);
+  if (n > 0) {
+    const void *tp[PNEC_HIP_TRACK_MAX_LEVELS], *np[PNEC_HIP_TRACK_MAX_LEVELS], *pp[PNEC_HIP_TRACK_MAX_LEVELS];
+    int64_t pitch[PNEC_HIP_TRACK_MAX_LEVELS];
+    const size_t es = PixelBytes(tmpl.pixel_type);
+    for (size_t l = 0; l < L; ++l) {
+      pitch[l] = tmpl.width >> l;
+      const size_t bytes = (size_t)(tmpl.height >> l) * (size_t)(tmpl.width >> l) * es;
+      for (const Pyramid *p : {&tmpl, &next, prev})
+        if (p && p->levels[l].size() != bytes) throw std::invalid_argument("a pyramid level has the wrong size");
+      tp[l] = tmpl.levels[l].data();
+      np[l] = next.levels[l].data();
+      pp[l] = prev ? prev->levels[l].data() : nullptr;
+    }
+    const int64_t offsets[2] = {0, (int64_t)n};
+    Check(pnec_hip_patch_track(tp, pitch, prev ? pp : nullptr, prev ? pitch : nullptr, np, pitch, (int32_t)L,
+                               (int)tmpl.pixel_type, 1, tmpl.height, tmpl.width, offsets, (int64_t)n, points[0].data(),
+                               init_points ? (*init_points)[0].data() : nullptr, init_angles ? init_angles->data() : nullptr,
+                               options.shift[0], options.shift[1], pat.empty() ? nullptr : pat[0].data(), (int32_t)pat.size(),
+                               options.max_iterations, options.max_recovered_dist2,
+                               options.backward ? 0u : PNEC_HIP_TRACK_NO_BACKWARD, options.scaling, out.points[0].data(),
+                               out.angles.data(), out.covariances[0].data(), out.dist2.data(), st.data(), lv.data(),
+                               PNEC_HIP_MEM_HOST, optimization::SolverOptions().device, nullptr));
+  }
+  out.status.assign(st.begin(), st.end());
+  out.lost_level.assign(lv.begin(), lv.end());
+  return out;
+}
+
 }  // namespace features
 
 // -------------------------------------------------------------------------------- optimization

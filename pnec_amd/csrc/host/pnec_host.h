@@ -170,6 +170,39 @@ std::vector<std::array<double, 3>> PatchCovariances(const void *image, pnec_hip_
                                                     double scaling = 10.0, const std::vector<double> *angles = nullptr,
                                                     std::vector<int> *status = nullptr,
                                                     const std::vector<std::array<double, 2>> *pattern = nullptr);
+
+// Addition: the tracker itself -- KLTPatchOpticalFlow::trackPoints / trackPoint / trackPointAtLevel
+// (klt_patch_optical_flow.h:195-342) and POpticalFlowPatch::residual (pnec_patch.h:139-170) on basalt's image pyramid
+// [EXT] -- for one image pair, in double: pnec_hip_image_pyramid_level and pnec_hip_patch_track, include/pnec_hip.h has
+// the definitions.  Detection, keypoint ids and the view graph are the caller's.
+struct Pyramid {
+  pnec_hip_pixel_type pixel_type = PNEC_HIP_PIXEL_U8;
+  int height = 0, width = 0;                  // of level 0; level l is (height >> l) x (width >> l), rows packed
+  std::vector<std::vector<unsigned char>> levels;
+};
+// `levels` levels (1 .. PNEC_HIP_TRACK_MAX_LEVELS) of one image (`pitch` elements per row, 0 = width); level 0 is a copy
+Pyramid ImagePyramid(const void *image, pnec_hip_pixel_type pixel_type, int height, int width, int64_t pitch, int levels);
+struct TrackOptions {
+  int max_iterations = 40;                    // per level (optical_flow_max_iterations)
+  double max_recovered_dist2 = 0.04;          // optical_flow_max_recovered_dist2
+  bool backward = true;                       // the forward-backward check
+  double scaling = 10.0;                      // uncertainty_scaling
+  std::array<double, 2> shift = {0.0, 0.0};   // the reference's `offset`
+};
+struct PatchTracks {
+  std::vector<std::array<double, 2>> points;        // the tracked translations in `next`
+  std::vector<double> angles;                       // the tracked rotations: PatchCovariances' `angles`
+  std::vector<std::array<double, 3>> covariances;   // (xx, xy, yy); NaN unless status is PNEC_HIP_TRACK_OK
+  std::vector<double> dist2;
+  std::vector<int> status, lost_level;              // pnec_hip_track_status; the level of a loss or -1
+};
+// Tracks the patches built at `points` in `tmpl` into `next` and back into `prev` (nullptr: tmpl); init_points /
+// init_angles are the transform in prev (nullptr: points / 0).
+PatchTracks TrackPatches(const Pyramid &tmpl, const Pyramid &next, const std::vector<std::array<double, 2>> &points,
+                         const TrackOptions &options = TrackOptions(), const Pyramid *prev = nullptr,
+                         const std::vector<std::array<double, 2>> *init_points = nullptr,
+                         const std::vector<double> *init_angles = nullptr,
+                         const std::vector<std::array<double, 2>> *pattern = nullptr);
 }  // namespace features
 
 namespace optimization {

@@ -7,6 +7,7 @@
 //   pyceresnec(host_bvs, target_bvs, init_pose) -> 4x4
 // host_bvs/target_bvs: sequence of 3-vectors (or an [N,3] array); covariances: sequence of 3x3
 // (or [N,3,3]); init_pose: 4x4.  Addition: ceres_solver_batch over ragged lists of pairs.
+#include <cstring>
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -310,6 +311,71 @@ py::tuple patch_covariance(py::array image, arr points, double scaling) {
   return py::make_tuple(C, S);
 }
 
+static pnec_hip_pixel_type pixel_type_of(const py::array &image) {
+  if (image.dtype().is(py::dtype::of<uint8_t>())) return PNEC_HIP_PIXEL_U8;
+  if (image.dtype().is(py::dtype::of<uint16_t>())) return PNEC_HIP_PIXEL_U16;
+  if (image.dtype().is(py::dtype::of<float>())) return PNEC_HIP_PIXEL_F32;
+  throw std::invalid_argument("image must be uint8, uint16 or float32");
+}
+
+static pnec::features::Pyramid pyramid_of(const py::array &image, int levels) {
+  if (image.ndim() != 2) throw std::invalid_argument("image must be [h,w]");
+  const pnec_hip_pixel_type type = pixel_type_of(image);
+  const py::ssize_t es = image.itemsize();
+  if (image.strides(1) != es || image.strides(0) % es != 0 || image.strides(0) < image.shape(1) * es)
+    throw std::invalid_argument("image rows must be contiguous (a row pitch is allowed)");
+  return pnec::features::ImagePyramid(image.data(), type, (int)image.shape(0), (int)image.shape(1),
+                                      (int64_t)(image.strides(0) / es), levels);
+}
+
+// the levels of one image's pyramid as a list of arrays of the image's dtype
+py::list image_pyramid(py::array image, int levels) {
+  const pnec::features::Pyramid p = pyramid_of(image, levels);
+  py::list out;
+  for (size_t l = 0; l < p.levels.size(); ++l) {
+    py::array a(image.dtype(), std::vector<py::ssize_t>{(py::ssize_t)(p.height >> l), (py::ssize_t)(p.width >> l)});
+    std::memcpy(a.mutable_data(), p.levels[l].data(), p.levels[l].size());
+    out.append(a);
+  }
+  return out;
+}
+
+// (pts [N,2], angle [N], cov [N,3], dist2 [N], status [N], lost_level [N]) of the patches at `points` of `image1`
+// tracked into `image2` and back
+py::tuple patch_track(py::array image1, py::array image2, arr points, int levels, int max_iterations,
+                      double max_recovered_dist2, bool backward, double scaling, double shift_x, double shift_y) {
+  if (points.ndim() != 2 || points.shape(1) != 2) throw std::invalid_argument("points must be [N,2]");
+  const pnec::features::Pyramid p1 = pyramid_of(image1, levels), p2 = pyramid_of(image2, levels);
+  const py::ssize_t n = points.shape(0);
+  std::vector<std::array<double, 2>> pts((size_t)n);
+  auto r = points.unchecked<2>();
+  for (py::ssize_t i = 0; i < n; ++i) pts[(size_t)i] = {r(i, 0), r(i, 1)};
+  pnec::features::TrackOptions o;
+  o.max_iterations = max_iterations;
+  o.max_recovered_dist2 = max_recovered_dist2;
+  o.backward = backward;
+  o.scaling = scaling;
+  o.shift = {shift_x, shift_y};
+  const pnec::features::PatchTracks t = pnec::features::TrackPatches(p1, p2, pts, o);
+  py::array_t<double> P({n, (py::ssize_t)2}), A(n), Cv({n, (py::ssize_t)3}), D(n);
+  py::array_t<int32_t> S(n), Lv(n);
+  auto pp = P.mutable_unchecked<2>();
+  auto cc = Cv.mutable_unchecked<2>();
+  auto aa = A.mutable_unchecked<1>();
+  auto dd = D.mutable_unchecked<1>();
+  auto ss = S.mutable_unchecked<1>();
+  auto ll = Lv.mutable_unchecked<1>();
+  for (py::ssize_t i = 0; i < n; ++i) {
+    for (int k = 0; k < 2; ++k) pp(i, k) = t.points[(size_t)i][(size_t)k];
+    for (int k = 0; k < 3; ++k) cc(i, k) = t.covariances[(size_t)i][(size_t)k];
+    aa(i) = t.angles[(size_t)i];
+    dd(i) = t.dist2[(size_t)i];
+    ss(i) = t.status[(size_t)i];
+    ll(i) = t.lost_level[(size_t)i];
+  }
+  return py::make_tuple(P, A, Cv, D, S, Lv);
+}
+
 // PNEC::Solve for ONE frame pair through the overload asked for (pnec.cc:69-75, :77-124, :126-134,
 // :135-208): overload 0 = (bvs1, bvs2, covs, init), 1 = (+ inliers), 2 = (+ timing), 3 = (+ inliers,
 // timing).  Returns (pose 4x4, inliers or None, timing dict or None).
@@ -411,6 +477,15 @@ PYBIND11_MODULE(pypnec, m) {
         "pnec::common::RelativeScale (addition; device): (scale, q25, q75, n_used, ratio [N]) -- the baseline of `pose` in "
         "units of the baseline of `pose_prev` from the tracks `link` ties to the previous pair -- include/pnec_hip.h "
         "pnec_hip_relative_scale");
+  m.def("image_pyramid", &image_pyramid, py::arg("image"), py::arg("levels"),
+        "pnec::features::ImagePyramid (addition; device): the levels of one image's pyramid, level 0 first -- "
+        "include/pnec_hip.h pnec_hip_image_pyramid_level");
+  m.def("patch_track", &patch_track, py::arg("image1"), py::arg("image2"), py::arg("points"), py::arg("levels") = 5,
+        py::arg("max_iterations") = 40, py::arg("max_recovered_dist2") = 0.04, py::arg("backward") = true,
+        py::arg("scaling") = 10.0, py::arg("shift_x") = 0.0, py::arg("shift_y") = 0.0,
+        "pnec::features::TrackPatches (addition; device): (pts [N,2], angle [N], cov [N,3], dist2 [N], status [N], "
+        "lost_level [N]) of the Pattern52 patches at `points` of image1 tracked into image2 and back, in double -- "
+        "include/pnec_hip.h pnec_hip_patch_track");
   m.def("patch_covariance", &patch_covariance, py::arg("image"), py::arg("points"), py::arg("scaling") = 10.0,
         "pnec::features::PatchCovariances (addition; device): (cov [N,3] as xx, xy, yy, status [N]) -- the 2x2 image "
         "covariance of the keypoints `points` [N,2] of one uint8 / uint16 / float32 image from their Pattern52 patches, in "

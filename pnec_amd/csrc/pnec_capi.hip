@@ -17,6 +17,7 @@
 #include "pnec_front_shared.hpp"
 #include "pnec_internal.hpp"
 #include "pnec_patch_cov.hpp"
+#include "pnec_patch_track.hpp"
 #include "pnec_pose_cov.hpp"
 #include "pnec_residuals.hpp"
 #include "pnec_relative_scale.hpp"
@@ -1375,6 +1376,194 @@ int pnec_hip_patch_covariance(const void *images, int pixel_type, int64_t n_imag
     if (int rc = stage.status()) return rc;
   }
   PNEC_HIP_TRY(launch_patch_covariance(pixel_type, a, stream));
+  return space == PNEC_HIP_MEM_HOST ? stage.finish() : 0;
+}
+
+// the pyramid's halving step and the tracker: pnec_patch_track.hip.  Staged like the patch covariances.
+static size_t pixel_bytes(int pixel_type) {
+  switch (pixel_type) {
+    case PNEC_HIP_PIXEL_U8: return 1;
+    case PNEC_HIP_PIXEL_U16: return 2;
+    case PNEC_HIP_PIXEL_F32: return 4;
+    default: return 0;
+  }
+}
+
+int pnec_hip_image_pyramid_level(const void *in, void *out, int pixel_type, int64_t n_images, int32_t height,
+                                 int32_t width, int64_t pitch_in, int64_t pitch_out, int space, int device,
+                                 void *stream_) {
+  if (!in || !out) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "image_pyramid_level: in or out is NULL");
+  const size_t elem = pixel_bytes(pixel_type);
+  if (!elem) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "image_pyramid_level: unknown pixel_type");
+  if (n_images < 1 || height < 4 || width < 4)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "image_pyramid_level: n_images must be >= 1, height and width >= 4");
+  if (pitch_in < width || pitch_out < width / 2)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "image_pyramid_level: a pitch (in elements) is below its width");
+  if (space != PNEC_HIP_MEM_DEVICE && space != PNEC_HIP_MEM_HOST)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "image_pyramid_level: bad memory space");
+  if (n_images > 0x7fffffffLL || (double)n_images * (double)height * (double)pitch_in * (double)elem > 9.0e18 ||
+      (double)n_images * (double)(height / 2) * (double)pitch_out * (double)elem > 9.0e18)
+    return fail(PNEC_HIP_ERR_UNSUPPORTED, "image_pyramid_level: the images do not fit a 64-bit byte count");
+  DeviceGuard guard(device);
+  if (!guard.ok) return fail(PNEC_HIP_ERR_HIP_RUNTIME, "hipSetDevice failed (no such device?)");
+  hipStream_t stream = (hipStream_t)stream_;
+  StageHolder holder;
+  holder.p.device = device;
+  HostStage stage(&holder.p, stream);
+  PyramidLevelArgs a;
+  a.w = width;
+  a.h = height;
+  a.pitch_in = pitch_in;
+  a.pitch_out = pitch_out;
+  a.n_images = n_images;
+  a.in = in;
+  a.out = out;
+  if (space == PNEC_HIP_MEM_HOST) {
+    const int64_t in_bytes = (int64_t)elem * ((n_images * (int64_t)height - 1) * pitch_in + width);
+    const int64_t out_bytes = (int64_t)elem * ((n_images * (int64_t)(height / 2) - 1) * pitch_out + width / 2);
+    if (int rc = stage.reserve((in_bytes + 7) / 8 + (out_bytes + 7) / 8, 0)) return rc;
+    a.in = stage.up_bytes(in, in_bytes);
+    // (the whole output block travels up first: the padding between its rows comes back as the caller had it)
+    a.out = stage.out(static_cast<uint8_t *>(out), out_bytes);
+    if (int rc = stage.status()) return rc;
+    PNEC_HIP_TRY(hipMemcpyAsync(a.out, out, (size_t)out_bytes, hipMemcpyHostToDevice, stream));
+  }
+  PNEC_HIP_TRY(launch_image_pyramid_level(pixel_type, a, stream));
+  return space == PNEC_HIP_MEM_HOST ? stage.finish() : 0;
+}
+
+int pnec_hip_patch_track(const void *const *tmpl, const int64_t *tmpl_pitch, const void *const *prev,
+                         const int64_t *prev_pitch, const void *const *next, const int64_t *next_pitch,
+                         int32_t n_levels, int pixel_type, int64_t n_images, int32_t height, int32_t width,
+                         const int64_t *offsets, int64_t n_points, const double *tmpl_pts, const double *init_pts,
+                         const double *init_angle, double shift_x, double shift_y, const double *pattern,
+                         int32_t n_pattern, int32_t max_iterations, double max_recovered_dist2, uint32_t flags,
+                         double scaling, double *out_pts, double *out_angle, double *out_cov, double *out_dist2,
+                         int32_t *out_status, int32_t *out_lost_level, int space, int device, void *stream_) {
+  if (!prev) {
+    prev = tmpl;
+    prev_pitch = tmpl_pitch;
+  }
+  if (!tmpl || !tmpl_pitch || !prev_pitch || !next || !next_pitch || !offsets || !pattern || (!tmpl_pts && n_points > 0))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT,
+                "patch_track: tmpl, next, a pitch array, offsets, tmpl_pts or pattern is NULL");
+  if (!out_pts && !out_angle && !out_cov && !out_dist2 && !out_status && !out_lost_level)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_track: every output is NULL");
+  if (n_levels < 1 || n_levels > PNEC_HIP_TRACK_MAX_LEVELS)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_track: n_levels must be 1 .. 8");
+  if (max_iterations < 1 || max_iterations > 255)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_track: max_iterations must be 1 .. 255");
+  if (n_pattern < 1 || n_pattern > PNEC_HIP_PATCH_MAX_POINTS)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_track: n_pattern must be 1 .. 64");
+  const size_t elem = pixel_bytes(pixel_type);
+  if (!elem) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_track: unknown pixel_type");
+  if (flags & ~PNEC_HIP_TRACK_NO_BACKWARD) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_track: unknown flags");
+  if (n_images < 1 || n_points < 0)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_track: n_images must be >= 1, n_points >= 0");
+  if (height < 1 || width < 1 || (height >> (n_levels - 1)) < 4 || (width >> (n_levels - 1)) < 4)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_track: the smallest level is below 4 pixels in height or width");
+  for (int l = 0; l < n_levels; ++l) {
+    if (!tmpl[l] || !prev[l] || !next[l]) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_track: a level pointer is NULL");
+    if (tmpl_pitch[l] < (width >> l) || prev_pitch[l] < (width >> l) || next_pitch[l] < (width >> l))
+      return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_track: a pitch (in elements) is below its level's width");
+  }
+  if (!(max_recovered_dist2 >= 0.0))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_track: max_recovered_dist2 must be >= 0");
+  if (!std::isfinite(shift_x) || !std::isfinite(shift_y))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_track: shift must be finite");
+  if (!(scaling > 0.0) || !std::isfinite(scaling))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_track: scaling must be positive and finite");
+  if (space != PNEC_HIP_MEM_DEVICE && space != PNEC_HIP_MEM_HOST)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_track: bad memory space");
+  if (n_images > 0x7fffffffLL)
+    return fail(PNEC_HIP_ERR_UNSUPPORTED, "patch_track: the images do not fit a 64-bit byte count");
+  for (int l = 0; l < n_levels; ++l) {
+    const double rows = (double)n_images * (double)(height >> l) * (double)elem;
+    if (rows * (double)tmpl_pitch[l] > 9.0e18 || rows * (double)prev_pitch[l] > 9.0e18 || rows * (double)next_pitch[l] > 9.0e18)
+      return fail(PNEC_HIP_ERR_UNSUPPORTED, "patch_track: the images do not fit a 64-bit byte count");
+  }
+  if (space == PNEC_HIP_MEM_HOST) {
+    bool ok = offsets[0] == 0 && offsets[n_images] == n_points;
+    for (int64_t f = 0; ok && f < n_images; ++f) ok = offsets[f] <= offsets[f + 1];
+    if (!ok) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_track: offsets must be non-decreasing from 0 to n_points");
+  }
+  if (n_points == 0) return 0;
+  DeviceGuard guard(device);
+  if (!guard.ok) return fail(PNEC_HIP_ERR_HIP_RUNTIME, "hipSetDevice failed (no such device?)");
+  hipStream_t stream = (hipStream_t)stream_;
+  StageHolder holder;
+  holder.p.device = device;
+  HostStage stage(&holder.p, stream);
+  PatchTrackArgs a{};
+  a.n_levels = n_levels;
+  a.w = width;
+  a.h = height;
+  a.n_images = n_images;
+  a.n_points = n_points;
+  a.shift_x = shift_x;
+  a.shift_y = shift_y;
+  a.n_pattern = n_pattern;
+  a.max_iterations = max_iterations;
+  a.max_recovered_dist2 = max_recovered_dist2;
+  a.backward = (flags & PNEC_HIP_TRACK_NO_BACKWARD) ? 0 : 1;
+  a.scaling = scaling;
+  for (int l = 0; l < n_levels; ++l) {
+    a.tmpl.pitch[l] = tmpl_pitch[l];
+    a.prev.pitch[l] = prev_pitch[l];
+    a.next.pitch[l] = next_pitch[l];
+  }
+  if (space == PNEC_HIP_MEM_DEVICE) {
+    for (int l = 0; l < n_levels; ++l) {
+      a.tmpl.level[l] = tmpl[l];
+      a.prev.level[l] = prev[l];
+      a.next.level[l] = next[l];
+    }
+    a.offsets = offsets;
+    a.tmpl_pts = tmpl_pts;
+    a.init_pts = init_pts;
+    a.init_angle = init_angle;
+    a.pattern = pattern;
+    a.out_pts = out_pts;
+    a.out_angle = out_angle;
+    a.out_cov = out_cov;
+    a.out_dist2 = out_dist2;
+    a.out_status = out_status;
+    a.out_lost_level = out_lost_level;
+  } else {
+    const int64_t M = n_points;
+    auto level_bytes = [&](int l, int64_t pitch) {
+      return (int64_t)elem * ((n_images * (int64_t)(height >> l) - 1) * pitch + (width >> l));
+    };
+    // a level that two pyramids share (prev = tmpl) is staged once
+    int64_t pixels8 = 0;
+    for (int l = 0; l < n_levels; ++l) {
+      pixels8 += (level_bytes(l, tmpl_pitch[l]) + 7) / 8 + (level_bytes(l, next_pitch[l]) + 7) / 8;
+      if (prev[l] != tmpl[l] || prev_pitch[l] != tmpl_pitch[l]) pixels8 += (level_bytes(l, prev_pitch[l]) + 7) / 8;
+    }
+    // stage: [pixels | offsets F+1 (int64) | tmpl_pts 2M | init_pts 2M | init_angle M | pattern 2P | pts 2M | angle M |
+    // cov 3M | dist2 M], ints [status M | lost_level M]
+    if (int rc = stage.reserve(pixels8 + (n_images + 1) + 12 * M + 2 * n_pattern, 2 * M)) return rc;
+    for (int l = 0; l < n_levels; ++l) {
+      a.tmpl.level[l] = stage.up_bytes(tmpl[l], level_bytes(l, tmpl_pitch[l]));
+      a.next.level[l] = stage.up_bytes(next[l], level_bytes(l, next_pitch[l]));
+      a.prev.level[l] = (prev[l] != tmpl[l] || prev_pitch[l] != tmpl_pitch[l])
+                            ? stage.up_bytes(prev[l], level_bytes(l, prev_pitch[l]))
+                            : a.tmpl.level[l];
+    }
+    a.offsets = stage.up(offsets, n_images + 1);
+    a.tmpl_pts = stage.up(tmpl_pts, 2 * M);
+    a.init_pts = stage.up(init_pts, 2 * M);
+    a.init_angle = stage.up(init_angle, M);
+    a.pattern = stage.up(pattern, 2 * (int64_t)n_pattern);
+    a.out_pts = stage.out(out_pts, 2 * M);
+    a.out_angle = stage.out(out_angle, M);
+    a.out_cov = stage.out(out_cov, 3 * M);
+    a.out_dist2 = stage.out(out_dist2, M);
+    a.out_status = stage.out(out_status, M);
+    a.out_lost_level = stage.out(out_lost_level, M);
+    if (int rc = stage.status()) return rc;
+  }
+  PNEC_HIP_TRY(launch_patch_track(pixel_type, a, stream));
   return space == PNEC_HIP_MEM_HOST ? stage.finish() : 0;
 }
 

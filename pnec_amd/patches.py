@@ -3,8 +3,12 @@
 ``Batch.fill_keypoints``, computed on the device from images and keypoint positions.
 
 This is the covariance POpticalFlowPatch::setFromImage keeps (include/features/tracking/pnec_patch.h:78-137) after
-KLTPatchOpticalFlow's scaling and rotation.  It is not tracking (positions come from the caller's tracker) and it is
-double arithmetic, not the reference's float: no float parity is claimed.
+KLTPatchOpticalFlow's scaling and rotation.  It is double arithmetic, not the reference's float: no float parity is
+claimed.
+
+Patch tracking: ``image_pyramid`` (``pnec_hip_image_pyramid_level``) and ``patch_track`` (``pnec_hip_patch_track``), the
+pyramidal SE(2) KLT iteration with its forward-backward check (klt_patch_optical_flow.h:195-342) -- the producer of the
+positions and of ``angle`` above.  Detection, keypoint ids and the view graph are not here.
 """
 from __future__ import annotations
 
@@ -18,6 +22,11 @@ PATCH_OK, PATCH_EMPTY, PATCH_SINGULAR = 0, 1, 2      # pnec_hip_patch_status
 PATCH_NAMES = {PATCH_OK: "ok", PATCH_EMPTY: "empty_patch", PATCH_SINGULAR: "singular_hessian"}
 PIXEL_U8, PIXEL_U16, PIXEL_F32 = 0, 1, 2             # pnec_hip_pixel_type
 PATCH_MAX_POINTS = 64
+TRACK_OK, TRACK_BAD_TEMPLATE, TRACK_LOST_FORWARD, TRACK_LOST_BACKWARD, TRACK_RECOVERED_TOO_FAR = range(5)  # pnec_hip_track_status
+TRACK_NAMES = {TRACK_OK: "ok", TRACK_BAD_TEMPLATE: "bad_template", TRACK_LOST_FORWARD: "lost_forward",
+               TRACK_LOST_BACKWARD: "lost_backward", TRACK_RECOVERED_TOO_FAR: "recovered_too_far"}
+TRACK_MAX_LEVELS = 8
+TRACK_NO_BACKWARD = 1
 
 
 def _pattern52() -> np.ndarray:
@@ -134,3 +143,178 @@ def patch_covariance(images, pts, offsets=None, pattern=PATTERN52, scaling: floa
         p(angle_d), p(out["cov"]), p(out["hessian"]), p(out["mean"]), p(out["n_valid"]), p(out["status"]), space, device,
         stream))
     return PatchCovariance(out["cov"], out["hessian"], out["mean"], out["n_valid"], out["status"], offsets_d)
+
+
+@dataclass
+class PatchTrack:
+    """pnec_hip_patch_track's outputs, one row per keypoint; numpy or torch, matching the input."""
+    pts: object          # [M,2] the tracked translation in `next` (where the forward track stood last, also when lost)
+    angle: object        # [M] the tracked rotation, radians: patch_covariance's `angle`
+    cov: object          # [M,3] (xx, xy, yy) of the level-0 template, rotated and scaled; NaN unless status == 0
+    dist2: object        # [M] squared forward-backward distance; NaN when the backward track did not finish
+    status: object       # [M] int32: TRACK_OK, TRACK_BAD_TEMPLATE, TRACK_LOST_FORWARD, TRACK_LOST_BACKWARD, TRACK_RECOVERED_TOO_FAR
+    lost_level: object   # [M] int32: the level of a bad template or a loss, -1 otherwise
+    offsets: object = None
+
+    def ok(self):
+        return self.status == TRACK_OK
+
+
+def _as_batch(images):
+    """images as ([F,h,w] array or tensor with unit pixel stride and evenly pitched images, on_device)"""
+    on_device = _is_torch(images) and images.is_cuda
+    if _is_torch(images) and not on_device:
+        images = images.numpy()
+    if not on_device:
+        images = np.asarray(images)
+    if images.ndim == 2:
+        images = images[None]
+    if images.ndim != 3:
+        raise ValueError("images must be [F,h,w] or [h,w]")
+    F, h, w = (int(x) for x in images.shape)
+    if on_device:
+        _pixel_type(str(images.dtype).replace("torch.", ""))
+        st = images.stride()
+        if st[2] != 1 or st[1] < w or (F > 1 and st[0] != h * st[1]):
+            images = images.contiguous()
+    else:
+        _pixel_type(images.dtype.name)
+        es, st = images.dtype.itemsize, images.strides
+        if st[2] != es or st[1] % es or st[1] < w * es or (F > 1 and st[0] != h * st[1]):
+            images = np.ascontiguousarray(images)
+    return images, on_device
+
+
+def _pitch(images, on_device) -> int:
+    return int(images.stride()[1]) if on_device else images.strides[1] // images.dtype.itemsize
+
+
+def _ptype(images, on_device) -> int:
+    return _pixel_type(str(images.dtype).replace("torch.", "") if on_device else images.dtype.name)
+
+
+def _where(images, on_device):
+    """(space, device, stream) of a call on `images`"""
+    if not on_device:
+        return capi.MEM_HOST, 0, None
+    import torch
+    dev = images.device
+    device = dev.index if dev.index is not None else torch.cuda.current_device()
+    return capi.MEM_DEVICE, device, torch.cuda.current_stream(device).cuda_stream
+
+
+def image_pyramid(images, levels: int) -> list:
+    """The `levels` levels (1 .. 8) of the pyramid of `images` [F,h,w] (or one image [h,w]), uint8 / uint16 / float32:
+    a list whose entry 0 is the input (as a [F,h,w] batch, not copied when its rows are evenly pitched) and whose entry l
+    is entry l - 1 halved by pnec_hip_image_pyramid_level (5-tap binomial filter, reflected borders, sizes floored).
+    torch.cuda in -> device tensors out, asynchronous on torch's current stream; numpy in -> numpy out."""
+    if not 1 <= int(levels) <= TRACK_MAX_LEVELS:
+        raise ValueError(f"levels must be 1 .. {TRACK_MAX_LEVELS}")
+    images, on_device = _as_batch(images)
+    space, device, stream = _where(images, on_device)
+    ptype = _ptype(images, on_device)
+    out = [images]
+    for _ in range(1, int(levels)):
+        src = out[-1]
+        F, h, w = (int(x) for x in src.shape)
+        if on_device:
+            import torch
+            dst = torch.empty((F, h // 2, w // 2), dtype=src.dtype, device=src.device)
+            ps, pd = src.data_ptr(), dst.data_ptr()
+        else:
+            dst = np.empty((F, h // 2, w // 2), dtype=src.dtype)
+            ps, pd = src.ctypes.data, dst.ctypes.data
+        capi.check(capi.lib().pnec_hip_image_pyramid_level(ps, pd, ptype, F, h, w, _pitch(src, on_device), w // 2, space,
+                                                          device, stream))
+        out.append(dst)
+    return out
+
+
+def patch_track(tmpl, next, tmpl_pts, offsets=None, prev=None, init_pts=None, init_angle=None, shift=(0.0, 0.0),
+                pattern=PATTERN52, max_iterations: int = 40, max_recovered_dist2: float = 0.04, backward: bool = True,
+                scaling: float = 10.0, outputs=("pts", "angle", "cov", "dist2", "status", "lost_level")) -> PatchTrack:
+    """Tracks the patches built at `tmpl_pts` [M,2] (level-0 pixels, x = column, y = row) in the pyramid `tmpl` into the
+    pyramid `next`, and back into `prev` (None: `tmpl`) for the forward-backward check.  A pyramid is a list of [F,h_l,w_l]
+    batches as image_pyramid returns it; keypoints [offsets[f], offsets[f+1]) lie in image f.  `init_pts` / `init_angle`
+    are the transform in `prev` (None: tmpl_pts / 0), `shift` is added to the forward start.  All pyramids in torch.cuda
+    tensors -> everything stays on the device, asynchronous on torch's current stream, torch.cuda tensors out; numpy in
+    -> staged, numpy out."""
+    pyrs = {"tmpl": tmpl, "next": next, "prev": prev}
+    levels = len(tmpl)
+    norm, on = {}, None
+    for name, pyr in pyrs.items():
+        if pyr is None:
+            continue
+        if len(pyr) != levels:
+            raise ValueError("the pyramids must have the same number of levels")
+        got = [_as_batch(lv) for lv in pyr]
+        if any(d != got[0][1] for _, d in got) or (on is not None and got[0][1] != on):
+            raise ValueError("the pyramids must all be on the device or all on the host")
+        on = got[0][1]
+        norm[name] = [a for a, _ in got]
+    if not 1 <= levels <= TRACK_MAX_LEVELS:
+        raise ValueError(f"a pyramid must have 1 .. {TRACK_MAX_LEVELS} levels")
+    base = norm["tmpl"][0]
+    F, h, w = (int(x) for x in base.shape)
+    ptype = _ptype(base, on)
+    for pyr in norm.values():
+        for l, lv in enumerate(pyr):
+            if tuple(int(x) for x in lv.shape) != (F, h >> l, w >> l) or _ptype(lv, on) != ptype:
+                raise ValueError(f"level {l} must be [{F},{h >> l},{w >> l}] of the pyramid's pixel type")
+    space, device, stream = _where(base, on)
+    if on:
+        import torch
+        dev = base.device
+        f64 = dict(dtype=torch.float64, device=dev)
+        as_in = lambda a, dt: a.to(device=dev, dtype=dt).contiguous() if _is_torch(a) else \
+            torch.as_tensor(np.array(a), dtype=dt, device=dev)
+        F64, I64 = torch.float64, torch.int64
+        p = lambda a: None if a is None else a.data_ptr()
+        M = int(tmpl_pts.shape[0])
+        new = {"pts": lambda: torch.empty((M, 2), **f64), "angle": lambda: torch.empty((M,), **f64),
+               "cov": lambda: torch.empty((M, 3), **f64), "dist2": lambda: torch.empty((M,), **f64),
+               "status": lambda: torch.empty((M,), dtype=torch.int32, device=dev),
+               "lost_level": lambda: torch.empty((M,), dtype=torch.int32, device=dev)}
+    else:
+        as_in = lambda a, dt: np.ascontiguousarray(a.cpu().numpy() if _is_torch(a) else a, dtype=dt)
+        F64, I64 = np.float64, np.int64
+        p = lambda a: None if a is None else a.ctypes.data
+        M = int(np.shape(tmpl_pts)[0])
+        new = {"pts": lambda: np.empty((M, 2)), "angle": lambda: np.empty(M), "cov": lambda: np.empty((M, 3)),
+               "dist2": lambda: np.empty(M), "status": lambda: np.empty(M, dtype=np.int32),
+               "lost_level": lambda: np.empty(M, dtype=np.int32)}
+    tmpl_pts = as_in(tmpl_pts, F64)
+    offsets_d = as_in(np.array([0, M], dtype=np.int64) if offsets is None else offsets, I64)
+    init_pts = None if init_pts is None else as_in(init_pts, F64)
+    init_angle = None if init_angle is None else as_in(init_angle, F64)
+    pattern_d = as_in(pattern, F64)
+    if tuple(tmpl_pts.shape) != (M, 2) or (init_pts is not None and tuple(init_pts.shape) != (M, 2)):
+        raise ValueError("tmpl_pts and init_pts must be [M,2] (x = column, y = row)")
+    if init_angle is not None and tuple(init_angle.shape) != (M,):
+        raise ValueError("init_angle must be [M]")
+    if tuple(offsets_d.shape) != (F + 1,):
+        raise ValueError("offsets must be [F+1] (one image: [0, M], or leave it out)")
+    if pattern_d.ndim != 2 or pattern_d.shape[1] != 2:
+        raise ValueError("pattern must be [P,2]")
+    unknown = set(outputs) - set(new)
+    if unknown:
+        raise ValueError(f"unknown outputs {sorted(unknown)}")
+    out = {k: (new[k]() if k in outputs else None) for k in new}
+
+    import ctypes as C
+
+    def table(pyr):
+        if pyr is None:
+            return None, None
+        ptrs = (C.c_void_p * levels)(*[p(lv) for lv in pyr])
+        pitches = (C.c_int64 * levels)(*[_pitch(lv, on) for lv in pyr])
+        return ptrs, pitches
+    tp, tq = table(norm["tmpl"])
+    pp, pq = table(norm.get("prev"))
+    np_, nq = table(norm["next"])
+    capi.check(capi.lib().pnec_hip_patch_track(
+        tp, tq, pp, pq, np_, nq, levels, ptype, F, h, w, p(offsets_d), M, p(tmpl_pts), p(init_pts), p(init_angle),
+        float(shift[0]), float(shift[1]), p(pattern_d), int(pattern_d.shape[0]), int(max_iterations),
+        float(max_recovered_dist2), 0 if backward else TRACK_NO_BACKWARD, float(scaling), p(out["pts"]), p(out["angle"]),
+        p(out["cov"]), p(out["dist2"]), p(out["status"]), p(out["lost_level"]), space, device, stream))
+    return PatchTrack(out["pts"], out["angle"], out["cov"], out["dist2"], out["status"], out["lost_level"], offsets_d)
