@@ -34,6 +34,8 @@
  *   KLTPatchOpticalFlow::trackPoints / trackPoint / trackPointAtLevel  pnec_hip_patch_track,
  *    klt_patch_optical_flow.h:195-342 + POpticalFlowPatch::residual     pnec_hip_image_pyramid_level
  *    pnec_patch.h:139-170  (the iteration and the pyramid: no detection, no ids; double, not the reference's float)
+ *   KLTPatchOpticalFlow::addPoints  klt_patch_optical_flow.h:344-385       pnec_hip_detect_keypoints
+ *    (basalt's detectKeypoints on a grid + cv::FAST [EXT]: the detector only -- no ids, no track bookkeeping)
  *   PNEC::Eigensolver (no RANSAC) / WeightedEigensolver  pnec.cc:231-348   pnec_hip_nec_eigensolver /
  *                                                               pnec_hip_weighted_eigensolver
  *
@@ -777,9 +779,9 @@ int pnec_hip_patch_covariance(const void *images, int pixel_type, int64_t n_imag
  * halving step of the image pyramid it runs on (added within ABI 8: pure additions, PNEC_HIP_ABI_VERSION is unchanged).
  * This is the producer of pnec_hip_patch_covariance's positions and of its `angle`: trackPoints / trackPoint /
  * trackPointAtLevel (include/features/tracking/klt_patch_optical_flow.h:195-342) and POpticalFlowPatch::residual
- * (pnec_patch.h:139-170) on top of setFromImage as restated above.  FAST detection, the grid, keypoint ids, the view
- * graph and stereo filtering are NOT here.  ALL ARITHMETIC IS DOUBLE; the reference's float bits are not reproduced and
- * not claimed.  [EXT] basalt's image.h (interp, InBounds), image_pyr.h (the pyramid) and Sophus (SE2::exp) are not in the
+ * (pnec_patch.h:139-170) on top of setFromImage as restated above.  Keypoint ids, the view graph and stereo filtering
+ * are NOT here; FAST detection on the grid is pnec_hip_detect_keypoints below.  ALL ARITHMETIC IS DOUBLE; the
+ * reference's float bits are not reproduced and not claimed.  [EXT] basalt's image.h (interp, InBounds), image_pyr.h (the pyramid) and Sophus (SE2::exp) are not in the
  * reference tree: they are restated from the published code, and what follows is this library's own definition.
  *
  * --- pnec_hip_image_pyramid_level: one halving step.
@@ -874,6 +876,70 @@ int pnec_hip_patch_track(const void *const *tmpl, const int64_t *tmpl_pitch, con
                          int32_t n_pattern, int32_t max_iterations, double max_recovered_dist2, uint32_t flags,
                          double scaling, double *out_pts, double *out_angle, double *out_cov, double *out_dist2,
                          int32_t *out_status, int32_t *out_lost_level, int space, int device, void *stream);
+
+/* Keypoint detection: grid FAST-9 corners (added within ABI 8: a pure addition, PNEC_HIP_ABI_VERSION is unchanged).
+ * This is the producer of pnec_hip_patch_track's tmpl_pts: what KLTPatchOpticalFlow::addPoints
+ * (include/features/tracking/klt_patch_optical_flow.h:344-385) gets from basalt's detectKeypoints(level image, kd,
+ * optical_flow_detection_grid_size, 1, current points), called for the first frame (:145) and after every tracking step
+ * (:180) to refill the grid cells whose tracks were lost.  Keypoint ids, the bookkeeping of tracks across frames, stereo
+ * filtering and the view graph are NOT here.  INTEGER ARITHMETIC ON 8-BIT PIXELS: every output is exact.
+ * [EXT] basalt's keypoints.cpp and OpenCV's cv::FAST, which it calls, are not in the reference tree: they are restated
+ * from the published code, and what follows is this library's own definition.
+ *
+ * Input.
+ *   images      n_images images of height x width pixels in pnec_hip_patch_covariance's layout, `pitch` elements per row.
+ *   pixel_type  PNEC_HIP_PIXEL_U8, or PNEC_HIP_PIXEL_U16 read as v >> 8 (the reference's quantisation of its 16-bit
+ *               pyramid; the low byte does not matter).  PNEC_HIP_PIXEL_F32 is refused: a float image has no declared
+ *               range to quantise.
+ *   grid        the cell size G, 8 <= G <= 64 (the reference's configurations use 20, 30 and 50); width, height >= G.
+ *   points_per_cell   K, 1 <= K <= 4 (the reference always passes 1).
+ *   min_threshold     T, 0 <= T <= 254 (the reference's loop ends at 5).
+ *   edge        E >= 0 (the reference's EDGE_THRESHOLD is 19).
+ *   cur_offsets, n_cur, cur_pts   int64 [n_images + 1], double [n_cur, 2]: the points already tracked in each image,
+ *               ragged, in the image's own pixel coordinates.  Either pointer may be NULL (with n_cur = 0): none.
+ *
+ * Cells.  x_start = (width % G) / 2, nx = width / G; cell column cx covers x_start + cx G .. x_start + cx G + G - 1; the
+ * same in y.  n_cells = nx ny, cell index c = cx ny + cy (the reference's loop order, x outer).
+ * Occupied cells.  A current point p with x_start <= p.x < x_start + nx G, and the same in y, marks cell
+ * ((int)((p.x - x_start) / G), (int)((p.y - y_start) / G)) in double arithmetic; a NaN coordinate marks nothing.  An
+ * occupied cell is not searched.
+ * Corner measure.  The detector sees each cell as a G x G image of its own, as the reference does: pixels within 3 of a
+ * cell's border are never corners and nothing outside the cell is read.  For an interior pixel p of value I and the 16
+ * ring pixels I_k at (0,-3) (1,-3) (2,-2) (3,-1) (3,0) (3,1) (2,2) (1,3) (0,3) (-1,3) (-2,2) (-3,1) (-3,0) (-3,-1) (-2,-2)
+ * (-1,-3):  m(p) = the largest value, over the 16 arcs of 9 contiguous ring pixels and both signs, of the minimum over
+ * the arc of +-(I_k - I), floored at 0.  p is a FAST-9 corner at threshold t iff m > t; cv::FAST's score is m - 1.
+ * Selection.  A candidate has m > T, m strictly greater than m at all 8 neighbours (a neighbour on the 3-pixel border has
+ * m = 0), and an image position with E <= x < width - E - 1 and E <= y < height - E - 1 (basalt's InBounds).  The cell's
+ * output is its up to K candidates by descending m, then ascending y, then ascending x.  For K = 1 this is what the
+ * reference's loop returns (cv::FAST with non-maximum suppression at thresholds 40, 20, 10, 5; the best in-bounds point
+ * of the first round that has one).  Two deviations: ties are broken by raster order (the reference's std::sort leaves
+ * them open), and for K > 1 the points are distinct (the reference's loop would add the same point again in the next
+ * round).
+ *
+ * Outputs, cap = n_images n_cells K entries provided by the caller.
+ *   out_cell        int32 [n_images, n_cells]  the number of points the cell produced, 0 .. K; -1 for an occupied cell.
+ *                   Required (it is the occupancy map while the call runs).
+ *   out_offsets     int64 [n_images + 1]       points [out_offsets[f], out_offsets[f+1]) lie in image f.  Required.
+ *   out_pts         double [cap, 2]            x, y: integers in doubles, what pnec_hip_patch_track / _patch_covariance
+ *                   take as tmpl_pts / pts.  Required.
+ *   out_score       int32 [cap]                m - 1.  May be NULL.
+ *   out_cell_index  int32 [cap]                c.  May be NULL.
+ * Points are compacted image by image, cell by cell in index order, rank by rank; entries at and beyond
+ * out_offsets[n_images] are left untouched.  Order and content are a function of the inputs alone (no atomic decides a
+ * position), and a cell's points depend on its own pixels and parameters only -- not on the call it sits in, nor on
+ * `space`, nor on the pixel type the same values are stored in.
+ * DEVICE space: every array is device memory of `device`, nothing is allocated, nothing waits, the call is asynchronous
+ * on `stream`, and the image index of a current point is clamped as in pnec_hip_patch_covariance.  HOST space:
+ * everything is staged, cur_offsets is checked, the call blocks.
+ * PNEC_HIP_ERR_INVALID_ARGUMENT: NULL images / out_cell / out_offsets / out_pts, grid, points_per_cell or min_threshold
+ * outside its range, edge < 0, width or height < grid, pitch < width, n_images < 1, n_cur < 0, F32 or an unknown
+ * pixel_type, cur_pts without cur_offsets (or cur_offsets with n_cur > 0 without cur_pts), a bad `space`; in HOST space
+ * also cur_offsets that do not run from 0 to n_cur without decreasing. */
+int pnec_hip_detect_keypoints(const void *images, int pixel_type, int64_t n_images, int32_t height, int32_t width,
+                              int64_t pitch, int32_t grid, int32_t points_per_cell, int32_t min_threshold, int32_t edge,
+                              const int64_t *cur_offsets, int64_t n_cur, const double *cur_pts, int32_t *out_cell,
+                              int64_t *out_offsets, double *out_pts, int32_t *out_score, int32_t *out_cell_index,
+                              int space, int device, void *stream);
 
 /* Name and launch geometry the auto-tuner would pick for this problem (for logs / profiles). */
 int pnec_hip_describe_launch(const pnec_hip_problem *p, const pnec_hip_options *opt,

@@ -11,8 +11,9 @@ Layout:
 from . import capi  # noqa: F401
 from .batch import (Batch, PoseCovariance, RelativeScale, ResidualReport, SolveResult, Triangulation, gate_sigma,  # noqa: F401
                     select_best)
-from .patches import PATTERN52, PatchCovariance, PatchTrack, image_pyramid, patch_covariance, patch_track  # noqa: F401
+from .patches import (PATTERN52, Keypoints, PatchCovariance, PatchTrack, detect_keypoints, image_pyramid,  # noqa: F401
+                      patch_covariance, patch_track)
 from .tracks import chain_scales  # noqa: F401
 
-__all__ = ["capi", "Batch", "PATTERN52", "PatchCovariance", "PatchTrack", "PoseCovariance", "RelativeScale", "ResidualReport", "SolveResult",
-           "Triangulation", "chain_scales", "gate_sigma", "image_pyramid", "patch_covariance", "patch_track", "select_best"]
+__all__ = ["capi", "Batch", "Keypoints", "PATTERN52", "PatchCovariance", "PatchTrack", "PoseCovariance", "RelativeScale", "ResidualReport", "SolveResult",
+           "Triangulation", "chain_scales", "detect_keypoints", "gate_sigma", "image_pyramid", "patch_covariance", "patch_track", "select_best"]

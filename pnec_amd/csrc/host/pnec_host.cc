@@ -523,6 +523,34 @@ PatchTracks TrackPatches(const Pyramid &tmpl, const Pyramid &next, const std::ve
   return out;
 }
 
+Keypoints DetectKeypoints(const void *image, pnec_hip_pixel_type pixel_type, int height, int width, int64_t pitch,
+                          const DetectOptions &options, const std::vector<std::array<double, 2>> *current) {
+  if (!image) throw std::invalid_argument("image is NULL");
+  if (options.grid < 8 || options.grid > 64) throw std::invalid_argument("grid must be 8 .. 64");
+  if (options.points_per_cell < 1 || options.points_per_cell > 4) throw std::invalid_argument("points_per_cell must be 1 .. 4");
+  if (height < options.grid || width < options.grid) throw std::invalid_argument("the image is smaller than one grid cell");
+  Keypoints out;
+  out.nx = width / options.grid;
+  out.ny = height / options.grid;
+  const size_t n_cells = (size_t)out.nx * (size_t)out.ny, cap = n_cells * (size_t)options.points_per_cell;
+  std::vector<int32_t> cell(n_cells, 0), score(cap, 0), index(cap, 0);
+  std::vector<std::array<double, 2>> pts(cap);
+  int64_t offsets[2] = {0, 0};
+  const int64_t n_cur = current ? (int64_t)current->size() : 0;
+  const int64_t cur_offsets[2] = {0, n_cur};
+  Check(pnec_hip_detect_keypoints(image, (int)pixel_type, 1, height, width, pitch > 0 ? pitch : width, options.grid,
+                                  options.points_per_cell, options.min_threshold, options.edge,
+                                  n_cur > 0 ? cur_offsets : nullptr, n_cur, n_cur > 0 ? (*current)[0].data() : nullptr,
+                                  cell.data(), offsets, pts[0].data(), score.data(), index.data(), PNEC_HIP_MEM_HOST,
+                                  optimization::SolverOptions().device, nullptr));
+  const size_t n = (size_t)offsets[1];
+  out.points.assign(pts.begin(), pts.begin() + (std::ptrdiff_t)n);
+  out.score.assign(score.begin(), score.begin() + (std::ptrdiff_t)n);
+  out.cell_index.assign(index.begin(), index.begin() + (std::ptrdiff_t)n);
+  out.cell.assign(cell.begin(), cell.end());
+  return out;
+}
+
 }  // namespace features
 
 // -------------------------------------------------------------------------------- optimization

@@ -203,6 +203,26 @@ PatchTracks TrackPatches(const Pyramid &tmpl, const Pyramid &next, const std::ve
                          const std::vector<std::array<double, 2>> *init_points = nullptr,
                          const std::vector<double> *init_angles = nullptr,
                          const std::vector<std::array<double, 2>> *pattern = nullptr);
+
+// Addition: the detector that feeds the tracker -- what KLTPatchOpticalFlow::addPoints (klt_patch_optical_flow.h:344-385)
+// gets from basalt's detectKeypoints [EXT]: grid FAST-9 corners of one uint8 / uint16 image, integer arithmetic --
+// pnec_hip_detect_keypoints, include/pnec_hip.h has the definition.  Keypoint ids and the track bookkeeping are the caller's.
+struct DetectOptions {
+  int grid = 30;                              // optical_flow_detection_grid_size (8 .. 64)
+  int points_per_cell = 1;                    // 1 .. 4; the reference passes 1
+  int min_threshold = 5;                      // the last threshold of the reference's loop
+  int edge = 19;                              // EDGE_THRESHOLD
+};
+struct Keypoints {
+  std::vector<std::array<double, 2>> points;  // x, y: what TrackPatches takes as `points`
+  std::vector<int> score, cell_index;         // cv::FAST's score (m - 1) and the cell cx * ny + cy, per point
+  std::vector<int> cell;                      // per cell: points produced, -1 for a cell a current point occupies
+  int nx = 0, ny = 0;
+};
+// `current` (nullptr: none): the points already tracked in this image; their cells are not searched
+Keypoints DetectKeypoints(const void *image, pnec_hip_pixel_type pixel_type, int height, int width, int64_t pitch,
+                          const DetectOptions &options = DetectOptions(),
+                          const std::vector<std::array<double, 2>> *current = nullptr);
 }  // namespace features
 
 namespace optimization {

@@ -376,6 +376,47 @@ py::tuple patch_track(py::array image1, py::array image2, arr points, int levels
   return py::make_tuple(P, A, Cv, D, S, Lv);
 }
 
+// (pts [N,2], score [N], cell_index [N], cell [n_cells]) of the grid FAST-9 corners of one uint8 / uint16 image
+py::tuple detect_keypoints(py::array image, int grid, int points_per_cell, int min_threshold, int edge, py::object current) {
+  if (image.ndim() != 2) throw std::invalid_argument("image must be [h,w]");
+  const pnec_hip_pixel_type type = pixel_type_of(image);
+  if (type == PNEC_HIP_PIXEL_F32) throw std::invalid_argument("image must be uint8 or uint16");
+  const py::ssize_t es = image.itemsize();
+  if (image.strides(1) != es || image.strides(0) % es != 0 || image.strides(0) < image.shape(1) * es)
+    throw std::invalid_argument("image rows must be contiguous (a row pitch is allowed)");
+  std::vector<std::array<double, 2>> cur;
+  if (!current.is_none()) {
+    arr c = current.cast<arr>();
+    if (c.ndim() != 2 || c.shape(1) != 2) throw std::invalid_argument("current must be [n,2]");
+    auto r = c.unchecked<2>();
+    cur.resize((size_t)c.shape(0));
+    for (py::ssize_t i = 0; i < c.shape(0); ++i) cur[(size_t)i] = {r(i, 0), r(i, 1)};
+  }
+  pnec::features::DetectOptions o;
+  o.grid = grid;
+  o.points_per_cell = points_per_cell;
+  o.min_threshold = min_threshold;
+  o.edge = edge;
+  const pnec::features::Keypoints k = pnec::features::DetectKeypoints(
+      image.data(), type, (int)image.shape(0), (int)image.shape(1), (int64_t)(image.strides(0) / es), o,
+      cur.empty() ? nullptr : &cur);
+  const py::ssize_t n = (py::ssize_t)k.points.size(), nc = (py::ssize_t)k.cell.size();
+  py::array_t<double> P({n, (py::ssize_t)2});
+  py::array_t<int32_t> S(n), I(n), Cl(nc);
+  auto pp = P.mutable_unchecked<2>();
+  auto ss = S.mutable_unchecked<1>();
+  auto ii = I.mutable_unchecked<1>();
+  auto cc = Cl.mutable_unchecked<1>();
+  for (py::ssize_t i = 0; i < n; ++i) {
+    pp(i, 0) = k.points[(size_t)i][0];
+    pp(i, 1) = k.points[(size_t)i][1];
+    ss(i) = k.score[(size_t)i];
+    ii(i) = k.cell_index[(size_t)i];
+  }
+  for (py::ssize_t i = 0; i < nc; ++i) cc(i) = k.cell[(size_t)i];
+  return py::make_tuple(P, S, I, Cl);
+}
+
 // PNEC::Solve for ONE frame pair through the overload asked for (pnec.cc:69-75, :77-124, :126-134,
 // :135-208): overload 0 = (bvs1, bvs2, covs, init), 1 = (+ inliers), 2 = (+ timing), 3 = (+ inliers,
 // timing).  Returns (pose 4x4, inliers or None, timing dict or None).
@@ -486,6 +527,11 @@ PYBIND11_MODULE(pypnec, m) {
         "pnec::features::TrackPatches (addition; device): (pts [N,2], angle [N], cov [N,3], dist2 [N], status [N], "
         "lost_level [N]) of the Pattern52 patches at `points` of image1 tracked into image2 and back, in double -- "
         "include/pnec_hip.h pnec_hip_patch_track");
+  m.def("detect_keypoints", &detect_keypoints, py::arg("image"), py::arg("grid") = 30, py::arg("points_per_cell") = 1,
+        py::arg("min_threshold") = 5, py::arg("edge") = 19, py::arg("current") = py::none(),
+        "pnec::features::DetectKeypoints (addition; device): (pts [N,2], score [N], cell_index [N], cell [n_cells]) -- the "
+        "grid FAST-9 corners of one uint8 / uint16 image, skipping the cells the `current` points [n,2] occupy -- "
+        "include/pnec_hip.h pnec_hip_detect_keypoints");
   m.def("patch_covariance", &patch_covariance, py::arg("image"), py::arg("points"), py::arg("scaling") = 10.0,
         "pnec::features::PatchCovariances (addition; device): (cov [N,3] as xx, xy, yy, status [N]) -- the 2x2 image "
         "covariance of the keypoints `points` [N,2] of one uint8 / uint16 / float32 image from their Pattern52 patches, in "

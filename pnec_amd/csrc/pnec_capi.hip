@@ -14,6 +14,7 @@
 
 #include "pnec_batch_kernels.hpp"
 #include "pnec_device.hpp"
+#include "pnec_detect.hpp"
 #include "pnec_front_shared.hpp"
 #include "pnec_internal.hpp"
 #include "pnec_patch_cov.hpp"
@@ -1564,6 +1565,109 @@ int pnec_hip_patch_track(const void *const *tmpl, const int64_t *tmpl_pitch, con
     if (int rc = stage.status()) return rc;
   }
   PNEC_HIP_TRY(launch_patch_track(pixel_type, a, stream));
+  return space == PNEC_HIP_MEM_HOST ? stage.finish() : 0;
+}
+
+// keypoint detection: pnec_detect.hip.  Staged like the patch covariances; the outputs travel up first, so that what
+// lies beyond out_offsets[n_images] comes back as the caller had it.
+int pnec_hip_detect_keypoints(const void *images, int pixel_type, int64_t n_images, int32_t height, int32_t width,
+                              int64_t pitch, int32_t grid, int32_t points_per_cell, int32_t min_threshold, int32_t edge,
+                              const int64_t *cur_offsets, int64_t n_cur, const double *cur_pts, int32_t *out_cell,
+                              int64_t *out_offsets, double *out_pts, int32_t *out_score, int32_t *out_cell_index,
+                              int space, int device, void *stream_) {
+  if (!images || !out_cell || !out_offsets || !out_pts)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "detect_keypoints: images, out_cell, out_offsets or out_pts is NULL");
+  if (pixel_type == PNEC_HIP_PIXEL_F32)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT,
+                "detect_keypoints: pixel_type F32 has no declared range to quantise to 8 bits (U8 or U16 only)");
+  if (pixel_type != PNEC_HIP_PIXEL_U8 && pixel_type != PNEC_HIP_PIXEL_U16)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "detect_keypoints: unknown pixel_type");
+  const size_t elem = pixel_type == PNEC_HIP_PIXEL_U8 ? 1 : 2;
+  if (grid < kDetectMinGrid || grid > kDetectMaxGrid)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "detect_keypoints: grid must be 8 .. 64");
+  if (points_per_cell < 1 || points_per_cell > kDetectMaxPerCell)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "detect_keypoints: points_per_cell must be 1 .. 4");
+  if (min_threshold < 0 || min_threshold > kDetectMaxThreshold)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "detect_keypoints: min_threshold must be 0 .. 254");
+  if (edge < 0) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "detect_keypoints: edge must be >= 0");
+  if (n_images < 1) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "detect_keypoints: n_images must be >= 1");
+  if (height < grid || width < grid)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "detect_keypoints: height and width must be at least one grid cell");
+  if (pitch < width) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "detect_keypoints: pitch (in elements) is below width");
+  if (n_cur < 0) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "detect_keypoints: n_cur must be >= 0");
+  if (cur_pts && !cur_offsets)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "detect_keypoints: cur_pts without cur_offsets");
+  if (cur_offsets && !cur_pts && n_cur > 0)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "detect_keypoints: cur_offsets and n_cur > 0 without cur_pts (NULL)");
+  if (space != PNEC_HIP_MEM_DEVICE && space != PNEC_HIP_MEM_HOST)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "detect_keypoints: bad memory space");
+  if (n_images > 0x7fffffffLL || (double)n_images * (double)height * (double)pitch * (double)elem > 9.0e18)
+    return fail(PNEC_HIP_ERR_UNSUPPORTED, "detect_keypoints: the images do not fit a 64-bit byte count");
+  const bool have_cur = cur_offsets && cur_pts && n_cur > 0;
+  if (space == PNEC_HIP_MEM_HOST && cur_offsets) {
+    bool ok = cur_offsets[0] == 0 && cur_offsets[n_images] == n_cur;
+    for (int64_t f = 0; ok && f < n_images; ++f) ok = cur_offsets[f] <= cur_offsets[f + 1];
+    if (!ok)
+      return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "detect_keypoints: cur_offsets must be non-decreasing from 0 to n_cur");
+  }
+  DetectArgs a{};
+  a.w = width;
+  a.h = height;
+  a.pitch = pitch;
+  a.n_images = n_images;
+  a.grid = grid;
+  a.per_cell = points_per_cell;
+  a.thr = min_threshold;
+  a.edge = edge;
+  a.nx = width / grid;
+  a.ny = height / grid;
+  a.x_start = (width % grid) / 2;
+  a.y_start = (height % grid) / 2;
+  a.n_cur = have_cur ? n_cur : 0;
+  const int64_t n_cells = (int64_t)a.nx * a.ny;
+  if (n_cells > 0x7fffffffLL / kDetectMaxPerCell || (double)n_images * (double)n_cells * kDetectMaxPerCell > 4.0e18)
+    return fail(PNEC_HIP_ERR_UNSUPPORTED, "detect_keypoints: too many cells");
+  const int64_t cap = n_images * n_cells * points_per_cell;
+  DeviceGuard guard(device);
+  if (!guard.ok) return fail(PNEC_HIP_ERR_HIP_RUNTIME, "hipSetDevice failed (no such device?)");
+  hipStream_t stream = (hipStream_t)stream_;
+  StageHolder holder;
+  holder.p.device = device;
+  HostStage stage(&holder.p, stream);
+  if (space == PNEC_HIP_MEM_DEVICE) {
+    a.images = images;
+    a.cur_offsets = have_cur ? cur_offsets : nullptr;
+    a.cur_pts = have_cur ? cur_pts : nullptr;
+    a.out_cell = out_cell;
+    a.out_offsets = out_offsets;
+    a.out_pts = out_pts;
+    a.out_score = out_score;
+    a.out_cell_index = out_cell_index;
+  } else {
+    const int64_t image_bytes = (int64_t)elem * ((n_images * (int64_t)height - 1) * pitch + width);
+    const int64_t C = have_cur ? n_cur : 0;
+    // stage: [pixels | cur_offsets F+1 (int64) | cur_pts 2C | offsets F+1 (int64) | pts 2 cap], ints [cell F n_cells |
+    // score cap | cell_index cap]
+    if (int rc = stage.reserve((image_bytes + 7) / 8 + (have_cur ? n_images + 1 + 2 * C : 0) + (n_images + 1) + 2 * cap,
+                               n_images * n_cells + 2 * cap))
+      return rc;
+    a.images = stage.up_bytes(images, image_bytes);
+    a.cur_offsets = have_cur ? stage.up(cur_offsets, n_images + 1) : nullptr;
+    a.cur_pts = have_cur ? stage.up(cur_pts, 2 * C) : nullptr;
+    a.out_cell = stage.out(out_cell, n_images * n_cells);
+    a.out_offsets = reinterpret_cast<int64_t *>(stage.out(reinterpret_cast<double *>(out_offsets), n_images + 1));
+    a.out_pts = stage.out(out_pts, 2 * cap);
+    a.out_score = stage.out(out_score, cap);
+    a.out_cell_index = stage.out(out_cell_index, cap);
+    if (int rc = stage.status()) return rc;
+    PNEC_HIP_TRY(hipMemcpyAsync(a.out_pts, out_pts, sizeof(double) * 2 * (size_t)cap, hipMemcpyHostToDevice, stream));
+    if (out_score)
+      PNEC_HIP_TRY(hipMemcpyAsync(a.out_score, out_score, sizeof(int32_t) * (size_t)cap, hipMemcpyHostToDevice, stream));
+    if (out_cell_index)
+      PNEC_HIP_TRY(hipMemcpyAsync(a.out_cell_index, out_cell_index, sizeof(int32_t) * (size_t)cap, hipMemcpyHostToDevice,
+                                  stream));
+  }
+  PNEC_HIP_TRY(launch_detect_keypoints(pixel_type, a, stream));
   return space == PNEC_HIP_MEM_HOST ? stage.finish() : 0;
 }
 

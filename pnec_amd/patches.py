@@ -8,7 +8,10 @@ claimed.
 
 Patch tracking: ``image_pyramid`` (``pnec_hip_image_pyramid_level``) and ``patch_track`` (``pnec_hip_patch_track``), the
 pyramidal SE(2) KLT iteration with its forward-backward check (klt_patch_optical_flow.h:195-342) -- the producer of the
-positions and of ``angle`` above.  Detection, keypoint ids and the view graph are not here.
+positions and of ``angle`` above.  Keypoint ids and the view graph are not here.
+
+Keypoint detection: ``detect_keypoints`` (``pnec_hip_detect_keypoints``), grid FAST-9 corners as
+KLTPatchOpticalFlow::addPoints gets them (klt_patch_optical_flow.h:344-385) -- the producer of ``tmpl_pts``.
 """
 from __future__ import annotations
 
@@ -27,6 +30,7 @@ TRACK_NAMES = {TRACK_OK: "ok", TRACK_BAD_TEMPLATE: "bad_template", TRACK_LOST_FO
                TRACK_LOST_BACKWARD: "lost_backward", TRACK_RECOVERED_TOO_FAR: "recovered_too_far"}
 TRACK_MAX_LEVELS = 8
 TRACK_NO_BACKWARD = 1
+DETECT_MIN_GRID, DETECT_MAX_GRID, DETECT_MAX_PER_CELL, DETECT_MAX_THRESHOLD = 8, 64, 4, 254
 
 
 def _pattern52() -> np.ndarray:
@@ -318,3 +322,85 @@ def patch_track(tmpl, next, tmpl_pts, offsets=None, prev=None, init_pts=None, in
         float(max_recovered_dist2), 0 if backward else TRACK_NO_BACKWARD, float(scaling), p(out["pts"]), p(out["angle"]),
         p(out["cov"]), p(out["dist2"]), p(out["status"]), p(out["lost_level"]), space, device, stream))
     return PatchTrack(out["pts"], out["angle"], out["cov"], out["dist2"], out["status"], out["lost_level"], offsets_d)
+
+
+@dataclass
+class Keypoints:
+    """pnec_hip_detect_keypoints' outputs; numpy or torch, matching the input.  Trimmed to offsets[-1] rows, or (the
+    `capacity` form) all F * n_cells * K rows of which the first offsets[-1] are written."""
+    offsets: object      # int64 [F+1]: points [offsets[f], offsets[f+1]) lie in image f
+    pts: object          # [N,2] x = column, y = row: integers in doubles, patch_track's tmpl_pts
+    score: object        # [N] int32: cv::FAST's score, m - 1
+    cell_index: object   # [N] int32: cx * ny + cy
+    cell: object         # [F, n_cells] int32: points per cell, -1 for a cell a current point occupies
+    grid_shape: tuple = None     # (nx, ny)
+    grid_origin: tuple = None    # (x_start, y_start)
+
+
+def detect_keypoints(images, grid: int = 30, points_per_cell: int = 1, min_threshold: int = 5, edge: int = 19,
+                     current=None, capacity: bool = False, out: Keypoints = None) -> Keypoints:
+    """Grid FAST-9 corners of `images` [F,h,w] (or one image [h,w]), uint8 or uint16 (read as v >> 8): in every
+    `grid` x `grid` cell that none of the `current` points lies in, the up to `points_per_cell` strongest corners above
+    `min_threshold` that are 3 x 3 maxima and at least `edge` pixels inside the image (include/pnec_hip.h has the
+    definition).  `current` = the tuple (offsets [F+1], pts [n,2]) or, for one image, pts [n,2] (an array or a tensor).
+
+    torch.cuda images -> everything stays on the device, asynchronous on torch's current stream, torch.cuda tensors out;
+    numpy (or CPU tensors) in -> staged, numpy out.  The arrays are trimmed to offsets[-1] rows: on the device THIS IS THE
+    ONE PLACE A SIZE IS READ BACK (one 8-byte copy that waits for the stream).  capacity=True returns the untrimmed arrays
+    -- F * n_cells * points_per_cell rows, the first offsets[-1] written -- without any wait, so a caller in a frame loop
+    never synchronises; `out` (a capacity-form result of the same shapes) is written in place of new arrays."""
+    images, on_device = _as_batch(images)
+    ptype = _ptype(images, on_device)
+    if ptype == PIXEL_F32:
+        raise TypeError("detect_keypoints takes uint8 or uint16 images: a float image has no declared range to quantise")
+    F, h, w = (int(x) for x in images.shape)
+    G, K = int(grid), int(points_per_cell)
+    if not DETECT_MIN_GRID <= G <= DETECT_MAX_GRID:
+        raise ValueError(f"grid must be {DETECT_MIN_GRID} .. {DETECT_MAX_GRID}")
+    if not 1 <= K <= DETECT_MAX_PER_CELL:
+        raise ValueError(f"points_per_cell must be 1 .. {DETECT_MAX_PER_CELL}")
+    if h < G or w < G:
+        raise ValueError("the images must be at least one grid cell in height and width")
+    nx, ny = w // G, h // G
+    n_cells, cap = nx * ny, F * nx * ny * K
+    space, device, stream = _where(images, on_device)
+    if on_device:
+        import torch
+        dev = images.device
+        as_in = lambda a, dt: a.to(device=dev, dtype=dt).contiguous() if _is_torch(a) else \
+            torch.as_tensor(np.array(a), dtype=dt, device=dev)
+        F64, I64 = torch.float64, torch.int64
+        p = lambda a: None if a is None else a.data_ptr()
+        new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        I32 = torch.int32
+    else:
+        as_in = lambda a, dt: np.ascontiguousarray(a.cpu().numpy() if _is_torch(a) else a, dtype=dt)
+        F64, I64, I32 = np.float64, np.int64, np.int32
+        p = lambda a: None if a is None else a.ctypes.data
+        new = lambda shape, dt: np.empty(shape, dtype=dt)
+    cur_offsets = cur_pts = None
+    n_cur = 0
+    if current is not None:
+        if isinstance(current, tuple) and len(current) == 2:
+            cur_offsets, cur_pts = as_in(current[0], I64), as_in(current[1], F64)
+        else:
+            if F != 1:
+                raise ValueError("current points of several images come as (offsets, pts)")
+            cur_pts = as_in(current, F64)
+            cur_offsets = as_in(np.array([0, int(cur_pts.shape[0])], dtype=np.int64), I64)
+        if cur_pts.ndim != 2 or cur_pts.shape[1] != 2 or tuple(cur_offsets.shape) != (F + 1,):
+            raise ValueError("current must be (offsets [F+1], pts [n,2])")
+        n_cur = int(cur_pts.shape[0])
+    if out is None:
+        out = Keypoints(new((F + 1,), I64), new((cap, 2), F64), new((cap,), I32), new((cap,), I32), new((F, n_cells), I32))
+    elif (tuple(out.offsets.shape), tuple(out.pts.shape), tuple(out.score.shape), tuple(out.cell_index.shape),
+          tuple(out.cell.shape)) != ((F + 1,), (cap, 2), (cap,), (cap,), (F, n_cells)):
+        raise ValueError("`out` must be a capacity-form result of the same images, grid and points_per_cell")
+    capi.check(capi.lib().pnec_hip_detect_keypoints(
+        p(images), ptype, F, h, w, _pitch(images, on_device), G, K, int(min_threshold), int(edge), p(cur_offsets), n_cur,
+        p(cur_pts), p(out.cell), p(out.offsets), p(out.pts), p(out.score), p(out.cell_index), space, device, stream))
+    shape, origin = (nx, ny), ((w % G) // 2, (h % G) // 2)
+    if capacity:
+        return Keypoints(out.offsets, out.pts, out.score, out.cell_index, out.cell, shape, origin)
+    n = int(out.offsets[-1])     # (on the device: the read-back)
+    return Keypoints(out.offsets, out.pts[:n], out.score[:n], out.cell_index[:n], out.cell, shape, origin)
