@@ -458,6 +458,72 @@ int select_finish(pnec_hip_problem *src, hipStream_t stream, pnec_hip_problem *d
 
 }  // namespace pnec_hip
 
+// ---- argument checks several entry points share; `name` is the entry point's, for the message ----------------------
+namespace {
+
+// prefix: "name: ", or "" where the entry point reports this one bare
+int check_space(const std::string &prefix, int space) {
+  if (space != PNEC_HIP_MEM_DEVICE && space != PNEC_HIP_MEM_HOST)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, prefix + "bad memory space");
+  return 0;
+}
+
+// the batch and the poses of a call that works on (pair, pose) slots
+int check_pose_args(const char *name, const pnec_hip_problem *p, const double *q, const double *t, int32_t n_hyp) {
+  const std::string pre = std::string(name) + ": ";
+  if (!p) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "problem is NULL");
+  if (!q || !t) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "q or t is NULL");
+  if (n_hyp < 1) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "n_hyp must be >= 1");
+  return 0;
+}
+
+// *S = the (pair, pose) slots of the call; 0: nothing to do.  what: "poses" / "solves"
+int pose_slots(const pnec_hip_problem *p, int32_t n_hyp, const char *what, int64_t *S) {
+  *S = p->n_pairs * (int64_t)n_hyp;
+  if (*S > 0x7fffffffLL) return fail(PNEC_HIP_ERR_UNSUPPORTED, std::string("more than 2^31-1 ") + what + " in one call");
+  return 0;
+}
+
+// (kernels that address a pair's planes with 32-bit byte offsets)
+int check_planes_fit(const char *name, const pnec_hip_problem *b) {
+  if ((int64_t)num_components(b->mode) * (((int64_t)b->n_max + kWave - 1) & ~(int64_t)(kWave - 1)) * 8 > 0xffffffffLL)
+    return fail(PNEC_HIP_ERR_UNSUPPORTED, std::string(name) + ": a pair of 4 GiB of planes or more");
+  return 0;
+}
+
+size_t pixel_bytes(int pixel_type) {
+  switch (pixel_type) {
+    case PNEC_HIP_PIXEL_U8: return 1;
+    case PNEC_HIP_PIXEL_U16: return 2;
+    case PNEC_HIP_PIXEL_F32: return 4;
+    default: return 0;
+  }
+}
+
+// n_images images of `rows` rows, `pitch` elements apart, as one block
+int check_images_fit(const char *name, int64_t n_images, int64_t rows, int64_t pitch, size_t elem) {
+  if (n_images > 0x7fffffffLL || (double)n_images * (double)rows * (double)pitch * (double)elem > 9.0e18)
+    return fail(PNEC_HIP_ERR_UNSUPPORTED, std::string(name) + ": the images do not fit a 64-bit byte count");
+  return 0;
+}
+// (its bytes: the last row of the last image need not be padded)
+int64_t image_block_bytes(size_t elem, int64_t n_images, int64_t rows, int64_t pitch, int64_t width) {
+  return (int64_t)elem * ((n_images * rows - 1) * pitch + width);
+}
+
+// HOST space only (the array is read): offsets[0 .. n] run from 0 to total without a step down
+int check_offsets(const char *name, const char *array, const int64_t *offsets, int64_t n, int64_t total,
+                  const char *total_name) {
+  bool ok = offsets[0] == 0 && offsets[n] == total;
+  for (int64_t f = 0; ok && f < n; ++f) ok = offsets[f] <= offsets[f + 1];
+  if (!ok)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT,
+                std::string(name) + ": " + array + " must be non-decreasing from 0 to " + total_name);
+  return 0;
+}
+
+}  // namespace
+
 // ==========================================================================================
 extern "C" {
 
@@ -795,8 +861,7 @@ int pnec_hip_solve(pnec_hip_problem *p, const double *init_q, const double *init
   if (!hyp_t) n_hyp = 1;
   if (n_hyp < 1) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "n_hyp must be >= 1");
   if (!hyp_t && !init_t) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "init_t and hyp_t are both NULL");
-  if (space != PNEC_HIP_MEM_DEVICE && space != PNEC_HIP_MEM_HOST)
-    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "bad memory space");
+  if (int rc = check_space("", space)) return rc;
   pnec_hip_options opt;
   if (opt_in)
     opt = *opt_in;
@@ -811,15 +876,14 @@ int pnec_hip_solve(pnec_hip_problem *p, const double *init_q, const double *init
     opt.waves_per_pair = kStreamWaves;
     opt.lds_corr_per_lane = 0;
   }
-  const int64_t S = p->n_pairs * (int64_t)n_hyp;
+  int64_t S;
+  if (int rc = pose_slots(p, n_hyp, "solves", &S)) return rc;
   if (S == 0) return 0;
-  if (S > 0x7fffffffLL) return fail(PNEC_HIP_ERR_UNSUPPORTED, "more than 2^31-1 solves in one call");
   Geometry g;
   if (int rc = choose_geometry(p, &opt, &g)) return rc;
 
-  DeviceGuard guard(p->device);
   hipStream_t stream = (hipStream_t)stream_;
-  HostStage stage(p, stream);
+  CallArrays io(p, space, stream);
   SolveArgs a;
   std::memset(&a, 0, sizeof(a));
   a.data = p->d_data;
@@ -835,30 +899,17 @@ int pnec_hip_solve(pnec_hip_problem *p, const double *init_q, const double *init
     if (int rc = solve_work_buffer(p->device, &a.work)) return rc;
   }
 
-  if (space == PNEC_HIP_MEM_DEVICE) {
-    a.init_q = init_q;
-    a.init_t = init_t;
-    a.hyp_t = hyp_t;
-    a.out_q = out_q;
-    a.out_t = out_t;
-    a.out_cost = out_cost;
-    a.out_iterations = out_iterations;
-    a.out_status = out_status;
-  } else {
-    // stage: [init_q 4P | init_t 3P | hyp_t 3S | out_q 4S | out_t 3S | out_cost S], ints [it S | st S]; every
-    // output is staged, wanted or not
-    const int64_t P = p->n_pairs;
-    if (int rc = stage.reserve(7 * P + 11 * S, 2 * S)) return rc;
-    a.init_q = stage.up(init_q, 4 * P);
-    a.init_t = stage.up(init_t, 3 * P);
-    a.hyp_t = stage.up(hyp_t, 3 * S);
-    a.out_q = stage.out(out_q, 4 * S, /*keep*/ true);
-    a.out_t = stage.out(out_t, 3 * S, /*keep*/ true);
-    a.out_cost = stage.out(out_cost, S, /*keep*/ true);
-    a.out_iterations = stage.out(out_iterations, S, /*keep*/ true);
-    a.out_status = stage.out(out_status, S, /*keep*/ true);
-    if (int rc = stage.status()) return rc;
-  }
+  // (every output is staged, wanted or not)
+  const int64_t P = p->n_pairs;
+  io.in(a.init_q, init_q, 4 * P);
+  io.in(a.init_t, init_t, 3 * P);
+  io.in(a.hyp_t, hyp_t, 3 * S);
+  io.out(a.out_q, out_q, 4 * S, kKeep);
+  io.out(a.out_t, out_t, 3 * S, kKeep);
+  io.out(a.out_cost, out_cost, S, kKeep);
+  io.out(a.out_iterations, out_iterations, S, kKeep);
+  io.out(a.out_status, out_status, S, kKeep);
+  if (int rc = io.commit()) return rc;
 
   // several hypotheses per pair on a several-wavefront geometry: the block-per-(pair, group of hypotheses) form -- the
   // pair's payload loaded once per group, one LM step for the whole group (bit-identical results).  PNEC_SOLVE_GROUPS=0
@@ -947,7 +998,7 @@ int pnec_hip_solve(pnec_hip_problem *p, const double *init_q, const double *init
   }
   if (e != hipSuccess) return fail_hip(e, "lm_solve_kernel launch");
 
-  return space == PNEC_HIP_MEM_HOST ? stage.finish() : 0;
+  return io.finish();
 }
 
 int pnec_hip_select_best(int64_t n_pairs, int32_t n_hyp, const double *cost, int32_t *best_index,
@@ -993,90 +1044,66 @@ int pnec_hip_cost_function(pnec_hip_problem *p, const double *q, const double *t
   if (p->mode != PNEC_HIP_MODE_TARGET)
     return fail(PNEC_HIP_ERR_UNSUPPORTED, "cost_function needs a TARGET-mode problem");
   if (p->n_pairs == 0) return 0;
-  DeviceGuard guard(p->device);
   hipStream_t stream = (hipStream_t)stream_;
-  const double *d_q = q, *d_t = t;
-  double *d_out = out;
+  const double *d_q, *d_t;
+  double *d_out;
   const int64_t P = p->n_pairs;
-  HostStage stage(p, stream);
-  if (space == PNEC_HIP_MEM_HOST) {
-    if (int rc = stage.reserve(8 * P, 0)) return rc;
-    d_q = stage.up(q, 4 * P);
-    d_t = stage.up(t, 3 * P);
-    d_out = stage.out(out, P);
-    if (int rc = stage.status()) return rc;
-  }
+  CallArrays io(p, space, stream);
+  io.in(d_q, q, 4 * P);
+  io.in(d_t, t, 3 * P);
+  io.out(d_out, out, P);
+  if (int rc = io.commit()) return rc;
   PNEC_HIP_TRY(launch_cost_function(P, p->d_data, p->d_block_offset, p->d_count, d_q, d_t, d_out, stream));
-  return space == PNEC_HIP_MEM_HOST ? stage.finish() : 0;
+  return io.finish();
 }
 
 // J'J, its lifted inverse, J'r and the cost of every (pair, pose) slot: pnec_pose_cov.hip
 int pnec_hip_pose_covariance(pnec_hip_problem *p, const double *q, const double *t, int32_t n_hyp, double reg,
                              double *out_info, double *out_cov, double *out_grad, double *out_cost,
                              int32_t *out_status, int space, void *stream_) {
-  if (!p) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "pose_covariance: problem is NULL");
-  if (!q || !t) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "pose_covariance: q or t is NULL");
-  if (n_hyp < 1) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "pose_covariance: n_hyp must be >= 1");
+  if (int rc = check_pose_args("pose_covariance", p, q, t, n_hyp)) return rc;
   if (!out_info && !out_cov && !out_grad && !out_cost && !out_status)
     return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "pose_covariance: every output is NULL");
-  if (space != PNEC_HIP_MEM_DEVICE && space != PNEC_HIP_MEM_HOST)
-    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "bad memory space");
-  const int64_t S = p->n_pairs * (int64_t)n_hyp;
+  if (int rc = check_space("", space)) return rc;
+  int64_t S;
+  if (int rc = pose_slots(p, n_hyp, "poses", &S)) return rc;
   if (S == 0) return 0;
-  if (S > 0x7fffffffLL) return fail(PNEC_HIP_ERR_UNSUPPORTED, "more than 2^31-1 poses in one call");
-  DeviceGuard guard(p->device);
   hipStream_t stream = (hipStream_t)stream_;
-  HostStage stage(p, stream);
+  CallArrays io(p, space, stream);
   PoseCovArgs a;
   a.data = p->d_data;
   a.block_offset = p->d_block_offset;
   a.count = p->d_count;
   a.n_hyp = n_hyp;
   a.reg = reg;
-  if (space == PNEC_HIP_MEM_DEVICE) {
-    a.q = q;
-    a.t = t;
-    a.out_info = out_info;
-    a.out_cov = out_cov;
-    a.out_grad = out_grad;
-    a.out_cost = out_cost;
-    a.out_status = out_status;
-  } else {
-    // stage: [q 4S | t 3S | cov 36S | info 15S | grad 5S | cost S], ints [status S]
-    if (int rc = stage.reserve(64 * S, S)) return rc;
-    a.q = stage.up(q, 4 * S);
-    a.t = stage.up(t, 3 * S);
-    a.out_cov = stage.out(out_cov, 36 * S);
-    a.out_info = stage.out(out_info, 15 * S);
-    a.out_grad = stage.out(out_grad, 5 * S);
-    a.out_cost = stage.out(out_cost, S);
-    a.out_status = stage.out(out_status, S);
-    if (int rc = stage.status()) return rc;
-  }
+  io.in(a.q, q, 4 * S);
+  io.in(a.t, t, 3 * S);
+  io.out(a.out_cov, out_cov, 36 * S);
+  io.out(a.out_info, out_info, 15 * S);
+  io.out(a.out_grad, out_grad, 5 * S);
+  io.out(a.out_cost, out_cost, S);
+  io.out(a.out_status, out_status, S);
+  if (int rc = io.commit()) return rc;
   // n_max of a batch whose sizes still live on the device (select) is the source's: an upper bound, which is all the
   // block size needs (the wavefronts a pair uses follow from its own count)
   PNEC_HIP_TRY(launch_pose_covariance(p->mode, S, cov_waves(p->n_max), a, stream));
-  return space == PNEC_HIP_MEM_HOST ? stage.finish() : 0;
+  return io.finish();
 }
 
 // r_i, its variance and the gate's verdict per correspondence, chi-square sums per (pair, pose) slot: pnec_residuals.hip
 int pnec_hip_residuals(pnec_hip_problem *p, const double *q, const double *t, int32_t n_hyp, double reg, double gate,
                        double *out_residual, double *out_variance, uint8_t *out_mask, double *out_chi2,
                        double *out_gated_chi2, int32_t *out_gated_count, double *out_max_abs, int space, void *stream_) {
-  if (!p) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "residuals: problem is NULL");
-  if (!q || !t) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "residuals: q or t is NULL");
-  if (n_hyp < 1) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "residuals: n_hyp must be >= 1");
+  if (int rc = check_pose_args("residuals", p, q, t, n_hyp)) return rc;
   if (!(gate >= 0.0)) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "residuals: gate must be >= 0 (sigmas; +inf allowed)");
   if (!out_residual && !out_variance && !out_mask && !out_chi2 && !out_gated_chi2 && !out_gated_count && !out_max_abs)
     return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "residuals: every output is NULL");
-  if (space != PNEC_HIP_MEM_DEVICE && space != PNEC_HIP_MEM_HOST)
-    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "residuals: bad memory space");
-  const int64_t S = p->n_pairs * (int64_t)n_hyp;
+  if (int rc = check_space("residuals: ", space)) return rc;
+  int64_t S;
+  if (int rc = pose_slots(p, n_hyp, "poses", &S)) return rc;
   if (S == 0) return 0;
-  if (S > 0x7fffffffLL) return fail(PNEC_HIP_ERR_UNSUPPORTED, "more than 2^31-1 poses in one call");
-  DeviceGuard guard(p->device);
   hipStream_t stream = (hipStream_t)stream_;
-  HostStage stage(p, stream);
+  CallArrays io(p, space, stream);
   ResidualArgs a;
   a.data = p->d_data;
   a.block_offset = p->d_block_offset;
@@ -1085,38 +1112,25 @@ int pnec_hip_residuals(pnec_hip_problem *p, const double *q, const double *t, in
   a.n_hyp = n_hyp;
   a.reg = reg;
   a.gate = gate;
-  if (space == PNEC_HIP_MEM_DEVICE) {
-    // (a batch whose sizes still live on the device needs no host-side number here: the kernel reads its offsets)
-    a.q = q;
-    a.t = t;
-    a.out_residual = out_residual;
-    a.out_variance = out_variance;
-    a.out_mask = out_mask;
-    a.out_chi2 = out_chi2;
-    a.out_gated_chi2 = out_gated_chi2;
-    a.out_gated_count = out_gated_count;
-    a.out_max_abs = out_max_abs;
-  } else {
-    // the lengths of the caller's arrays are the batch's own totals: a batch made by select waits for its sizes here
+  // HOST space: the lengths of the caller's arrays are the batch's own totals, so a batch made by select waits for its
+  // sizes here.  (DEVICE space needs no host-side number: the kernel reads the batch's offsets.)
+  if (io.host())
     if (int rc = materialize(p)) return rc;
-    const int64_t M = p->n_corr * (int64_t)n_hyp;   // entries of a per-correspondence array
-    // stage: [q 4S | t 3S | chi2 S | gated chi2 S | max S | residual M | variance M | mask M bytes], ints [count S]
-    if (int rc = stage.reserve(10 * S + 2 * M + (M + 7) / 8, S)) return rc;
-    a.q = stage.up(q, 4 * S);
-    a.t = stage.up(t, 3 * S);
-    a.out_chi2 = stage.out(out_chi2, S);
-    a.out_gated_chi2 = stage.out(out_gated_chi2, S);
-    a.out_max_abs = stage.out(out_max_abs, S);
-    a.out_residual = stage.out(out_residual, M);
-    a.out_variance = stage.out(out_variance, M);
-    a.out_mask = stage.out(out_mask, M);
-    a.out_gated_count = stage.out(out_gated_count, S);
-    if (int rc = stage.status()) return rc;
-  }
+  const int64_t M = p->n_corr * (int64_t)n_hyp;   // entries of a per-correspondence array
+  io.in(a.q, q, 4 * S);
+  io.in(a.t, t, 3 * S);
+  io.out(a.out_chi2, out_chi2, S);
+  io.out(a.out_gated_chi2, out_gated_chi2, S);
+  io.out(a.out_max_abs, out_max_abs, S);
+  io.out(a.out_residual, out_residual, M);
+  io.out(a.out_variance, out_variance, M);
+  io.out(a.out_mask, out_mask, M);
+  io.out(a.out_gated_count, out_gated_count, S);
+  if (int rc = io.commit()) return rc;
   // n_max of a batch whose sizes still live on the device (select) is the source's: an upper bound, which is all the
   // block size needs (the wavefronts a pair uses follow from its own count)
   PNEC_HIP_TRY(launch_residuals(p->mode, S, cov_waves(p->n_max), a, stream));
-  return space == PNEC_HIP_MEM_HOST ? stage.finish() : 0;
+  return io.finish();
 }
 
 // depths, points, parallax and depth variance per correspondence, the cheirality vote per (pair, pose) slot:
@@ -1125,24 +1139,18 @@ int pnec_hip_triangulate(pnec_hip_problem *p, const double *q, const double *t, 
                          double *out_point, double *out_depth1, double *out_depth2, double *out_parallax,
                          double *out_depth1_var, uint8_t *out_front, int32_t *out_n_front, int32_t *out_n_back,
                          int32_t *out_sign, double *out_t_oriented, double *out_parallax_mean, int space, void *stream_) {
-  if (!p) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "triangulate: problem is NULL");
-  if (!q || !t) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "triangulate: q or t is NULL");
-  if (n_hyp < 1) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "triangulate: n_hyp must be >= 1");
+  if (int rc = check_pose_args("triangulate", p, q, t, n_hyp)) return rc;
   if (flags & ~PNEC_HIP_TRI_ORIENT) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "triangulate: unknown bit in flags");
   if (!out_point && !out_depth1 && !out_depth2 && !out_parallax && !out_depth1_var && !out_front && !out_n_front &&
       !out_n_back && !out_sign && !out_t_oriented && !out_parallax_mean)
     return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "triangulate: every output is NULL");
-  if (space != PNEC_HIP_MEM_DEVICE && space != PNEC_HIP_MEM_HOST)
-    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "triangulate: bad memory space");
-  const int64_t S = p->n_pairs * (int64_t)n_hyp;
+  if (int rc = check_space("triangulate: ", space)) return rc;
+  int64_t S;
+  if (int rc = pose_slots(p, n_hyp, "poses", &S)) return rc;
   if (S == 0) return 0;
-  if (S > 0x7fffffffLL) return fail(PNEC_HIP_ERR_UNSUPPORTED, "more than 2^31-1 poses in one call");
-  // (the kernel addresses a pair's planes with 32-bit byte offsets)
-  if ((int64_t)num_components(p->mode) * (((int64_t)p->n_max + kWave - 1) & ~(int64_t)(kWave - 1)) * 8 > 0xffffffffLL)
-    return fail(PNEC_HIP_ERR_UNSUPPORTED, "triangulate: a pair of 4 GiB of planes or more");
-  DeviceGuard guard(p->device);
+  if (int rc = check_planes_fit("triangulate", p)) return rc;
   hipStream_t stream = (hipStream_t)stream_;
-  HostStage stage(p, stream);
+  CallArrays io(p, space, stream);
   TriangulateArgs a;
   a.data = p->d_data;
   a.block_offset = p->d_block_offset;
@@ -1150,47 +1158,29 @@ int pnec_hip_triangulate(pnec_hip_problem *p, const double *q, const double *t, 
   a.offsets = p->d_offsets;
   a.n_hyp = n_hyp;
   a.flags = flags;
-  if (space == PNEC_HIP_MEM_DEVICE) {
-    // (a batch whose sizes still live on the device needs no host-side number here: the kernel reads its offsets)
-    a.q = q;
-    a.t = t;
-    a.out_point = out_point;
-    a.out_depth1 = out_depth1;
-    a.out_depth2 = out_depth2;
-    a.out_parallax = out_parallax;
-    a.out_depth1_var = out_depth1_var;
-    a.out_front = out_front;
-    a.out_n_front = out_n_front;
-    a.out_n_back = out_n_back;
-    a.out_sign = out_sign;
-    a.out_t_oriented = out_t_oriented;
-    a.out_parallax_mean = out_parallax_mean;
-  } else {
-    // the lengths of the caller's arrays are the batch's own totals: a batch made by select waits for its sizes here
+  // HOST space: the lengths of the caller's arrays are the batch's own totals, so a batch made by select waits for its
+  // sizes here.  (DEVICE space needs no host-side number: the kernel reads the batch's offsets.)
+  if (io.host())
     if (int rc = materialize(p)) return rc;
-    const int64_t M = p->n_corr * (int64_t)n_hyp;   // entries of a per-correspondence array
-    // stage: [q 4S | t 3S | t_oriented 3S | parallax mean S | point 3M | depth1 M | depth2 M | parallax M | variance M |
-    //         front M bytes], ints [n_front S | n_back S | sign S]
-    if (int rc = stage.reserve(11 * S + 7 * M + (M + 7) / 8, 3 * S)) return rc;
-    a.q = stage.up(q, 4 * S);
-    a.t = stage.up(t, 3 * S);
-    a.out_t_oriented = stage.out(out_t_oriented, 3 * S);
-    a.out_parallax_mean = stage.out(out_parallax_mean, S);
-    a.out_point = stage.out(out_point, 3 * M);
-    a.out_depth1 = stage.out(out_depth1, M);
-    a.out_depth2 = stage.out(out_depth2, M);
-    a.out_parallax = stage.out(out_parallax, M);
-    a.out_depth1_var = stage.out(out_depth1_var, M);
-    a.out_front = stage.out(out_front, M);
-    a.out_n_front = stage.out(out_n_front, S);
-    a.out_n_back = stage.out(out_n_back, S);
-    a.out_sign = stage.out(out_sign, S);
-    if (int rc = stage.status()) return rc;
-  }
+  const int64_t M = p->n_corr * (int64_t)n_hyp;   // entries of a per-correspondence array
+  io.in(a.q, q, 4 * S);
+  io.in(a.t, t, 3 * S);
+  io.out(a.out_t_oriented, out_t_oriented, 3 * S);
+  io.out(a.out_parallax_mean, out_parallax_mean, S);
+  io.out(a.out_point, out_point, 3 * M);
+  io.out(a.out_depth1, out_depth1, M);
+  io.out(a.out_depth2, out_depth2, M);
+  io.out(a.out_parallax, out_parallax, M);
+  io.out(a.out_depth1_var, out_depth1_var, M);
+  io.out(a.out_front, out_front, M);
+  io.out(a.out_n_front, out_n_front, S);
+  io.out(a.out_n_back, out_n_back, S);
+  io.out(a.out_sign, out_sign, S);
+  if (int rc = io.commit()) return rc;
   // n_max of a batch whose sizes still live on the device (select) is the source's: an upper bound, which is all the
   // block size needs (the wavefronts a pair uses follow from its own count)
   PNEC_HIP_TRY(launch_triangulate(p->mode, S, cov_waves(p->n_max), a, stream));
-  return space == PNEC_HIP_MEM_HOST ? stage.finish() : 0;
+  return io.finish();
 }
 
 // the ratio of every pair's baseline to its previous pair's from the tracks they share, and three exact order
@@ -1207,20 +1197,16 @@ int pnec_hip_relative_scale(pnec_hip_problem *cur, pnec_hip_problem *prev, const
     return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "relative_scale: min_parallax must be >= 0 and finite (radians)");
   if (!out_ratio && !out_used && !out_scale && !out_n_linked && !out_n_used)
     return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "relative_scale: every output is NULL");
-  if (space != PNEC_HIP_MEM_DEVICE && space != PNEC_HIP_MEM_HOST)
-    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "relative_scale: bad memory space");
+  if (int rc = check_space("relative_scale: ", space)) return rc;
   if (cur->device != prev->device)
     return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "relative_scale: cur and prev live on different devices");
   const int64_t P = cur->n_pairs, Pp = prev->n_pairs;
   if (P == 0) return 0;
   if (P > 0x7fffffffLL) return fail(PNEC_HIP_ERR_UNSUPPORTED, "more than 2^31-1 pairs in one call");
-  // (the kernel addresses a pair's planes with 32-bit byte offsets, on either side)
-  for (const pnec_hip_problem *b : {(const pnec_hip_problem *)cur, (const pnec_hip_problem *)prev})
-    if ((int64_t)num_components(b->mode) * (((int64_t)b->n_max + kWave - 1) & ~(int64_t)(kWave - 1)) * 8 > 0xffffffffLL)
-      return fail(PNEC_HIP_ERR_UNSUPPORTED, "relative_scale: a pair of 4 GiB of planes or more");
-  DeviceGuard guard(cur->device);
+  if (int rc = check_planes_fit("relative_scale", cur)) return rc;
+  if (int rc = check_planes_fit("relative_scale", prev)) return rc;
   hipStream_t stream = (hipStream_t)stream_;
-  HostStage stage(cur, stream);
+  CallArrays io(cur, space, stream);
   RelativeScaleArgs a;
   a.data = cur->d_data;
   a.block_offset = cur->d_block_offset;
@@ -1234,69 +1220,43 @@ int pnec_hip_relative_scale(pnec_hip_problem *cur, pnec_hip_problem *prev, const
   const double sn = std::sin(min_parallax);
   a.sin2_min = min_parallax >= 1.5707963267948966 ? 2.0 : sn * sn;
   a.gate_a10 = min_parallax > 0.0 ? 1 : 0;
-  if (space == PNEC_HIP_MEM_DEVICE) {
-    // (a batch whose sizes still live on the device needs no host-side number here: the kernel reads its offsets; n_corr
-    // of such a batch is the source's, an upper bound)
-    a.prev_pair = prev_pair;
-    a.link = link;
-    a.q = q_cur;
-    a.t = t_cur;
-    a.q_prev = q_prev;
-    a.t_prev = t_prev;
-    a.ratio = out_ratio;
-    if (!out_ratio) {
-      const int64_t need = std::max<int64_t>(cur->n_corr, 1);
-      if (need > cur->ratio_doubles) {
-        if (cur->d_ratio) (void)dev_free(cur->d_ratio);
-        cur->d_ratio = nullptr;
-        cur->ratio_doubles = 0;
-        PNEC_HIP_TRY(dev_alloc(&cur->d_ratio, sizeof(double) * (size_t)need));
-        cur->ratio_doubles = need;
-      }
-      a.ratio = cur->d_ratio;
-    }
-    a.out_used = out_used;
-    a.out_scale = out_scale;
-    a.out_n_linked = out_n_linked;
-    a.out_n_used = out_n_used;
-  } else {
-    // the lengths of the caller's arrays are the batch's own totals: a batch made by select waits for its sizes here
+  // HOST space: the lengths of the caller's arrays are the batch's own totals, so a batch made by select waits for its
+  // sizes here.  (DEVICE space needs no host-side number: the kernel reads the batch's offsets, and n_corr of such a batch
+  // is the source's, an upper bound.)
+  if (io.host())
     if (int rc = materialize(cur)) return rc;
-    const int64_t M = cur->n_corr;
-    // stage: [q 4P | t 3P | q_prev 4Pp | t_prev 3Pp | prev_pair P (int64) | scale 3P | ratio M | used M bytes],
-    //        ints [link M | n_linked P | n_used P]; the ratios are staged whether or not the caller wants them
-    if (int rc = stage.reserve(11 * P + 7 * Pp + M + (M + 7) / 8, M + 2 * P)) return rc;
-    a.q = stage.up(q_cur, 4 * P);
-    a.t = stage.up(t_cur, 3 * P);
-    a.q_prev = stage.up(q_prev, 4 * Pp);
-    a.t_prev = stage.up(t_prev, 3 * Pp);
-    a.prev_pair = stage.up(prev_pair, P);
-    a.out_scale = stage.out(out_scale, 3 * P);
-    a.ratio = stage.out(out_ratio, M, true);
-    a.out_used = stage.out(out_used, M);
-    a.link = stage.up(link, M);
-    a.out_n_linked = stage.out(out_n_linked, P);
-    a.out_n_used = stage.out(out_n_used, P);
-    if (int rc = stage.status()) return rc;
+  const int64_t M = cur->n_corr;
+  io.in(a.q, q_cur, 4 * P);
+  io.in(a.t, t_cur, 3 * P);
+  io.in(a.q_prev, q_prev, 4 * Pp);
+  io.in(a.t_prev, t_prev, 3 * Pp);
+  io.in(a.prev_pair, prev_pair, P);
+  io.out(a.out_scale, out_scale, 3 * P);
+  io.out(a.ratio, out_ratio, M, kKeep);   // (the pass writes the ratios whether or not the caller wants them)
+  io.out(a.out_used, out_used, M);
+  io.in(a.link, link, M);
+  io.out(a.out_n_linked, out_n_linked, P);
+  io.out(a.out_n_used, out_n_used, P);
+  if (int rc = io.commit()) return rc;
+  if (!io.host() && !out_ratio) {   // DEVICE space without out_ratio: the batch keeps the ratios between the pass and the selection
+    const int64_t need = std::max<int64_t>(M, 1);
+    if (need > cur->ratio_doubles) {
+      if (cur->d_ratio) (void)dev_free(cur->d_ratio);
+      cur->d_ratio = nullptr;
+      cur->ratio_doubles = 0;
+      PNEC_HIP_TRY(dev_alloc(&cur->d_ratio, sizeof(double) * (size_t)need));
+      cur->ratio_doubles = need;
+    }
+    a.ratio = cur->d_ratio;
   }
   // n_max of a batch whose sizes still live on the device (select) is the source's: an upper bound, which is all the
   // block size needs (the wavefronts a pair uses follow from its own count)
   PNEC_HIP_TRY(launch_relative_scale(P, cov_waves(cur->n_max), a, stream));
-  return space == PNEC_HIP_MEM_HOST ? stage.finish() : 0;
+  return io.finish();
 }
 
-// the 2x2 image covariance of keypoints from their image patches: pnec_patch_cov.hip.  No batch is involved; a HOST-space
-// call stages through HostStage in buffers of its own, which a handle-less holder owns for the call.
-namespace {
-struct StageHolder {
-  pnec_hip_problem p;
-  ~StageHolder() {
-    if (p.d_stage) (void)dev_free(p.d_stage);
-    if (p.d_stage_i) (void)dev_free(p.d_stage_i);
-  }
-};
-}  // namespace
-
+// the 2x2 image covariance of keypoints from their image patches: pnec_patch_cov.hip.  No batch is involved: a HOST-space
+// call stages in buffers that live for the call only (CallArrays made from the device).
 int pnec_hip_patch_covariance(const void *images, int pixel_type, int64_t n_images, int32_t height, int32_t width,
                               int64_t pitch, const int64_t *offsets, int64_t n_points, const double *pts,
                               const double *pattern, int32_t n_pattern, double scaling, const double *angle,
@@ -1308,37 +1268,20 @@ int pnec_hip_patch_covariance(const void *images, int pixel_type, int64_t n_imag
     return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_covariance: every output is NULL");
   if (n_pattern < 1 || n_pattern > PNEC_HIP_PATCH_MAX_POINTS)
     return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_covariance: n_pattern must be 1 .. 64");
-  size_t elem = 0;
-  switch (pixel_type) {
-    case PNEC_HIP_PIXEL_U8: elem = 1; break;
-    case PNEC_HIP_PIXEL_U16: elem = 2; break;
-    case PNEC_HIP_PIXEL_F32: elem = 4; break;
-    default: return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_covariance: unknown pixel_type");
-  }
+  const size_t elem = pixel_bytes(pixel_type);
+  if (!elem) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_covariance: unknown pixel_type");
   if (n_images < 1 || height < 1 || width < 1 || n_points < 0)
     return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_covariance: n_images, height, width must be >= 1, n_points >= 0");
   if (pitch < width) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_covariance: pitch (in elements) is below width");
   if (!(scaling > 0.0) || !std::isfinite(scaling))
     return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_covariance: scaling must be positive and finite");
-  if (space != PNEC_HIP_MEM_DEVICE && space != PNEC_HIP_MEM_HOST)
-    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_covariance: bad memory space");
-  // (the pixels of all images, counted in elements: the last row of the last image need not be padded)
-  if (n_images > 0x7fffffffLL || (double)n_images * (double)height * (double)pitch * (double)elem > 9.0e18)
-    return fail(PNEC_HIP_ERR_UNSUPPORTED, "patch_covariance: the images do not fit a 64-bit byte count");
-  if (space == PNEC_HIP_MEM_HOST) {
-    bool ok = offsets[0] == 0 && offsets[n_images] == n_points;
-    for (int64_t f = 0; ok && f < n_images; ++f) ok = offsets[f] <= offsets[f + 1];
-    if (!ok)
-      return fail(PNEC_HIP_ERR_INVALID_ARGUMENT,
-                  "patch_covariance: offsets must be non-decreasing from 0 to n_points");
-  }
+  if (int rc = check_space("patch_covariance: ", space)) return rc;
+  if (int rc = check_images_fit("patch_covariance", n_images, height, pitch, elem)) return rc;
+  if (space == PNEC_HIP_MEM_HOST)
+    if (int rc = check_offsets("patch_covariance", "offsets", offsets, n_images, n_points, "n_points")) return rc;
   if (n_points == 0) return 0;
-  DeviceGuard guard(device);
-  if (!guard.ok) return fail(PNEC_HIP_ERR_HIP_RUNTIME, "hipSetDevice failed (no such device?)");
   hipStream_t stream = (hipStream_t)stream_;
-  StageHolder holder;
-  holder.p.device = device;
-  HostStage stage(&holder.p, stream);
+  CallArrays io(device, space, stream);
   PatchCovArgs a;
   a.w = width;
   a.h = height;
@@ -1347,49 +1290,23 @@ int pnec_hip_patch_covariance(const void *images, int pixel_type, int64_t n_imag
   a.n_points = n_points;
   a.n_pattern = n_pattern;
   a.scaling = scaling;
-  if (space == PNEC_HIP_MEM_DEVICE) {
-    a.images = images;
-    a.offsets = offsets;
-    a.pts = pts;
-    a.pattern = pattern;
-    a.angle = angle;
-    a.out_cov = out_cov;
-    a.out_hessian = out_hessian;
-    a.out_mean = out_mean;
-    a.out_n_valid = out_n_valid;
-    a.out_status = out_status;
-  } else {
-    const int64_t M = n_points;
-    const int64_t image_bytes = (int64_t)elem * ((n_images * (int64_t)height - 1) * pitch + width);
-    // stage: [pixels | offsets F+1 (int64) | pts 2M | pattern 2P | angle M | cov 3M | hessian 6M | mean M], ints
-    // [n_valid M | status M]
-    if (int rc = stage.reserve((image_bytes + 7) / 8 + (n_images + 1) + 13 * M + 2 * n_pattern, 2 * M)) return rc;
-    a.images = stage.up_bytes(images, image_bytes);
-    a.offsets = stage.up(offsets, n_images + 1);
-    a.pts = stage.up(pts, 2 * M);
-    a.pattern = stage.up(pattern, 2 * (int64_t)n_pattern);
-    a.angle = stage.up(angle, M);
-    a.out_cov = stage.out(out_cov, 3 * M);
-    a.out_hessian = stage.out(out_hessian, 6 * M);
-    a.out_mean = stage.out(out_mean, M);
-    a.out_n_valid = stage.out(out_n_valid, M);
-    a.out_status = stage.out(out_status, M);
-    if (int rc = stage.status()) return rc;
-  }
+  const int64_t M = n_points;
+  io.in_bytes(a.images, images, image_block_bytes(elem, n_images, height, pitch, width));
+  io.in(a.offsets, offsets, n_images + 1);
+  io.in(a.pts, pts, 2 * M);
+  io.in(a.pattern, pattern, 2 * (int64_t)n_pattern);
+  io.in(a.angle, angle, M);
+  io.out(a.out_cov, out_cov, 3 * M);
+  io.out(a.out_hessian, out_hessian, 6 * M);
+  io.out(a.out_mean, out_mean, M);
+  io.out(a.out_n_valid, out_n_valid, M);
+  io.out(a.out_status, out_status, M);
+  if (int rc = io.commit()) return rc;
   PNEC_HIP_TRY(launch_patch_covariance(pixel_type, a, stream));
-  return space == PNEC_HIP_MEM_HOST ? stage.finish() : 0;
+  return io.finish();
 }
 
 // the pyramid's halving step and the tracker: pnec_patch_track.hip.  Staged like the patch covariances.
-static size_t pixel_bytes(int pixel_type) {
-  switch (pixel_type) {
-    case PNEC_HIP_PIXEL_U8: return 1;
-    case PNEC_HIP_PIXEL_U16: return 2;
-    case PNEC_HIP_PIXEL_F32: return 4;
-    default: return 0;
-  }
-}
-
 int pnec_hip_image_pyramid_level(const void *in, void *out, int pixel_type, int64_t n_images, int32_t height,
                                  int32_t width, int64_t pitch_in, int64_t pitch_out, int space, int device,
                                  void *stream_) {
@@ -1400,37 +1317,23 @@ int pnec_hip_image_pyramid_level(const void *in, void *out, int pixel_type, int6
     return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "image_pyramid_level: n_images must be >= 1, height and width >= 4");
   if (pitch_in < width || pitch_out < width / 2)
     return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "image_pyramid_level: a pitch (in elements) is below its width");
-  if (space != PNEC_HIP_MEM_DEVICE && space != PNEC_HIP_MEM_HOST)
-    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "image_pyramid_level: bad memory space");
-  if (n_images > 0x7fffffffLL || (double)n_images * (double)height * (double)pitch_in * (double)elem > 9.0e18 ||
-      (double)n_images * (double)(height / 2) * (double)pitch_out * (double)elem > 9.0e18)
-    return fail(PNEC_HIP_ERR_UNSUPPORTED, "image_pyramid_level: the images do not fit a 64-bit byte count");
-  DeviceGuard guard(device);
-  if (!guard.ok) return fail(PNEC_HIP_ERR_HIP_RUNTIME, "hipSetDevice failed (no such device?)");
+  if (int rc = check_space("image_pyramid_level: ", space)) return rc;
+  if (int rc = check_images_fit("image_pyramid_level", n_images, height, pitch_in, elem)) return rc;
+  if (int rc = check_images_fit("image_pyramid_level", n_images, height / 2, pitch_out, elem)) return rc;
   hipStream_t stream = (hipStream_t)stream_;
-  StageHolder holder;
-  holder.p.device = device;
-  HostStage stage(&holder.p, stream);
+  CallArrays io(device, space, stream);
   PyramidLevelArgs a;
   a.w = width;
   a.h = height;
   a.pitch_in = pitch_in;
   a.pitch_out = pitch_out;
   a.n_images = n_images;
-  a.in = in;
-  a.out = out;
-  if (space == PNEC_HIP_MEM_HOST) {
-    const int64_t in_bytes = (int64_t)elem * ((n_images * (int64_t)height - 1) * pitch_in + width);
-    const int64_t out_bytes = (int64_t)elem * ((n_images * (int64_t)(height / 2) - 1) * pitch_out + width / 2);
-    if (int rc = stage.reserve((in_bytes + 7) / 8 + (out_bytes + 7) / 8, 0)) return rc;
-    a.in = stage.up_bytes(in, in_bytes);
-    // (the whole output block travels up first: the padding between its rows comes back as the caller had it)
-    a.out = stage.out(static_cast<uint8_t *>(out), out_bytes);
-    if (int rc = stage.status()) return rc;
-    PNEC_HIP_TRY(hipMemcpyAsync(a.out, out, (size_t)out_bytes, hipMemcpyHostToDevice, stream));
-  }
+  io.in_bytes(a.in, in, image_block_bytes(elem, n_images, height, pitch_in, width));
+  // (the whole output block travels up first: the padding between its rows comes back as the caller had it)
+  io.out(a.out, static_cast<uint8_t *>(out), image_block_bytes(elem, n_images, height / 2, pitch_out, width / 2), kPreload);
+  if (int rc = io.commit()) return rc;
   PNEC_HIP_TRY(launch_image_pyramid_level(pixel_type, a, stream));
-  return space == PNEC_HIP_MEM_HOST ? stage.finish() : 0;
+  return io.finish();
 }
 
 int pnec_hip_patch_track(const void *const *tmpl, const int64_t *tmpl_pitch, const void *const *prev,
@@ -1474,27 +1377,15 @@ int pnec_hip_patch_track(const void *const *tmpl, const int64_t *tmpl_pitch, con
     return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_track: shift must be finite");
   if (!(scaling > 0.0) || !std::isfinite(scaling))
     return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_track: scaling must be positive and finite");
-  if (space != PNEC_HIP_MEM_DEVICE && space != PNEC_HIP_MEM_HOST)
-    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_track: bad memory space");
-  if (n_images > 0x7fffffffLL)
-    return fail(PNEC_HIP_ERR_UNSUPPORTED, "patch_track: the images do not fit a 64-bit byte count");
-  for (int l = 0; l < n_levels; ++l) {
-    const double rows = (double)n_images * (double)(height >> l) * (double)elem;
-    if (rows * (double)tmpl_pitch[l] > 9.0e18 || rows * (double)prev_pitch[l] > 9.0e18 || rows * (double)next_pitch[l] > 9.0e18)
-      return fail(PNEC_HIP_ERR_UNSUPPORTED, "patch_track: the images do not fit a 64-bit byte count");
-  }
-  if (space == PNEC_HIP_MEM_HOST) {
-    bool ok = offsets[0] == 0 && offsets[n_images] == n_points;
-    for (int64_t f = 0; ok && f < n_images; ++f) ok = offsets[f] <= offsets[f + 1];
-    if (!ok) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_track: offsets must be non-decreasing from 0 to n_points");
-  }
+  if (int rc = check_space("patch_track: ", space)) return rc;
+  for (int l = 0; l < n_levels; ++l)
+    for (const int64_t pitch : {tmpl_pitch[l], prev_pitch[l], next_pitch[l]})
+      if (int rc = check_images_fit("patch_track", n_images, height >> l, pitch, elem)) return rc;
+  if (space == PNEC_HIP_MEM_HOST)
+    if (int rc = check_offsets("patch_track", "offsets", offsets, n_images, n_points, "n_points")) return rc;
   if (n_points == 0) return 0;
-  DeviceGuard guard(device);
-  if (!guard.ok) return fail(PNEC_HIP_ERR_HIP_RUNTIME, "hipSetDevice failed (no such device?)");
   hipStream_t stream = (hipStream_t)stream_;
-  StageHolder holder;
-  holder.p.device = device;
-  HostStage stage(&holder.p, stream);
+  CallArrays io(device, space, stream);
   PatchTrackArgs a{};
   a.n_levels = n_levels;
   a.w = width;
@@ -1513,59 +1404,31 @@ int pnec_hip_patch_track(const void *const *tmpl, const int64_t *tmpl_pitch, con
     a.prev.pitch[l] = prev_pitch[l];
     a.next.pitch[l] = next_pitch[l];
   }
-  if (space == PNEC_HIP_MEM_DEVICE) {
-    for (int l = 0; l < n_levels; ++l) {
-      a.tmpl.level[l] = tmpl[l];
-      a.prev.level[l] = prev[l];
-      a.next.level[l] = next[l];
-    }
-    a.offsets = offsets;
-    a.tmpl_pts = tmpl_pts;
-    a.init_pts = init_pts;
-    a.init_angle = init_angle;
-    a.pattern = pattern;
-    a.out_pts = out_pts;
-    a.out_angle = out_angle;
-    a.out_cov = out_cov;
-    a.out_dist2 = out_dist2;
-    a.out_status = out_status;
-    a.out_lost_level = out_lost_level;
-  } else {
-    const int64_t M = n_points;
-    auto level_bytes = [&](int l, int64_t pitch) {
-      return (int64_t)elem * ((n_images * (int64_t)(height >> l) - 1) * pitch + (width >> l));
-    };
-    // a level that two pyramids share (prev = tmpl) is staged once
-    int64_t pixels8 = 0;
-    for (int l = 0; l < n_levels; ++l) {
-      pixels8 += (level_bytes(l, tmpl_pitch[l]) + 7) / 8 + (level_bytes(l, next_pitch[l]) + 7) / 8;
-      if (prev[l] != tmpl[l] || prev_pitch[l] != tmpl_pitch[l]) pixels8 += (level_bytes(l, prev_pitch[l]) + 7) / 8;
-    }
-    // stage: [pixels | offsets F+1 (int64) | tmpl_pts 2M | init_pts 2M | init_angle M | pattern 2P | pts 2M | angle M |
-    // cov 3M | dist2 M], ints [status M | lost_level M]
-    if (int rc = stage.reserve(pixels8 + (n_images + 1) + 12 * M + 2 * n_pattern, 2 * M)) return rc;
-    for (int l = 0; l < n_levels; ++l) {
-      a.tmpl.level[l] = stage.up_bytes(tmpl[l], level_bytes(l, tmpl_pitch[l]));
-      a.next.level[l] = stage.up_bytes(next[l], level_bytes(l, next_pitch[l]));
-      a.prev.level[l] = (prev[l] != tmpl[l] || prev_pitch[l] != tmpl_pitch[l])
-                            ? stage.up_bytes(prev[l], level_bytes(l, prev_pitch[l]))
-                            : a.tmpl.level[l];
-    }
-    a.offsets = stage.up(offsets, n_images + 1);
-    a.tmpl_pts = stage.up(tmpl_pts, 2 * M);
-    a.init_pts = stage.up(init_pts, 2 * M);
-    a.init_angle = stage.up(init_angle, M);
-    a.pattern = stage.up(pattern, 2 * (int64_t)n_pattern);
-    a.out_pts = stage.out(out_pts, 2 * M);
-    a.out_angle = stage.out(out_angle, M);
-    a.out_cov = stage.out(out_cov, 3 * M);
-    a.out_dist2 = stage.out(out_dist2, M);
-    a.out_status = stage.out(out_status, M);
-    a.out_lost_level = stage.out(out_lost_level, M);
-    if (int rc = stage.status()) return rc;
+  const int64_t M = n_points;
+  auto level_bytes = [&](int l, int64_t pitch) { return image_block_bytes(elem, n_images, height >> l, pitch, width >> l); };
+  // a level that two pyramids share (prev = tmpl) is staged once
+  auto shared = [&](int l) { return prev[l] == tmpl[l] && prev_pitch[l] == tmpl_pitch[l]; };
+  for (int l = 0; l < n_levels; ++l) {
+    io.in_bytes(a.tmpl.level[l], tmpl[l], level_bytes(l, tmpl_pitch[l]));
+    io.in_bytes(a.next.level[l], next[l], level_bytes(l, next_pitch[l]));
+    if (!shared(l)) io.in_bytes(a.prev.level[l], prev[l], level_bytes(l, prev_pitch[l]));
   }
+  io.in(a.offsets, offsets, n_images + 1);
+  io.in(a.tmpl_pts, tmpl_pts, 2 * M);
+  io.in(a.init_pts, init_pts, 2 * M);
+  io.in(a.init_angle, init_angle, M);
+  io.in(a.pattern, pattern, 2 * (int64_t)n_pattern);
+  io.out(a.out_pts, out_pts, 2 * M);
+  io.out(a.out_angle, out_angle, M);
+  io.out(a.out_cov, out_cov, 3 * M);
+  io.out(a.out_dist2, out_dist2, M);
+  io.out(a.out_status, out_status, M);
+  io.out(a.out_lost_level, out_lost_level, M);
+  if (int rc = io.commit()) return rc;
+  for (int l = 0; l < n_levels; ++l)
+    if (shared(l)) a.prev.level[l] = a.tmpl.level[l];
   PNEC_HIP_TRY(launch_patch_track(pixel_type, a, stream));
-  return space == PNEC_HIP_MEM_HOST ? stage.finish() : 0;
+  return io.finish();
 }
 
 // keypoint detection: pnec_detect.hip.  Staged like the patch covariances; the outputs travel up first, so that what
@@ -1580,9 +1443,8 @@ int pnec_hip_detect_keypoints(const void *images, int pixel_type, int64_t n_imag
   if (pixel_type == PNEC_HIP_PIXEL_F32)
     return fail(PNEC_HIP_ERR_INVALID_ARGUMENT,
                 "detect_keypoints: pixel_type F32 has no declared range to quantise to 8 bits (U8 or U16 only)");
-  if (pixel_type != PNEC_HIP_PIXEL_U8 && pixel_type != PNEC_HIP_PIXEL_U16)
-    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "detect_keypoints: unknown pixel_type");
-  const size_t elem = pixel_type == PNEC_HIP_PIXEL_U8 ? 1 : 2;
+  const size_t elem = pixel_bytes(pixel_type);
+  if (!elem) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "detect_keypoints: unknown pixel_type");
   if (grid < kDetectMinGrid || grid > kDetectMaxGrid)
     return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "detect_keypoints: grid must be 8 .. 64");
   if (points_per_cell < 1 || points_per_cell > kDetectMaxPerCell)
@@ -1599,17 +1461,11 @@ int pnec_hip_detect_keypoints(const void *images, int pixel_type, int64_t n_imag
     return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "detect_keypoints: cur_pts without cur_offsets");
   if (cur_offsets && !cur_pts && n_cur > 0)
     return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "detect_keypoints: cur_offsets and n_cur > 0 without cur_pts (NULL)");
-  if (space != PNEC_HIP_MEM_DEVICE && space != PNEC_HIP_MEM_HOST)
-    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "detect_keypoints: bad memory space");
-  if (n_images > 0x7fffffffLL || (double)n_images * (double)height * (double)pitch * (double)elem > 9.0e18)
-    return fail(PNEC_HIP_ERR_UNSUPPORTED, "detect_keypoints: the images do not fit a 64-bit byte count");
+  if (int rc = check_space("detect_keypoints: ", space)) return rc;
+  if (int rc = check_images_fit("detect_keypoints", n_images, height, pitch, elem)) return rc;
   const bool have_cur = cur_offsets && cur_pts && n_cur > 0;
-  if (space == PNEC_HIP_MEM_HOST && cur_offsets) {
-    bool ok = cur_offsets[0] == 0 && cur_offsets[n_images] == n_cur;
-    for (int64_t f = 0; ok && f < n_images; ++f) ok = cur_offsets[f] <= cur_offsets[f + 1];
-    if (!ok)
-      return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "detect_keypoints: cur_offsets must be non-decreasing from 0 to n_cur");
-  }
+  if (space == PNEC_HIP_MEM_HOST && cur_offsets)
+    if (int rc = check_offsets("detect_keypoints", "cur_offsets", cur_offsets, n_images, n_cur, "n_cur")) return rc;
   DetectArgs a{};
   a.w = width;
   a.h = height;
@@ -1628,47 +1484,19 @@ int pnec_hip_detect_keypoints(const void *images, int pixel_type, int64_t n_imag
   if (n_cells > 0x7fffffffLL / kDetectMaxPerCell || (double)n_images * (double)n_cells * kDetectMaxPerCell > 4.0e18)
     return fail(PNEC_HIP_ERR_UNSUPPORTED, "detect_keypoints: too many cells");
   const int64_t cap = n_images * n_cells * points_per_cell;
-  DeviceGuard guard(device);
-  if (!guard.ok) return fail(PNEC_HIP_ERR_HIP_RUNTIME, "hipSetDevice failed (no such device?)");
   hipStream_t stream = (hipStream_t)stream_;
-  StageHolder holder;
-  holder.p.device = device;
-  HostStage stage(&holder.p, stream);
-  if (space == PNEC_HIP_MEM_DEVICE) {
-    a.images = images;
-    a.cur_offsets = have_cur ? cur_offsets : nullptr;
-    a.cur_pts = have_cur ? cur_pts : nullptr;
-    a.out_cell = out_cell;
-    a.out_offsets = out_offsets;
-    a.out_pts = out_pts;
-    a.out_score = out_score;
-    a.out_cell_index = out_cell_index;
-  } else {
-    const int64_t image_bytes = (int64_t)elem * ((n_images * (int64_t)height - 1) * pitch + width);
-    const int64_t C = have_cur ? n_cur : 0;
-    // stage: [pixels | cur_offsets F+1 (int64) | cur_pts 2C | offsets F+1 (int64) | pts 2 cap], ints [cell F n_cells |
-    // score cap | cell_index cap]
-    if (int rc = stage.reserve((image_bytes + 7) / 8 + (have_cur ? n_images + 1 + 2 * C : 0) + (n_images + 1) + 2 * cap,
-                               n_images * n_cells + 2 * cap))
-      return rc;
-    a.images = stage.up_bytes(images, image_bytes);
-    a.cur_offsets = have_cur ? stage.up(cur_offsets, n_images + 1) : nullptr;
-    a.cur_pts = have_cur ? stage.up(cur_pts, 2 * C) : nullptr;
-    a.out_cell = stage.out(out_cell, n_images * n_cells);
-    a.out_offsets = reinterpret_cast<int64_t *>(stage.out(reinterpret_cast<double *>(out_offsets), n_images + 1));
-    a.out_pts = stage.out(out_pts, 2 * cap);
-    a.out_score = stage.out(out_score, cap);
-    a.out_cell_index = stage.out(out_cell_index, cap);
-    if (int rc = stage.status()) return rc;
-    PNEC_HIP_TRY(hipMemcpyAsync(a.out_pts, out_pts, sizeof(double) * 2 * (size_t)cap, hipMemcpyHostToDevice, stream));
-    if (out_score)
-      PNEC_HIP_TRY(hipMemcpyAsync(a.out_score, out_score, sizeof(int32_t) * (size_t)cap, hipMemcpyHostToDevice, stream));
-    if (out_cell_index)
-      PNEC_HIP_TRY(hipMemcpyAsync(a.out_cell_index, out_cell_index, sizeof(int32_t) * (size_t)cap, hipMemcpyHostToDevice,
-                                  stream));
-  }
+  CallArrays io(device, space, stream);
+  io.in_bytes(a.images, images, image_block_bytes(elem, n_images, height, pitch, width));
+  io.in(a.cur_offsets, have_cur ? cur_offsets : nullptr, n_images + 1);
+  io.in(a.cur_pts, have_cur ? cur_pts : nullptr, 2 * n_cur);
+  io.out(a.out_cell, out_cell, n_images * n_cells);
+  io.out(a.out_offsets, out_offsets, n_images + 1);
+  io.out(a.out_pts, out_pts, 2 * cap, kPreload);
+  io.out(a.out_score, out_score, cap, kPreload);
+  io.out(a.out_cell_index, out_cell_index, cap, kPreload);
+  if (int rc = io.commit()) return rc;
   PNEC_HIP_TRY(launch_detect_keypoints(pixel_type, a, stream));
-  return space == PNEC_HIP_MEM_HOST ? stage.finish() : 0;
+  return io.finish();
 }
 
 // shared driver of the two eigensolver stages (host or device pointers)
@@ -1679,23 +1507,18 @@ static int run_front_stage(pnec_hip_problem *p, bool weighted, const double *ini
     return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
   if (weighted && p->mode != PNEC_HIP_MODE_TARGET)
     return fail(PNEC_HIP_ERR_UNSUPPORTED, "the weighted eigensolver needs a TARGET-mode problem");
-  if (space != PNEC_HIP_MEM_DEVICE && space != PNEC_HIP_MEM_HOST)
-    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "bad memory space");
+  if (int rc = check_space("", space)) return rc;
   if (p->n_pairs == 0) return 0;
-  DeviceGuard guard(p->device);
   hipStream_t stream = (hipStream_t)stream_;
   const int64_t P = p->n_pairs;
-  const double *d_q = init_q, *d_t = init_t;
-  double *d_oq = out_q, *d_ot = out_t;
-  HostStage stage(p, stream);
-  if (space == PNEC_HIP_MEM_HOST) {
-    if (int rc = stage.reserve(14 * P, 0)) return rc;
-    d_q = stage.up(init_q, 4 * P);
-    d_t = stage.up(init_t, 3 * P);   // (NULL for the unweighted stage, which has no use for it)
-    d_oq = stage.out(out_q, 4 * P);
-    d_ot = stage.out(out_t, 3 * P);
-    if (int rc = stage.status()) return rc;
-  }
+  const double *d_q, *d_t;
+  double *d_oq, *d_ot;
+  CallArrays io(p, space, stream);
+  io.in(d_q, init_q, 4 * P);
+  io.in(d_t, init_t, 3 * P);   // (NULL for the unweighted stage, which has no use for it)
+  io.out(d_oq, out_q, 4 * P);
+  io.out(d_ot, out_t, 3 * P);
+  if (int rc = io.commit()) return rc;
   if (int rc = ensure_front(p)) return rc;
   hipError_t e = weighted
                      ? launch_weighted_eigensolver(p->device, p->d_data, p->d_block_offset, p->d_count, P, p->n_max, d_q,
@@ -1704,7 +1527,7 @@ static int run_front_stage(pnec_hip_problem *p, bool weighted, const double *ini
                      : launch_nec_eigensolver(p->d_data, p->d_block_offset, p->d_count, P, d_q, d_oq, d_ot,
                                               nullptr, p->d_front, p->d_front_i, stream, p->es_scheme);
   if (e != hipSuccess) return fail_hip(e, weighted ? "weighted_eigensolver_kernel" : "nec_eigensolver_kernel");
-  return space == PNEC_HIP_MEM_HOST ? stage.finish() : 0;
+  return io.finish();
 }
 
 int pnec_hip_problem_set_eigensolver_scheme(pnec_hip_problem *p, int32_t scheme) {
@@ -1749,40 +1572,26 @@ int pnec_hip_ransac_eigensolver(pnec_hip_problem *p, const double *init_q, uint6
   if (max_iterations < 0 || sample_size < 1) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "bad RANSAC parameters");
   if (sample_size > PNEC_HIP_MAX_RANSAC_SAMPLE)
     return fail(PNEC_HIP_ERR_UNSUPPORTED, "ransac sample_size > 16 is not built (a hypothesis keeps its sample in registers)");
-  if (space != PNEC_HIP_MEM_DEVICE && space != PNEC_HIP_MEM_HOST)
-    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "bad memory space");
+  if (int rc = check_space("", space)) return rc;
   if (p->n_pairs == 0) return 0;
   if (space == PNEC_HIP_MEM_HOST)  // host-side per-correspondence arrays need the exact sizes
     if (int rc = materialize(p)) return rc;
-  DeviceGuard guard(p->device);
   hipStream_t stream = (hipStream_t)stream_;
   const int64_t P = p->n_pairs, M = p->n_corr;
-  const double *d_q = init_q;
-  double *d_oq = out_q, *d_ot = out_t;
-  uint8_t *d_mask = out_inlier_mask;
-  int32_t *d_cnt = out_inlier_count, *d_it = out_ransac_iterations;
-  uint8_t *tmp_mask = nullptr;
-  HostStage stage(p, stream);
-  if (space == PNEC_HIP_MEM_HOST) {
-    // (the counts are staged, wanted or not: the stage fills both)
-    if (int rc = stage.reserve(11 * P, 2 * P)) return rc;
-    d_q = stage.up(init_q, 4 * P);
-    d_oq = stage.out(out_q, 4 * P);
-    d_ot = stage.out(out_t, 3 * P);
-    d_cnt = stage.out(out_inlier_count, P, /*keep*/ true);
-    d_it = stage.out(out_ransac_iterations, P, /*keep*/ true);
-    if (int rc = stage.status()) return rc;
-    if (out_inlier_mask) {
-      PNEC_HIP_TRY(dev_alloc(&tmp_mask, (size_t)std::max<int64_t>(M, 1)));
-      d_mask = tmp_mask;
-    }
-  }
-  int rc_ws = ensure_front(p);
-  if (!rc_ws) rc_ws = ensure_order_hint(p);
-  if (rc_ws) {
-    if (tmp_mask) (void)dev_free(tmp_mask);
-    return rc_ws;
-  }
+  const double *d_q;
+  double *d_oq, *d_ot;
+  uint8_t *d_mask;
+  int32_t *d_cnt, *d_it;
+  CallArrays io(p, space, stream);
+  io.in(d_q, init_q, 4 * P);
+  io.out(d_oq, out_q, 4 * P);
+  io.out(d_ot, out_t, 3 * P);
+  io.out(d_mask, out_inlier_mask, M);
+  io.out(d_cnt, out_inlier_count, P, kKeep);   // (the stage fills both counts, wanted or not)
+  io.out(d_it, out_ransac_iterations, P, kKeep);
+  if (int rc = io.commit()) return rc;
+  if (int rc = ensure_front(p)) return rc;
+  if (int rc = ensure_order_hint(p)) return rc;
   if (p->order_hint && !d_it) d_it = p->d_hint_its;
   hipError_t e = launch_ransac_eigensolver(p->d_data, p->d_block_offset, p->d_offsets, p->d_count, P, d_q, seed,
                                            /*first_pair_id*/ 0ull, max_iterations, sample_size, threshold, d_oq, d_ot, d_mask, d_cnt, d_it,
@@ -1794,11 +1603,8 @@ int pnec_hip_ransac_eigensolver(pnec_hip_problem *p, const double *init_q, uint6
     e = launch_ransac_order(d_it, P, p->d_order, stream);
     p->order_pairs = P;
   }
-  if (e == hipSuccess && tmp_mask && M > 0)
-    e = hipMemcpyAsync(out_inlier_mask, tmp_mask, (size_t)M, hipMemcpyDeviceToHost, stream);
-  const int rc = e != hipSuccess ? fail_hip(e, "ransac_eigensolver_kernel") : space == PNEC_HIP_MEM_HOST ? stage.finish() : 0;
-  if (tmp_mask) (void)dev_free(tmp_mask);
-  return rc;
+  if (e != hipSuccess) return fail_hip(e, "ransac_eigensolver_kernel");
+  return io.finish();
 }
 
 static int select_into(pnec_hip_problem *src, const uint8_t *d_mask, hipStream_t stream, pnec_hip_problem *dst,

@@ -7,9 +7,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cstring>
+#include <optional>
 #include <string>
+#include <type_traits>
 #include <vector>
 
+#include "pnec_call_plan.hpp"
 #include "pnec_hip.h"
 
 // ------------------------------------------------------------------------------------------
@@ -158,98 +162,104 @@ int alloc_like(pnec_hip_problem *src, hipStream_t stream, pnec_hip_problem **out
 int select_prepare(pnec_hip_problem *src, hipStream_t stream, pnec_hip_problem *dst);
 int select_finish(pnec_hip_problem *src, hipStream_t stream, pnec_hip_problem *dst, bool scan = true);
 
-// ---- staging of a HOST-space call in the batch's d_stage / d_stage_i ------------------------
-// reserve() sizes the two buffers once, before any pointer is handed out (growing them later would invalidate the
-// pointers); up() and out() then carve them front to back and refuse to go past what was reserved, so a miscounted
-// total is an error, never a write into a neighbouring array.  Copies are queued on the call's stream; finish() queues
-// the copies back, in the order of the out() calls, and waits for the stream.
-class HostStage {
+// ---- the arrays of one ABI call, in either memory space --------------------------------------
+// An entry point names each array once -- in(), in_bytes(), out(), scratch() with the field of its argument struct, the
+// caller's pointer and the length -- then commit()s, launches, and returns finish().
+//   DEVICE space: the fields get the caller's pointers; nothing is allocated, copied or waited for (scratch() aside).
+//   HOST space: commit() sizes the owner's d_stage / d_stage_i once from the list (CallPlan, pnec_call_plan.hpp), points
+//   the fields into them and queues the uploads on the call's stream; finish() queues the copies back, in the order of
+//   the out() calls, and waits for the stream.
+// The staging buffers are the batch's, or, for a call without a batch (the image entry points), the call's own.  The
+// object also makes the batch's (the given) device the current one for as long as it lives; that the given device
+// could not be selected is commit()'s first error.
+class CallArrays {
  public:
-  HostStage(pnec_hip_problem *p, hipStream_t stream) : p_(p), stream_(stream) {}
-  int reserve(int64_t doubles, int64_t ints) {
-    if (int rc = ensure_stage(p_, doubles, ints)) return rc;
-    d_left_ = doubles;
-    i_left_ = ints;
-    d_next_ = p_->d_stage;
-    i_next_ = p_->d_stage_i;
-    return 0;
+  CallArrays(pnec_hip_problem *owner, int space, hipStream_t stream)
+      : guard_(owner->device), p_(owner), host_(space == PNEC_HIP_MEM_HOST), stream_(stream) {}
+  CallArrays(int device, int space, hipStream_t stream)
+      : guard_(device), host_(space == PNEC_HIP_MEM_HOST), stream_(stream) {
+    own_.emplace();
+    own_->device = device;
+    p_ = &*own_;
   }
-  // n doubles of `host` on the device; nullptr (and no room taken) for a NULL array
-  const double *up(const double *host, int64_t n) {
-    double *d = host ? take(d_next_, d_left_, n) : nullptr;
-    if (d && n > 0 && err_ == hipSuccess) err_ = hipMemcpyAsync(d, host, sizeof(double) * n, hipMemcpyHostToDevice, stream_);
-    return d;
+  ~CallArrays() {
+    if (own_ && own_->d_stage) (void)dev_free(own_->d_stage);
+    if (own_ && own_->d_stage_i) (void)dev_free(own_->d_stage_i);
   }
-  // the same for 64-bit integers (they live among the doubles) and 32-bit integers
-  const int64_t *up(const int64_t *host, int64_t n) {
-    int64_t *d = host ? reinterpret_cast<int64_t *>(take(d_next_, d_left_, n)) : nullptr;
-    if (d && n > 0 && err_ == hipSuccess) err_ = hipMemcpyAsync(d, host, sizeof(int64_t) * n, hipMemcpyHostToDevice, stream_);
-    return d;
+  CallArrays(const CallArrays &) = delete;
+  CallArrays &operator=(const CallArrays &) = delete;
+
+  bool host() const { return host_; }
+  // n doubles, 64-bit or 32-bit integers; a NULL array gives nullptr and takes no room
+  template <typename F, typename T>
+  void in(F &field, const T *caller, int64_t n) {
+    static_assert(sizeof(T) == 8 || sizeof(T) == 4, "doubles, int64_t or int32_t");
+    if (!host_) field = caller;
+    else note(field, caller, plan_.in(caller != nullptr, n, sizeof(T)));
   }
-  const int32_t *up(const int32_t *host, int64_t n) {
-    int32_t *d = host ? take(i_next_, i_left_, n) : nullptr;
-    if (d && n > 0 && err_ == hipSuccess) err_ = hipMemcpyAsync(d, host, sizeof(int32_t) * n, hipMemcpyHostToDevice, stream_);
-    return d;
+  // n bytes of anything (pixels)
+  template <typename F>
+  void in_bytes(F &field, const void *caller, int64_t n) {
+    if (!host_) field = caller;
+    else note(field, caller, plan_.in(caller != nullptr, n, 1));
   }
-  // n bytes of anything (pixels): they live among the doubles, in whole doubles
-  const void *up_bytes(const void *host, int64_t n) {
-    void *d = host ? static_cast<void *>(take(d_next_, d_left_, (n + 7) / 8)) : nullptr;
-    if (d && n > 0 && err_ == hipSuccess) err_ = hipMemcpyAsync(d, host, (size_t)n, hipMemcpyHostToDevice, stream_);
-    return d;
+  // an output of n doubles, 64-bit or 32-bit integers or bytes; a NULL one gives nullptr unless kKeep; kPreload: the
+  // caller's content travels up first, so that what the kernel leaves alone comes back as it was
+  template <typename F, typename T>
+  void out(F &field, T *caller, int64_t n, unsigned flags = 0) {
+    static_assert(sizeof(T) == 8 || sizeof(T) == 4 || sizeof(T) == 1, "doubles, int64_t, int32_t or bytes");
+    if (!host_) field = caller;
+    else note(field, caller, plan_.out(caller != nullptr, n, sizeof(T), flags));
   }
-  // room for an output of n items that finish() copies to `host`; for a NULL `host`: nullptr, or with `keep` (the
-  // kernel writes the array whether or not the caller wants it) room that is not copied back
-  double *out(double *host, int64_t n, bool keep = false) {
-    return host || keep ? back(host, take(d_next_, d_left_, n), sizeof(double) * n) : nullptr;
+  // n doubles or 32-bit integers the call's kernels use among themselves, in either space
+  template <typename T>
+  void scratch(T *&field, int64_t n) {
+    static_assert(sizeof(T) == 8 || sizeof(T) == 4, "doubles or int32_t");
+    note(field, nullptr, plan_.scratch(n, sizeof(T)));
   }
-  int32_t *out(int32_t *host, int64_t n, bool keep = false) {
-    return host || keep ? back(host, take(i_next_, i_left_, n), sizeof(int32_t) * n) : nullptr;
-  }
-  uint8_t *out(uint8_t *host, int64_t n) {  // bytes live behind the doubles, in whole doubles
-    return host ? back(host, reinterpret_cast<uint8_t *>(take(d_next_, d_left_, (n + 7) / 8)), (size_t)n) : nullptr;
-  }
-  // 0, or the error of the first reservation or copy that failed
-  int status() const {
-    if (overflow_) return fail(PNEC_HIP_ERR_HIP_RUNTIME, "host staging: more room taken than reserved");
-    return err_ == hipSuccess ? 0 : fail_hip(err_, "host staging copy");
+  int commit() {
+    if (own_ && !guard_.ok) return fail(PNEC_HIP_ERR_HIP_RUNTIME, "hipSetDevice failed (no such device?)");
+    if (slots_.empty()) return 0;
+    if (int rc = ensure_stage(p_, plan_.doubles, plan_.ints)) return rc;
+    for (size_t i = 0; i < slots_.size(); ++i) {
+      const CallPlan::Entry &e = plan_.entries[i];
+      Slot &s = slots_[i];
+      if (e.room) s.dev = e.ints ? static_cast<void *>(p_->d_stage_i + e.offset) : static_cast<void *>(p_->d_stage + e.offset);
+      std::memcpy(s.field, &s.dev, sizeof(void *));
+      if (e.up && err_ == hipSuccess) err_ = hipMemcpyAsync(s.dev, s.caller, e.bytes, hipMemcpyHostToDevice, stream_);
+    }
+    return status();
   }
   int finish() {
-    for (const Back &b : backs_)
-      if (err_ == hipSuccess) err_ = hipMemcpyAsync(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost, stream_);
-    if (err_ == hipSuccess && !overflow_) err_ = hipStreamSynchronize(stream_);
+    if (!host_) return 0;
+    for (size_t i = 0; i < slots_.size(); ++i)
+      if (plan_.entries[i].back && err_ == hipSuccess)
+        err_ = hipMemcpyAsync(slots_[i].caller, slots_[i].dev, plan_.entries[i].bytes, hipMemcpyDeviceToHost, stream_);
+    if (err_ == hipSuccess) err_ = hipStreamSynchronize(stream_);
     return status();
   }
 
  private:
-  struct Back {
-    void *host;
-    const void *dev;
-    size_t bytes;
+  struct Slot {
+    void *field;   // the pointer of the argument struct that commit() sets
+    void *caller;
+    void *dev;
   };
-  template <typename T>
-  T *take(T *&next, int64_t &left, int64_t n) {
-    if (n > left) {
-      overflow_ = true;
-      return nullptr;
-    }
-    T *at = next;
-    next += n;
-    left -= n;
-    return at;
+  // slots_[i] goes with plan_.entries[i]
+  template <typename F>
+  void note(F &field, const void *caller, const CallPlan::Entry &) {
+    static_assert(std::is_pointer<F>::value, "a field is a pointer");
+    slots_.push_back({&field, const_cast<void *>(caller), nullptr});
   }
-  template <typename T>
-  T *back(T *host, T *dev, size_t bytes) {
-    if (host && dev && bytes) backs_.push_back({host, dev, bytes});
-    return dev;
-  }
-  pnec_hip_problem *p_;
+  int status() const { return err_ == hipSuccess ? 0 : fail_hip(err_, "host staging copy"); }
+  DeviceGuard guard_;
+  std::optional<pnec_hip_problem> own_;  // a call without a batch: the holder of its staging buffers
+  pnec_hip_problem *p_ = nullptr;
+  bool host_;
   hipStream_t stream_;
-  double *d_next_ = nullptr;
-  int32_t *i_next_ = nullptr;
-  int64_t d_left_ = 0, i_left_ = 0;
   hipError_t err_ = hipSuccess;
-  bool overflow_ = false;
-  std::vector<Back> backs_;
+  CallPlan plan_;
+  std::vector<Slot> slots_;
 };
 
 // ---- launchers defined by the kernels' translation units ------------------------------------

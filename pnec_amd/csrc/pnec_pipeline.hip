@@ -253,31 +253,27 @@ int pnec_hip_solve_pipeline(pnec_hip_problem *p, const double *init_q, const dou
   if (P == 0) return 0;
   if (space == PNEC_HIP_MEM_HOST && out_inlier_mask)
     if (int rc = materialize(p)) return rc;  // a host mask is sized by the exact total
-  DeviceGuard guard(p->device);
   hipStream_t stream = (hipStream_t)stream_;
   const int64_t M = std::max<int64_t>(p->n_corr, 1);
 
-  // device scratch of the chain: [in_q 4P | in_t 3P | es_q 4P | es_t 3P | w_q 4P | w_t 3P | o_q 4P | o_t 3P], ints [cnt P | its P]
-  if (int rc = ensure_stage(p, 28 * P, 2 * P)) return rc;
-  double *w = p->d_stage;
-  double *in_q = w; w += 4 * P;
-  double *in_t = w; w += 3 * P;
-  double *es_q = w; w += 4 * P;
-  double *es_t = w; w += 3 * P;
-  double *w_q = w;  w += 4 * P;
-  double *w_t = w;  w += 3 * P;
-  double *o_q = w;  w += 4 * P;
-  double *o_t = w;
-  int32_t *cnt = p->d_stage_i;
-  const double *d_iq = init_q, *d_it = init_t;
-  double *d_oq = out_q, *d_ot = out_t;
-  uint8_t *d_mask = out_inlier_mask;
-  int32_t *d_cnt = out_inlier_count ? out_inlier_count : cnt;
-  if (space == PNEC_HIP_MEM_HOST) {
-    PNEC_HIP_TRY(hipMemcpyAsync(in_q, init_q, sizeof(double) * 4 * P, hipMemcpyHostToDevice, stream));
-    PNEC_HIP_TRY(hipMemcpyAsync(in_t, init_t, sizeof(double) * 3 * P, hipMemcpyHostToDevice, stream));
-    d_iq = in_q; d_it = in_t; d_oq = o_q; d_ot = o_t; d_cnt = cnt; d_mask = nullptr;
-  }
+  // the poses in and out, and between them the chain's own: the eigensolver's, the weighted stage's, the inlier counts
+  const double *d_iq, *d_it;
+  double *es_q, *es_t, *w_q, *w_t, *d_oq, *d_ot;
+  int32_t *cnt;
+  CallArrays io(p, space, stream);
+  io.in(d_iq, init_q, 4 * P);
+  io.in(d_it, init_t, 3 * P);
+  io.scratch(es_q, 4 * P);
+  io.scratch(es_t, 3 * P);
+  io.scratch(w_q, 4 * P);
+  io.scratch(w_t, 3 * P);
+  io.out(d_oq, out_q, 4 * P);
+  io.out(d_ot, out_t, 3 * P);
+  io.scratch(cnt, P);
+  if (int rc = io.commit()) return rc;
+  // HOST space: the mask and the counts are the batch's own until the copies at the end
+  uint8_t *d_mask = io.host() ? nullptr : out_inlier_mask;
+  int32_t *d_cnt = io.host() || !out_inlier_count ? cnt : out_inlier_count;
   if (o.use_ransac && !d_mask) {
     if (p->mask_bytes < M) {  // (a re-shaped batch may have grown)
       if (p->d_mask) (void)dev_free(p->d_mask);
@@ -352,9 +348,7 @@ int pnec_hip_solve_pipeline(pnec_hip_problem *p, const double *init_q, const dou
     if (inliers_used)
       if (int rc = select_finish(p, stream, p->sel_view)) return rc;   // (one scan over all ranges' counts)
   }
-  if (space == PNEC_HIP_MEM_HOST) {
-    PNEC_HIP_TRY(hipMemcpyAsync(out_q, d_oq, sizeof(double) * 4 * P, hipMemcpyDeviceToHost, stream));
-    PNEC_HIP_TRY(hipMemcpyAsync(out_t, d_ot, sizeof(double) * 3 * P, hipMemcpyDeviceToHost, stream));
+  if (io.host()) {
     if (o.use_ransac) {
       if (out_inlier_mask && p->n_corr > 0)
         PNEC_HIP_TRY(hipMemcpyAsync(out_inlier_mask, p->d_mask, (size_t)p->n_corr, hipMemcpyDeviceToHost, stream));
@@ -364,11 +358,10 @@ int pnec_hip_solve_pipeline(pnec_hip_problem *p, const double *init_q, const dou
       if (out_inlier_mask && p->n_corr > 0) std::memset(out_inlier_mask, 0, (size_t)p->n_corr);
       if (out_inlier_count) std::memset(out_inlier_count, 0, sizeof(int32_t) * P);
     }
-    PNEC_HIP_TRY(hipStreamSynchronize(stream));
   } else if (!o.use_ransac && out_inlier_mask && p->n_corr > 0) {
     PNEC_HIP_TRY(hipMemsetAsync(out_inlier_mask, 0, (size_t)p->n_corr, stream));
   }
-  return 0;
+  return io.finish();
 }
 
 }  // extern "C"

@@ -27,6 +27,8 @@ def kernels(path):
             continue
         t = l.split("//")[0].strip()
         t = re.sub(r"<[^>]*>", "<>", t)
+        if t == "...":
+            continue  # objdump's stand-in for the zero padding behind a kernel: what follows it decides whether it shows
         if t and not t.endswith(":"):
             # branch offsets are relative: identical code has identical ones; keep the text as is
             out[cur].append(t)
