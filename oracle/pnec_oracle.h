@@ -227,6 +227,20 @@ int pnec_oracle_ransac_eigensolver(int64_t n, const double *bvs1, const double *
                                    uint64_t seed, uint64_t pair_id, int max_iterations, int sample_size,
                                    double threshold, double R_out[9], double t_out[3], uint8_t *inlier_mask,
                                    int32_t *n_inliers, int32_t *iterations);
+/* the smallest |score - threshold| over every score the calling thread's last pnec_oracle_ransac_eigensolver compared with
+ * its threshold (all hypotheses and the final pass; +inf when it compared none): how far that call's decisions are from
+ * depending on the last bits of a score -- the precondition of the tests that demand equal masks of the device */
+double pnec_oracle_ransac_last_margin(void);
+/* a first-order running error bound of one score: |computed - exact| <= this, for the checker's evaluation and the device's */
+double pnec_oracle_reprojection_score_error_bound(const double f1[3], const double f2[3], const double R[9],
+                                                  const double t[3]);
+/* the smallest |score - threshold| / (2 x that score's error bound) over the same scores; computed only while tracking is
+ * switched on (a second evaluation per score; process-wide, set before a call), NaN otherwise; +inf when none compared.
+ * A score, or a bound, that is not a number takes the read-outs (this one and the plain margin) to 0. */
+void pnec_oracle_set_ransac_margin_tracking(int on);
+double pnec_oracle_ransac_last_margin_ratio(void);
+/* ... and the model (R row-major, t) whose scores made that call's final mask: the best hypothesis', before the refit */
+void pnec_oracle_ransac_last_model(double R[9], double t[3]);
 /* pnec.cc:283-348, literal: every round re-runs the eigensolver, every scf call runs its 10 steps */
 void pnec_oracle_weighted_eigensolver_ex(int64_t n, const double *bvs1, const double *bvs2,
                                          const double *covs, const double R_init[9], const double t_init[3],

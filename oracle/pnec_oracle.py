@@ -159,6 +159,16 @@ def lib() -> C.CDLL:
         _lib.pnec_oracle_reprojection_score.restype = C.c_double
         _lib.pnec_oracle_ransac_eigensolver.argtypes = [C.c_int64, _dp, _dp, _dp, C.c_uint64, C.c_uint64, C.c_int,
                                                         C.c_int, C.c_double, _dp, _dp, C.POINTER(C.c_uint8), _ip, _ip]
+        _lib.pnec_oracle_ransac_last_margin.argtypes = []
+        _lib.pnec_oracle_ransac_last_margin.restype = C.c_double
+        _lib.pnec_oracle_ransac_last_margin_ratio.argtypes = []
+        _lib.pnec_oracle_ransac_last_margin_ratio.restype = C.c_double
+        _lib.pnec_oracle_set_ransac_margin_tracking.argtypes = [C.c_int]
+        _lib.pnec_oracle_set_ransac_margin_tracking.restype = None
+        _lib.pnec_oracle_reprojection_score_error_bound.argtypes = [_dp, _dp, _dp, _dp]
+        _lib.pnec_oracle_reprojection_score_error_bound.restype = C.c_double
+        _lib.pnec_oracle_ransac_last_model.argtypes = [_dp, _dp]
+        _lib.pnec_oracle_ransac_last_model.restype = None
         _lib.pnec_oracle_weighted_eigensolver.argtypes = [C.c_int64, _dp, _dp, _dp, _dp, _dp, C.c_double,
                                                           C.c_int, _dp, _dp]
         _lib.pnec_oracle_weighted_eigensolver_batch.argtypes = [C.c_int64, _lp, _dp, _dp, _dp, _dp, _dp, C.c_double,
@@ -421,6 +431,41 @@ def ransac_eigensolver(bvs1, bvs2, R0, seed=1, pair_id=0, max_iterations=5000, s
                                          R.ctypes.data_as(_dp), t.ctypes.data_as(_dp),
                                          mask.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(cnt), C.byref(it))
     return R.reshape(3, 3), t, mask[:n].astype(bool), it.value
+
+
+def ransac_last_margin() -> float:
+    """The smallest |score - threshold| over every score this thread's last ransac_eigensolver call compared with its
+    threshold (all hypotheses and the final pass; inf when it compared none: fewer correspondences than the sample)."""
+    return float(lib().pnec_oracle_ransac_last_margin())
+
+
+def set_ransac_margin_tracking(on: bool) -> None:
+    """switch the per-score error bounds behind ransac_last_margin_ratio on or off (process-wide; off by default: they cost a
+    second evaluation per score)"""
+    lib().pnec_oracle_set_ransac_margin_tracking(int(bool(on)))
+
+
+def ransac_last_margin_ratio() -> float:
+    """The smallest |score - threshold| / (2 x the score's error bound) over every score this thread's last
+    ransac_eigensolver call compared -- 2 x: what two realisations of the score can differ by.  NaN unless
+    set_ransac_margin_tracking(True) was in force during the call; inf when the call compared nothing; 0 when a score or
+    its bound was not a number (parallel rays, a triangulated point at a camera centre)."""
+    return float(lib().pnec_oracle_ransac_last_margin_ratio())
+
+
+def reprojection_score_error_bound(f1, f2, R, t) -> float:
+    """first-order running error bound of reprojection_score(f1, f2, R, t): |computed - exact| <= this, for the checker's
+    evaluation and for the device's (pnec_oracle_frontend.c)"""
+    a, ap = _d(f1); b, bp = _d(f2); r, rp = _d(np.asarray(R).reshape(9)); c, cp = _d(t)
+    return float(lib().pnec_oracle_reprojection_score_error_bound(ap, bp, rp, cp))
+
+
+def ransac_last_model():
+    """-> (R [3,3], t [3]): the model whose scores made the final mask of this thread's last ransac_eigensolver call (the
+    best hypothesis', before the eigensolver on its inliers)."""
+    R, t = np.zeros(9), np.zeros(3)
+    lib().pnec_oracle_ransac_last_model(R.ctypes.data_as(_dp), t.ctypes.data_as(_dp))
+    return R.reshape(3, 3), t
 
 
 def reprojection_score(f1, f2, R, t):

@@ -644,10 +644,122 @@ static void es_model_translation(int64_t m, const double *b1, const double *b2, 
     for (int k = 0; k < 3; ++k) t[k] = -t[k];
 }
 
+/* The smallest |score - threshold| over every score the calling thread's last pnec_oracle_ransac_eigensolver compared with
+ * its threshold: all hypotheses' scoring passes and the final pass over the best model.  +inf when the call compared none
+ * (fewer correspondences than the sample size: the fallback scores nothing).  Test tooling: a second realisation of the
+ * score's arithmetic (the device's) can decide a comparison differently only where the score is closer to the threshold
+ * than the two realisations are to each other; a test that demands equal masks and iteration numbers first asks this
+ * read-out whether its inputs permit the demand.  Per thread: read it on the thread that made the call (the batch
+ * driver's OpenMP workers keep theirs to themselves).
+ * Per score there is also a BOUND (pnec_oracle_reprojection_score_error_bound): a running first-order error analysis of
+ * the triangulation, operation by operation, and of the two cosine terms through the direction of the triangulated point
+ * (ev_cosine_term).  It knows what a count of roundings does not -- that the triangulation divides by
+ * det = -sin^2(angle between f1 and R f2), a difference of two numbers near one, and that a triangulated point close to a
+ * camera centre has no direction to speak of.  On near-parallel rays with a large score (a gross outlier) two
+ * realisations of the score lie tens of thousands of ulps apart; at a small score on rays with parallax, tens.  The
+ * RATIO read-out is the smallest |score - threshold| / (2 bound) over the same scores -- 2 bound: what two realisations
+ * can differ by.  It costs a second evaluation per score, so it is computed only while
+ * pnec_oracle_set_ransac_margin_tracking(1) is in force, and reads NaN otherwise. */
+typedef struct { double v, e; } ev_t; /* a value and a bound of its absolute error */
+#define EV_U 1.1102230246251565e-16 /* 2^-53 */
+static inline ev_t ev_in(double v) { ev_t r = {v, 0.0}; return r; }
+static inline ev_t ev_add(ev_t a, ev_t b) { ev_t r = {a.v + b.v, 0.0}; r.e = a.e + b.e + EV_U * fabs(r.v); return r; }
+static inline ev_t ev_sub(ev_t a, ev_t b) { ev_t r = {a.v - b.v, 0.0}; r.e = a.e + b.e + EV_U * fabs(r.v); return r; }
+static inline ev_t ev_mul(ev_t a, ev_t b) {
+  ev_t r = {a.v * b.v, 0.0};
+  r.e = fabs(a.v) * b.e + fabs(b.v) * a.e + EV_U * fabs(r.v);
+  return r;
+}
+/* a quotient: the checker divides (u), the device multiplies (u) by fast_rcp (<= 1 ulp = 2 u): 3 u covers both */
+static inline ev_t ev_div(ev_t a, ev_t b) {
+  ev_t r = {a.v / b.v, 0.0};
+  r.e = (a.e + fabs(r.v) * b.e) / fabs(b.v) + 3.0 * EV_U * fabs(r.v);
+  return r;
+}
+/* a . b of three terms in ANY order of summation, fused or not: three products, two sums -> 3 u sum |a_i b_i| */
+static inline ev_t ev_dot3(const ev_t a[3], const ev_t b[3]) {
+  ev_t r = {0.0, 0.0};
+  double mag = 0.0;
+  for (int k = 0; k < 3; ++k) {
+    r.v += a[k].v * b[k].v;
+    mag += fabs(a[k].v * b[k].v);
+    r.e += fabs(a[k].v) * b[k].e + fabs(b[k].v) * a[k].e;
+  }
+  r.e += 3.0 * EV_U * mag;
+  return r;
+}
+/* One term 1 - f . x / |x| of the score, f a unit bearing, x a triangulated point with the error bounds it arrived with.
+ * The term is 1 - cos(theta), theta the angle between f and x, and depends on x through its DIRECTION alone: x turns by at
+ * most delta = |e_x| / |x|, which changes the term by sin(theta) delta + delta^2 / 2, sin(theta) <= sqrt(2 (1 - cos)).  (A
+ * bound that takes the errors of x's components one by one loses the factor sin(theta): a thousand at the scores an
+ * inlier threshold cuts through.)  Evaluating the term from x adds 12 u: f . x and x . x (3 u, and 3 u halved by the root),
+ * the root and the quotient -- or fast_rsqrt (< 1 ulp = 2 u) and a product -- (3 u), and the device's unit vector R f2 in
+ * the place of f2, 3 u off unit length; 10.5 u, rounded up. */
+static inline double ev_cosine_term(const ev_t f[3], const ev_t x[3]) {
+  double fx = 0.0, xx = 0.0, ee = 0.0;
+  for (int k = 0; k < 3; ++k) { fx += f[k].v * x[k].v; xx += x[k].v * x[k].v; ee += x[k].e * x[k].e; }
+  const double delta = sqrt(ee / xx), term = fabs(1.0 - fx / sqrt(xx));
+  return sqrt(2.0 * term) * delta + delta * delta + 12.0 * EV_U;
+}
+/* |computed - exact| <= this for the checker's evaluation of the score and for the device's (which forms u . d where the
+ * checker forms f2 . R'd: one rotation's worth of roundings less), to first order in u = 2^-53 */
+double pnec_oracle_reprojection_score_error_bound(const double f1_[3], const double f2_[3], const double R_[9],
+                                                  const double t_[3]) {
+  ev_t f1[3], f2[3], t[3], R[3][3], Rt[3][3], u[3], p[3], d[3], p2[3];
+  for (int k = 0; k < 3; ++k) {
+    f1[k] = ev_in(f1_[k]); f2[k] = ev_in(f2_[k]); t[k] = ev_in(t_[k]);
+    for (int c = 0; c < 3; ++c) { R[k][c] = ev_in(R_[3 * k + c]); Rt[c][k] = R[k][c]; }
+  }
+  for (int k = 0; k < 3; ++k) u[k] = ev_dot3(R[k], f2);
+  const ev_t b0 = ev_dot3(t, f1), b1 = ev_dot3(t, u);
+  const ev_t a00 = ev_dot3(f1, f1), a10 = ev_dot3(f1, u), uu = ev_dot3(u, u);
+  const ev_t det = ev_sub(ev_mul(a10, a10), ev_mul(a00, uu)); /* a00 a11 - a01 a10 with a11 = -u.u, a01 = -a10 */
+  const ev_t l0 = ev_div(ev_sub(ev_mul(a10, b1), ev_mul(uu, b0)), det);
+  const ev_t l1 = ev_div(ev_sub(ev_mul(a00, b1), ev_mul(a10, b0)), det);
+  for (int k = 0; k < 3; ++k) {
+    p[k] = ev_add(ev_add(ev_mul(l0, f1[k]), t[k]), ev_mul(l1, u[k]));
+    p[k].v *= 0.5; p[k].e *= 0.5;
+    d[k] = ev_sub(p[k], t[k]);
+  }
+  for (int k = 0; k < 3; ++k) p2[k] = ev_dot3(Rt[k], d);
+  return ev_cosine_term(f1, p) + ev_cosine_term(f2, p2) + 4.0 * EV_U; /* (1 - c1) + (1 - c2): three roundings of <= 2 */
+}
+static int g_ransac_margin_tracking = 0; /* process-wide, like the other switches: set it before, not during, a call */
+void pnec_oracle_set_ransac_margin_tracking(int on) { g_ransac_margin_tracking = on; }
+static double g_ransac_margin = INFINITY, g_ransac_margin_ratio = NAN;
+#pragma omp threadprivate(g_ransac_margin, g_ransac_margin_ratio)
+double pnec_oracle_ransac_last_margin(void) { return g_ransac_margin; }
+double pnec_oracle_ransac_last_margin_ratio(void) { return g_ransac_margin_ratio; }
+static inline int ransac_below_threshold(const double f1[3], const double f2[3], const double R[9], const double t[3],
+                                         double threshold) {
+  const double score = pnec_oracle_reprojection_score(f1, f2, R, t);
+  /* A score that is not a number (rays exactly parallel: det = 0), or one whose bound is not (a triangulated point exactly
+   * at a camera centre), is the least trustworthy of all: it takes the read-outs to ZERO.  fmin alone would drop it. */
+  const double dist = fabs(score - threshold);
+  g_ransac_margin = dist == dist ? fmin(g_ransac_margin, dist) : 0.0;
+  if (g_ransac_margin_tracking) {
+    const double ratio = dist / (2.0 * pnec_oracle_reprojection_score_error_bound(f1, f2, R, t));
+    g_ransac_margin_ratio = ratio == ratio ? fmin(g_ransac_margin_ratio, ratio) : 0.0; /* (inf / inf, x / NaN: NaN) */
+  }
+  return score < threshold;
+}
+/* ... and the model that call's final pass scored (the best hypothesis', before the eigensolver on its inliers): what a test
+ * needs to recompute the final mask's scores.  The start rotation and t = (0, 0, 1) when the call compared nothing. */
+static double g_ransac_model[12];
+#pragma omp threadprivate(g_ransac_model)
+void pnec_oracle_ransac_last_model(double R[9], double t[3]) {
+  memcpy(R, g_ransac_model, 9 * sizeof(double));
+  memcpy(t, g_ransac_model + 9, 3 * sizeof(double));
+}
+
 int pnec_oracle_ransac_eigensolver(int64_t n, const double *bvs1, const double *bvs2, const double R0[9],
                                    uint64_t seed, uint64_t pair_id, int max_iterations, int sample_size,
                                    double threshold, double R_out[9], double t_out[3], uint8_t *inlier_mask,
                                    int32_t *n_inliers, int32_t *iterations) {
+  g_ransac_margin = INFINITY;
+  g_ransac_margin_ratio = g_ransac_margin_tracking ? INFINITY : NAN;
+  memcpy(g_ransac_model, R0, 9 * sizeof(double));
+  g_ransac_model[9] = 0.0; g_ransac_model[10] = 0.0; g_ransac_model[11] = 1.0;
   if (sample_size > 16) sample_size = 16;
   if (n < sample_size || sample_size < 1) { /* cannot sample: plain eigensolver, everything an inlier */
     pnec_oracle_nec_eigensolver(n, bvs1, bvs2, R0, R_out, t_out);
@@ -691,7 +803,7 @@ int pnec_oracle_ransac_eigensolver(int64_t n, const double *bvs1, const double *
     const int cut_off = !g_ransac_frozen_rules && g_es_scheme == 0 && newton_its >= hyp_cap; /* (schemes 1, 2: every hypothesis
                                                                                               is scored, as opengv does) */
     for (int64_t i = 0; i < n && !cut_off; ++i)
-      count += pnec_oracle_reprojection_score(bvs1 + 3 * i, bvs2 + 3 * i, R, t) < threshold;
+      count += ransac_below_threshold(bvs1 + 3 * i, bvs2 + 3 * i, R, t, threshold);
     if (g_ransac_chained_starts && !cut_off) pnec_oracle_rot_to_cayley(R, v0); /* the scored model stays in the adapter */
     if (count > best_count) {
       best_count = count;
@@ -707,10 +819,12 @@ int pnec_oracle_ransac_eigensolver(int64_t n, const double *bvs1, const double *
     if (it > max_iterations) break;
   }
   /* inliers of the best model, then optimizeModelCoefficients on them */
+  memcpy(g_ransac_model, best_R, sizeof(best_R));
+  memcpy(g_ransac_model + 9, best_t, sizeof(best_t));
   int32_t cnt = 0;
   double *i1 = (double *)malloc(sizeof(double) * 3 * (size_t)n), *i2 = (double *)malloc(sizeof(double) * 3 * (size_t)n);
   for (int64_t i = 0; i < n; ++i) {
-    const int in = pnec_oracle_reprojection_score(bvs1 + 3 * i, bvs2 + 3 * i, best_R, best_t) < threshold;
+    const int in = ransac_below_threshold(bvs1 + 3 * i, bvs2 + 3 * i, best_R, best_t, threshold);
     inlier_mask[i] = (uint8_t)in;
     if (in) {
       memcpy(i1 + 3 * cnt, bvs1 + 3 * i, 3 * sizeof(double));
