@@ -35,7 +35,9 @@
  *    klt_patch_optical_flow.h:195-342 + POpticalFlowPatch::residual     pnec_hip_image_pyramid_level
  *    pnec_patch.h:139-170  (the iteration and the pyramid: no detection, no ids; double, not the reference's float)
  *   KLTPatchOpticalFlow::addPoints  klt_patch_optical_flow.h:344-385       pnec_hip_detect_keypoints
- *    (basalt's detectKeypoints on a grid + cv::FAST [EXT]: the detector only -- no ids, no track bookkeeping)
+ *    (basalt's detectKeypoints on a grid + cv::FAST [EXT]: the detector only)
+ *   KLTPatchOpticalFlow::processFrame klt_patch_optical_flow.h:121-191      pnec_hip_tracks_retain, pnec_hip_tracks_append,
+ *    (ids, the surviving tracks, the refill, a template image per track)     pnec_hip_patch_track_indexed
  *   PNEC::Eigensolver (no RANSAC) / WeightedEigensolver  pnec.cc:231-348   pnec_hip_nec_eigensolver /
  *                                                               pnec_hip_weighted_eigensolver
  *
@@ -779,8 +781,8 @@ int pnec_hip_patch_covariance(const void *images, int pixel_type, int64_t n_imag
  * halving step of the image pyramid it runs on (added within ABI 8: pure additions, PNEC_HIP_ABI_VERSION is unchanged).
  * This is the producer of pnec_hip_patch_covariance's positions and of its `angle`: trackPoints / trackPoint /
  * trackPointAtLevel (include/features/tracking/klt_patch_optical_flow.h:195-342) and POpticalFlowPatch::residual
- * (pnec_patch.h:139-170) on top of setFromImage as restated above.  Keypoint ids, the view graph and stereo filtering
- * are NOT here; FAST detection on the grid is pnec_hip_detect_keypoints below.  ALL ARITHMETIC IS DOUBLE; the
+ * (pnec_patch.h:139-170) on top of setFromImage as restated above.  The view graph and stereo filtering are NOT here;
+ * FAST detection on the grid is pnec_hip_detect_keypoints, keypoint ids and the tracks' bookkeeping pnec_hip_tracks_* below.  ALL ARITHMETIC IS DOUBLE; the
  * reference's float bits are not reproduced and not claimed.  [EXT] basalt's image.h (interp, InBounds), image_pyr.h (the pyramid) and Sophus (SE2::exp) are not in the
  * reference tree: they are restated from the published code, and what follows is this library's own definition.
  *
@@ -881,8 +883,8 @@ int pnec_hip_patch_track(const void *const *tmpl, const int64_t *tmpl_pitch, con
  * This is the producer of pnec_hip_patch_track's tmpl_pts: what KLTPatchOpticalFlow::addPoints
  * (include/features/tracking/klt_patch_optical_flow.h:344-385) gets from basalt's detectKeypoints(level image, kd,
  * optical_flow_detection_grid_size, 1, current points), called for the first frame (:145) and after every tracking step
- * (:180) to refill the grid cells whose tracks were lost.  Keypoint ids, the bookkeeping of tracks across frames, stereo
- * filtering and the view graph are NOT here.  INTEGER ARITHMETIC ON 8-BIT PIXELS: every output is exact.
+ * (:180) to refill the grid cells whose tracks were lost.  Keypoint ids and the bookkeeping of tracks across frames are
+ * pnec_hip_tracks_retain / _append below; stereo filtering and the view graph are NOT here.  INTEGER ARITHMETIC ON 8-BIT PIXELS: every output is exact.
  * [EXT] basalt's keypoints.cpp and OpenCV's cv::FAST, which it calls, are not in the reference tree: they are restated
  * from the published code, and what follows is this library's own definition.
  *
@@ -940,6 +942,102 @@ int pnec_hip_detect_keypoints(const void *images, int pixel_type, int64_t n_imag
                               const int64_t *cur_offsets, int64_t n_cur, const double *cur_pts, int32_t *out_cell,
                               int64_t *out_offsets, double *out_pts, int32_t *out_score, int32_t *out_cell_index,
                               int space, int device, void *stream);
+
+/* Tracks across frames: the bookkeeping of KLTPatchOpticalFlow::processFrame
+ * (include/features/tracking/klt_patch_optical_flow.h:121-191) on the device, and the tracker with a template image per
+ * track (added within ABI 8: pure additions, PNEC_HIP_ABI_VERSION is unchanged).  After trackPoints the reference keeps
+ * the tracks that came back valid in id order (`observations` is a std::map, :198-212, :282-283), hands their positions
+ * to addPoints as the occupied cells (:344-355) and gives every new corner the next id and an identity transform
+ * (:359-385); a track's patches are built in the frame it was born in (:361-369) and tracked for its whole life (:228).
+ * Stereo filtering and the view graph are NOT here.
+ *
+ * --- A track set.  Ragged over n_images images (sequences in lockstep): offsets int64 [n_images + 1] and arrays of
+ * n_rows rows; rows [offsets[f], offsets[f+1]) belong to image f, rows at and beyond offsets[n_images] are padding.
+ *   id          int64  [n_rows]     unique per image, >= 0                                     padding -1
+ *   tmpl_image  int32  [n_rows]     index of the birth image in a stack of template images     padding 0
+ *   tmpl_pts    double [n_rows, 2]  where the patch was built                                  padding NaN
+ *   age         int32  [n_rows]     frames since birth                                         padding 0
+ *   pts, angle  double [n_rows, 2], [n_rows]   the transform in the set's frame                padding NaN
+ *   cov         double [n_rows, 3]  the 2x2 covariance there (xx, xy, yy)                      padding NaN
+ * Both calls below write the padding themselves, to the end of the arrays, so the next pnec_hip_patch_track_indexed /
+ * _detect_keypoints / _patch_covariance call can be given the full n_rows as its n_points without reading a size back:
+ * a NaN template is BAD_TEMPLATE, a NaN current point marks no cell, a NaN point is an EMPTY patch.
+ * Positions come from counts and prefix sums, never from an atomic: the outputs are a function of the inputs alone, and
+ * an image's rows do not depend on the other images of the call, nor on `space`.
+ * DEVICE space: every array is device memory of `device`, nothing is allocated, nothing waits, the calls are
+ * asynchronous on `stream`; offsets are not checked (a row range is cut to the rows there are).  HOST space: everything
+ * is staged, the offsets are checked (from 0, non-decreasing, at most n_rows / n_det), the call blocks.
+ * Outputs are fresh arrays: none may be an input of the same call.
+ *
+ * --- pnec_hip_tracks_retain: the surviving tracks of one tracking step, compacted.
+ * Input: a set (its `angle` is not needed) and pnec_hip_patch_track's outputs for its rows, trk_pts / trk_angle / trk_cov
+ * / trk_status; max_age >= 0.  Row k is retained iff k < offsets[n_images], id[k] >= 0, trk_status[k] ==
+ * PNEC_HIP_TRACK_OK, and max_age == 0 or age[k] + 1 <= max_age.
+ * Output: a set of the same n_rows.  Per image the retained rows in their input order (stable: the reference's id order);
+ * id, tmpl_image, tmpl_pts copied; age + 1, saturating; pts / angle / cov = the track's outputs; out_prev_pts /
+ * out_prev_cov = the input set's pts / cov of the same track; out_src int64 = the input row (-1 in padding).  May be
+ * NULL: cov, trk_cov, out_cov and out_prev_cov (together), out_prev_pts, out_src.  The retained set is the
+ * correspondence list of the pair (previous frame, this frame): pnec_hip_problem_fill_keypoints takes out_prev_pts,
+ * out_pts, out_cov with out_offsets as they stand.
+ * PNEC_HIP_ERR_INVALID_ARGUMENT: n_images < 1, n_rows < 0, NULL offsets / out_offsets, with n_rows > 0 a NULL required
+ * array, the four covariance arrays not given together, max_age < 0, an output that is an input, a bad `space`; in HOST
+ * space also bad offsets.
+ *
+ * --- pnec_hip_tracks_append: addPoints' bookkeeping.
+ * Input: a set (absent on the first frame: offsets and all its pointers NULL, n_rows = 0; `cov` may be NULL);
+ * detections det_offsets [n_images + 1], det_pts [n_det, 2], det_cov [n_det, 3] or NULL (pnec_hip_detect_keypoints'
+ * outputs as they stand, n_det its capacity, and pnec_hip_patch_covariance there); tmpl_image_base >= 0 with
+ * tmpl_image_base + n_images - 1 fitting int32; per_image_capacity C >= 1; next_id int64 [n_images], read and written.
+ * For image f with a = offsets[f+1] - offsets[f] and d = det_offsets[f+1] - det_offsets[f]: take_a = min(a, C), take_d =
+ * min(d, C - take_a); its output rows are the first take_a set rows unchanged, then the first take_d detections, where
+ * detection r gets id = next_id[f] + r, tmpl_image = tmpl_image_base + f, tmpl_pts = pts = det_pts, age = 0, angle = 0,
+ * cov = det_cov or NaN; then next_id[f] += take_d, and out_dropped[f] = (a - take_a) + (d - take_d) (may be NULL).
+ * n_out rows are provided by the caller: at least min(n_images C, n_rows + n_det) -- checked from the arguments alone;
+ * HOST space also checks it against the rows the call produces.  Padding is written to n_out.  Ids are 64-bit throughout.
+ * PNEC_HIP_ERR_INVALID_ARGUMENT: n_images < 1, a negative count, a set given in part, NULL det_offsets / det_pts /
+ * next_id / out_offsets / (n_out > 0) a required output, C < 1, tmpl_image_base out of range, n_out too small, an output
+ * that is an input, a bad `space`; in HOST space also bad offsets.
+ *
+ * --- pnec_hip_patch_track_indexed: pnec_hip_patch_track with a template image per keypoint.
+ * pnec_hip_patch_track's arguments plus n_tmpl_images and tmpl_image int32 [n_points]: `tmpl` holds n_tmpl_images images
+ * per level, and keypoint k builds its templates -- and its out_cov -- in image tmpl_image[k] of `tmpl`; prev and next
+ * stay indexed by the keypoint's own image.  Everything else is pnec_hip_patch_track's definition, bit for bit: a call
+ * whose tmpl_image names, for every keypoint, an image with the pixels of its own image in a plain call returns the plain
+ * call's bits.  tmpl_image == NULL requires n_tmpl_images == n_images, means "the keypoint's own image" and runs
+ * pnec_hip_patch_track's kernel.  With tmpl_image, prev must not be NULL.  DEVICE space: the index is clamped to
+ * [0, n_tmpl_images - 1]; HOST space: an index outside that range is PNEC_HIP_ERR_INVALID_ARGUMENT.
+ *
+ * The frame loop (pnec_amd.Tracker): a ring of R >= 3 pyramids as one stack of R n_images images per level, frame n in
+ * slot n % R; per frame pyramid -> patch_track_indexed (tmpl = the stack, prev / next = two slots, init = the set) ->
+ * tracks_retain (max_age = R - 2) -> detect_keypoints (current = the retained set) -> patch_covariance ->
+ * tracks_append (tmpl_image_base = slot * n_images), none of which reads anything back.  DEVIATION: the reference keeps a
+ * track's patch for ever; here a track is retired when its age would reach R - 1, the step before its birth frame's slot
+ * is overwritten, and the pair loses that track's correspondence on that step. */
+int pnec_hip_tracks_retain(int64_t n_images, const int64_t *offsets, int64_t n_rows, const int64_t *id,
+                           const int32_t *tmpl_image, const double *tmpl_pts, const int32_t *age, const double *pts,
+                           const double *cov, const double *trk_pts, const double *trk_angle, const double *trk_cov,
+                           const int32_t *trk_status, int32_t max_age, int64_t *out_offsets, int64_t *out_id,
+                           int32_t *out_tmpl_image, double *out_tmpl_pts, int32_t *out_age, double *out_pts,
+                           double *out_angle, double *out_cov, double *out_prev_pts, double *out_prev_cov,
+                           int64_t *out_src, int space, int device, void *stream);
+int pnec_hip_tracks_append(int64_t n_images, const int64_t *offsets, int64_t n_rows, const int64_t *id,
+                           const int32_t *tmpl_image, const double *tmpl_pts, const int32_t *age, const double *pts,
+                           const double *angle, const double *cov, const int64_t *det_offsets, int64_t n_det,
+                           const double *det_pts, const double *det_cov, int32_t tmpl_image_base,
+                           int64_t per_image_capacity, int64_t *next_id, int64_t n_out, int64_t *out_offsets,
+                           int64_t *out_id, int32_t *out_tmpl_image, double *out_tmpl_pts, int32_t *out_age,
+                           double *out_pts, double *out_angle, double *out_cov, int64_t *out_dropped, int space,
+                           int device, void *stream);
+int pnec_hip_patch_track_indexed(const void *const *tmpl, const int64_t *tmpl_pitch, int64_t n_tmpl_images,
+                                 const void *const *prev, const int64_t *prev_pitch, const void *const *next,
+                                 const int64_t *next_pitch, int32_t n_levels, int pixel_type, int64_t n_images,
+                                 int32_t height, int32_t width, const int64_t *offsets, int64_t n_points,
+                                 const double *tmpl_pts, const int32_t *tmpl_image, const double *init_pts,
+                                 const double *init_angle, double shift_x, double shift_y, const double *pattern,
+                                 int32_t n_pattern, int32_t max_iterations, double max_recovered_dist2, uint32_t flags,
+                                 double scaling, double *out_pts, double *out_angle, double *out_cov,
+                                 double *out_dist2, int32_t *out_status, int32_t *out_lost_level, int space, int device,
+                                 void *stream);
 
 /* Name and launch geometry the auto-tuner would pick for this problem (for logs / profiles). */
 int pnec_hip_describe_launch(const pnec_hip_problem *p, const pnec_hip_options *opt,

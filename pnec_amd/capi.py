@@ -71,6 +71,9 @@ SYMBOLS = [
     "pnec_hip_image_pyramid_level",
     "pnec_hip_patch_track",
     "pnec_hip_detect_keypoints",
+    "pnec_hip_tracks_retain",
+    "pnec_hip_tracks_append",
+    "pnec_hip_patch_track_indexed",
     "pnec_hip_nec_eigensolver",
     "pnec_hip_ransac_eigensolver",
     "pnec_hip_problem_select",
@@ -230,6 +233,14 @@ def lib() -> C.CDLL:
                                                    C.c_double, C.c_uint32, C.c_double] + [_vp] * 6 + [C.c_int, C.c_int, _vp]
     L.pnec_hip_detect_keypoints.argtypes = [_vp, C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_int64] + [C.c_int32] * 4 + \
         [_vp, C.c_int64] + [_vp] * 6 + [C.c_int, C.c_int, _vp]
+    L.pnec_hip_tracks_retain.argtypes = [C.c_int64, _vp, C.c_int64] + [_vp] * 10 + [C.c_int32] + [_vp] * 11 + \
+        [C.c_int, C.c_int, _vp]
+    L.pnec_hip_tracks_append.argtypes = [C.c_int64, _vp, C.c_int64] + [_vp] * 8 + [C.c_int64, _vp, _vp, C.c_int32, C.c_int64,
+                                                                                 _vp, C.c_int64] + [_vp] * 9 + \
+        [C.c_int, C.c_int, _vp]
+    L.pnec_hip_patch_track_indexed.argtypes = [_vp, _vp, C.c_int64] + [_vp] * 4 + [
+        C.c_int32, C.c_int, C.c_int64, C.c_int32, C.c_int32, _vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp,
+        C.c_int32, C.c_int32, C.c_double, C.c_uint32, C.c_double] + [_vp] * 6 + [C.c_int, C.c_int, _vp]
     L.pnec_hip_describe_launch.argtypes = [_vp, C.POINTER(Options)] + [C.POINTER(C.c_int32)] * 5
     L.pnec_hip_unscented_transform.argtypes = [C.c_int64, _vp, _vp, _vp, C.c_double, C.c_int, _vp, _vp,
                                                C.c_int, C.c_int, _vp]

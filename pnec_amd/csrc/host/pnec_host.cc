@@ -551,6 +551,154 @@ Keypoints DetectKeypoints(const void *image, pnec_hip_pixel_type pixel_type, int
   return out;
 }
 
+Tracks RetainTracks(const Tracks &t, const PatchTracks &r, int max_age) {
+  const size_t n = t.id.size();
+  const bool cov = !t.covariances.empty() || n == 0;
+  if (t.tmpl_image.size() != n || t.age.size() != n || t.tmpl_points.size() != n || t.points.size() != n ||
+      (!t.covariances.empty() && t.covariances.size() != n))
+    throw std::invalid_argument("the arrays of a track set must have one entry per track");
+  if (r.points.size() != n || r.angles.size() != n || r.status.size() != n || (cov && r.covariances.size() != n))
+    throw std::invalid_argument("the track result must have one entry per track");
+  Tracks out;
+  if (n == 0) return out;
+  const double nan = std::nan("");
+  std::vector<int32_t> ti(t.tmpl_image.begin(), t.tmpl_image.end()), age(t.age.begin(), t.age.end()),
+      st(r.status.begin(), r.status.end()), o_ti(n), o_age(n);
+  out.id.assign(n, -1);
+  out.src.assign(n, -1);
+  out.tmpl_points.assign(n, {nan, nan});
+  out.points.assign(n, {nan, nan});
+  out.prev_points.assign(n, {nan, nan});
+  out.angles.assign(n, nan);
+  if (cov) {
+    out.covariances.assign(n, {nan, nan, nan});
+    out.prev_covariances.assign(n, {nan, nan, nan});
+  }
+  const int64_t offsets[2] = {0, (int64_t)n};
+  int64_t o_off[2] = {0, 0};
+  Check(pnec_hip_tracks_retain(1, offsets, (int64_t)n, t.id.data(), ti.data(), t.tmpl_points[0].data(), age.data(),
+                               t.points[0].data(), cov ? t.covariances[0].data() : nullptr, r.points[0].data(),
+                               r.angles.data(), cov ? r.covariances[0].data() : nullptr, st.data(), max_age, o_off,
+                               out.id.data(), o_ti.data(), out.tmpl_points[0].data(), o_age.data(), out.points[0].data(),
+                               out.angles.data(), cov ? out.covariances[0].data() : nullptr, out.prev_points[0].data(),
+                               cov ? out.prev_covariances[0].data() : nullptr, out.src.data(), PNEC_HIP_MEM_HOST,
+                               optimization::SolverOptions().device, nullptr));
+  const size_t m = (size_t)o_off[1];
+  out.id.resize(m);
+  out.src.resize(m);
+  out.tmpl_points.resize(m);
+  out.points.resize(m);
+  out.prev_points.resize(m);
+  out.angles.resize(m);
+  if (cov) {
+    out.covariances.resize(m);
+    out.prev_covariances.resize(m);
+  }
+  out.tmpl_image.assign(o_ti.begin(), o_ti.begin() + (std::ptrdiff_t)m);
+  out.age.assign(o_age.begin(), o_age.begin() + (std::ptrdiff_t)m);
+  return out;
+}
+
+Tracks AppendTracks(const Tracks *t, const Keypoints &det, const std::vector<std::array<double, 3>> *det_cov, int tmpl_image,
+                    int64_t capacity, int64_t *next_id, int64_t *dropped) {
+  if (!next_id) throw std::invalid_argument("next_id is NULL");
+  if (capacity < 1) throw std::invalid_argument("capacity must be >= 1");
+  const size_t n = t ? t->id.size() : 0, d = det.points.size();
+  if (t && (t->tmpl_image.size() != n || t->age.size() != n || t->tmpl_points.size() != n || t->points.size() != n ||
+            t->angles.size() != n || (!t->covariances.empty() && t->covariances.size() != n)))
+    throw std::invalid_argument("the arrays of a track set must have one entry per track");
+  if (det_cov && det_cov->size() != d) throw std::invalid_argument("det_covariances must have one entry per detection");
+  const bool set = t && n > 0, set_cov = set && !t->covariances.empty(), cov = det_cov || set_cov;
+  const size_t rows = std::min<size_t>((size_t)std::min<int64_t>(capacity, (int64_t)(n + d)), n + d);
+  const double nan = std::nan("");
+  Tracks out;
+  std::vector<int32_t> ti, age, o_ti(rows), o_age(rows);
+  if (set) {
+    ti.assign(t->tmpl_image.begin(), t->tmpl_image.end());
+    age.assign(t->age.begin(), t->age.end());
+  }
+  out.id.assign(rows, -1);
+  out.tmpl_points.assign(rows, {nan, nan});
+  out.points.assign(rows, {nan, nan});
+  out.angles.assign(rows, nan);
+  if (cov) out.covariances.assign(rows, {nan, nan, nan});
+  const int64_t offsets[2] = {0, (int64_t)n}, det_offsets[2] = {0, (int64_t)d};
+  int64_t o_off[2] = {0, 0}, drop = 0;
+  const std::array<double, 2> none2 = {nan, nan};
+  Check(pnec_hip_tracks_append(1, set ? offsets : nullptr, set ? (int64_t)n : 0, set ? t->id.data() : nullptr,
+                               set ? ti.data() : nullptr, set ? t->tmpl_points[0].data() : nullptr, set ? age.data() : nullptr,
+                               set ? t->points[0].data() : nullptr, set ? t->angles.data() : nullptr,
+                               set_cov ? t->covariances[0].data() : nullptr, det_offsets, (int64_t)d,
+                               d > 0 ? det.points[0].data() : none2.data(), det_cov && d > 0 ? (*det_cov)[0].data() : nullptr,
+                               tmpl_image, capacity, next_id, (int64_t)rows, o_off, rows ? out.id.data() : nullptr,
+                               o_ti.data(), rows ? out.tmpl_points[0].data() : nullptr, o_age.data(),
+                               rows ? out.points[0].data() : nullptr, out.angles.data(),
+                               cov && rows ? out.covariances[0].data() : nullptr, &drop, PNEC_HIP_MEM_HOST,
+                               optimization::SolverOptions().device, nullptr));
+  out.tmpl_image.assign(o_ti.begin(), o_ti.end());
+  out.age.assign(o_age.begin(), o_age.end());
+  if (dropped) *dropped = drop;
+  return out;
+}
+
+PatchTracks TrackPatches(const std::vector<const Pyramid *> &stack, const std::vector<int> &tmpl_image, const Pyramid &prev,
+                         const Pyramid &next, const std::vector<std::array<double, 2>> &points, const TrackOptions &options,
+                         const std::vector<std::array<double, 2>> *init_points, const std::vector<double> *init_angles,
+                         const std::vector<std::array<double, 2>> *pattern) {
+  const size_t n = points.size(), L = next.levels.size(), S = stack.size();
+  if (L < 1 || L > PNEC_HIP_TRACK_MAX_LEVELS) throw std::invalid_argument("a pyramid must have 1 .. 8 levels");
+  if (S < 1) throw std::invalid_argument("the template stack is empty");
+  if (tmpl_image.size() != n) throw std::invalid_argument("tmpl_image must have one entry per keypoint");
+  std::vector<const Pyramid *> all(stack);
+  all.push_back(&prev);
+  for (const Pyramid *p : all)
+    if (!p || p->levels.size() != L || p->height != next.height || p->width != next.width || p->pixel_type != next.pixel_type)
+      throw std::invalid_argument("the pyramids must have the same levels, size and pixel type");
+  if ((init_points && init_points->size() != n) || (init_angles && init_angles->size() != n))
+    throw std::invalid_argument("init_points / init_angles must have one entry per keypoint");
+  const std::vector<std::array<double, 2>> &pat = pattern ? *pattern : Pattern52();
+  const double nan = std::nan("");
+  PatchTracks out;
+  out.points.assign(n, std::array<double, 2>{nan, nan});
+  out.angles.assign(n, nan);
+  out.covariances.assign(n, std::array<double, 3>{nan, nan, nan});
+  out.dist2.assign(n, nan);
+  std::vector<int32_t> st(n, PNEC_HIP_TRACK_BAD_TEMPLATE), lv(n, -1), ti(tmpl_image.begin(), tmpl_image.end());
+  if (n > 0) {
+    // the stack as one block of S images per level
+    std::vector<std::vector<unsigned char>> block(L);
+    const void *tp[PNEC_HIP_TRACK_MAX_LEVELS], *np[PNEC_HIP_TRACK_MAX_LEVELS], *pp[PNEC_HIP_TRACK_MAX_LEVELS];
+    int64_t pitch[PNEC_HIP_TRACK_MAX_LEVELS];
+    const size_t es = PixelBytes(next.pixel_type);
+    for (size_t l = 0; l < L; ++l) {
+      pitch[l] = next.width >> l;
+      const size_t bytes = (size_t)(next.height >> l) * (size_t)(next.width >> l) * es;
+      all.push_back(&next);
+      for (const Pyramid *p : all)
+        if (p->levels[l].size() != bytes) throw std::invalid_argument("a pyramid level has the wrong size");
+      all.pop_back();
+      block[l].resize(bytes * S);
+      for (size_t i = 0; i < S; ++i) std::memcpy(block[l].data() + i * bytes, stack[i]->levels[l].data(), bytes);
+      tp[l] = block[l].data();
+      np[l] = next.levels[l].data();
+      pp[l] = prev.levels[l].data();
+    }
+    const int64_t offsets[2] = {0, (int64_t)n};
+    Check(pnec_hip_patch_track_indexed(tp, pitch, (int64_t)S, pp, pitch, np, pitch, (int32_t)L, (int)next.pixel_type, 1,
+                                       next.height, next.width, offsets, (int64_t)n, points[0].data(), ti.data(),
+                                       init_points ? (*init_points)[0].data() : nullptr,
+                                       init_angles ? init_angles->data() : nullptr, options.shift[0], options.shift[1],
+                                       pat.empty() ? nullptr : pat[0].data(), (int32_t)pat.size(), options.max_iterations,
+                                       options.max_recovered_dist2, options.backward ? 0u : PNEC_HIP_TRACK_NO_BACKWARD,
+                                       options.scaling, out.points[0].data(), out.angles.data(), out.covariances[0].data(),
+                                       out.dist2.data(), st.data(), lv.data(), PNEC_HIP_MEM_HOST,
+                                       optimization::SolverOptions().device, nullptr));
+  }
+  out.status.assign(st.begin(), st.end());
+  out.lost_level.assign(lv.begin(), lv.end());
+  return out;
+}
+
 }  // namespace features
 
 // -------------------------------------------------------------------------------- optimization

@@ -174,7 +174,8 @@ std::vector<std::array<double, 3>> PatchCovariances(const void *image, pnec_hip_
 // Addition: the tracker itself -- KLTPatchOpticalFlow::trackPoints / trackPoint / trackPointAtLevel
 // (klt_patch_optical_flow.h:195-342) and POpticalFlowPatch::residual (pnec_patch.h:139-170) on basalt's image pyramid
 // [EXT] -- for one image pair, in double: pnec_hip_image_pyramid_level and pnec_hip_patch_track, include/pnec_hip.h has
-// the definitions.  Detection, keypoint ids and the view graph are the caller's.
+// the definitions.  Detection is DetectKeypoints, ids and bookkeeping RetainTracks / AppendTracks; the view graph is the
+// caller's.
 struct Pyramid {
   pnec_hip_pixel_type pixel_type = PNEC_HIP_PIXEL_U8;
   int height = 0, width = 0;                  // of level 0; level l is (height >> l) x (width >> l), rows packed
@@ -206,7 +207,8 @@ PatchTracks TrackPatches(const Pyramid &tmpl, const Pyramid &next, const std::ve
 
 // Addition: the detector that feeds the tracker -- what KLTPatchOpticalFlow::addPoints (klt_patch_optical_flow.h:344-385)
 // gets from basalt's detectKeypoints [EXT]: grid FAST-9 corners of one uint8 / uint16 image, integer arithmetic --
-// pnec_hip_detect_keypoints, include/pnec_hip.h has the definition.  Keypoint ids and the track bookkeeping are the caller's.
+// pnec_hip_detect_keypoints, include/pnec_hip.h has the definition.  Keypoint ids and the track bookkeeping: RetainTracks /
+// AppendTracks below.
 struct DetectOptions {
   int grid = 30;                              // optical_flow_detection_grid_size (8 .. 64)
   int points_per_cell = 1;                    // 1 .. 4; the reference passes 1
@@ -223,6 +225,41 @@ struct Keypoints {
 Keypoints DetectKeypoints(const void *image, pnec_hip_pixel_type pixel_type, int height, int width, int64_t pitch,
                           const DetectOptions &options = DetectOptions(),
                           const std::vector<std::array<double, 2>> *current = nullptr);
+
+// Addition: the bookkeeping of KLTPatchOpticalFlow::processFrame (klt_patch_optical_flow.h:121-191) for one image --
+// pnec_hip_tracks_retain, pnec_hip_tracks_append and pnec_hip_patch_track_indexed, include/pnec_hip.h has the definitions.
+// A track keeps the image it was born in as its template (tmpl_image: an index into a stack of pyramids the caller
+// keeps).  DEVIATION when that stack is a ring: the reference keeps a patch for ever, a ring of R frames retires a track
+// when its age would reach R - 1 (max_age = R - 2), which costs the pair that track's correspondence on that step.
+struct Tracks {
+  std::vector<int64_t> id;                          // unique, >= 0
+  std::vector<int> tmpl_image, age;                 // the birth image in the caller's stack; frames since birth
+  std::vector<std::array<double, 2>> tmpl_points;   // where the patch was built
+  std::vector<std::array<double, 2>> points;        // the transform in the set's frame
+  std::vector<double> angles;
+  std::vector<std::array<double, 3>> covariances;   // (xx, xy, yy); empty: none
+  // a retained set: the same track in the set it was retained from -- (prev_points, points, covariances) are the
+  // correspondences of the pair -- and the row it had there
+  std::vector<std::array<double, 2>> prev_points;
+  std::vector<std::array<double, 3>> prev_covariances;
+  std::vector<int64_t> src;
+};
+// the tracks of `tracks` that `result` (TrackPatches' output for its rows) brought back with PNEC_HIP_TRACK_OK and, with
+// max_age > 0, whose age + 1 stays <= max_age: in their order, age + 1, the tracked transform and covariance
+Tracks RetainTracks(const Tracks &tracks, const PatchTracks &result, int max_age = 0);
+// `tracks` (nullptr: none yet) cut to `capacity` rows and refilled with as many of `detections` as still fit: ids from
+// *next_id (advanced), tmpl_image, age 0, identity transform, det_covariances (nullptr: NaN).  *dropped: what did not fit.
+Tracks AppendTracks(const Tracks *tracks, const Keypoints &detections,
+                    const std::vector<std::array<double, 3>> *det_covariances, int tmpl_image, int64_t capacity,
+                    int64_t *next_id, int64_t *dropped = nullptr);
+// The indexed form of TrackPatches: keypoint k builds its templates in pyramid tmpl_image[k] of `tmpl_stack` (all of one
+// size and pixel type) and is tracked from `prev` (where init_points / init_angles hold) into `next` and back.
+PatchTracks TrackPatches(const std::vector<const Pyramid *> &tmpl_stack, const std::vector<int> &tmpl_image,
+                         const Pyramid &prev, const Pyramid &next, const std::vector<std::array<double, 2>> &tmpl_points,
+                         const TrackOptions &options = TrackOptions(),
+                         const std::vector<std::array<double, 2>> *init_points = nullptr,
+                         const std::vector<double> *init_angles = nullptr,
+                         const std::vector<std::array<double, 2>> *pattern = nullptr);
 }  // namespace features
 
 namespace optimization {

@@ -13,6 +13,7 @@
 #include <pybind11/stl.h>
 
 #include <array>
+#include <string>
 #include <vector>
 
 #include "pnec_host.h"
@@ -376,6 +377,93 @@ py::tuple patch_track(py::array image1, py::array image2, arr points, int levels
   return py::make_tuple(P, A, Cv, D, S, Lv);
 }
 
+using iarr64 = py::array_t<int64_t, py::array::c_style | py::array::forcecast>;
+using iarr32 = py::array_t<int32_t, py::array::c_style | py::array::forcecast>;
+
+template <size_t W>
+std::vector<std::array<double, W>> rows_of(const arr &a, const char *what) {
+  if (a.ndim() != 2 || a.shape(1) != (py::ssize_t)W) throw std::invalid_argument(std::string(what) + " has the wrong shape");
+  std::vector<std::array<double, W>> v((size_t)a.shape(0));
+  auto r = a.unchecked<2>();
+  for (py::ssize_t i = 0; i < a.shape(0); ++i)
+    for (size_t k = 0; k < W; ++k) v[(size_t)i][k] = r(i, (py::ssize_t)k);
+  return v;
+}
+template <size_t W>
+py::array_t<double> array_of(const std::vector<std::array<double, W>> &v) {
+  py::array_t<double> a({(py::ssize_t)v.size(), (py::ssize_t)W});
+  auto w = a.mutable_unchecked<2>();
+  for (size_t i = 0; i < v.size(); ++i)
+    for (size_t k = 0; k < W; ++k) w((py::ssize_t)i, (py::ssize_t)k) = v[i][k];
+  return a;
+}
+template <typename T, typename V>
+py::array_t<T> vector_of(const V &v) {
+  py::array_t<T> a((py::ssize_t)v.size());
+  auto w = a.template mutable_unchecked<1>();
+  for (size_t i = 0; i < v.size(); ++i) w((py::ssize_t)i) = (T)v[i];
+  return a;
+}
+
+pnec::features::Tracks tracks_of(iarr64 id, iarr32 tmpl_image, arr tmpl_pts, iarr32 age, arr pts, py::object angle,
+                                 py::object cov) {
+  pnec::features::Tracks t;
+  t.id.assign(id.data(), id.data() + id.size());
+  t.tmpl_image.assign(tmpl_image.data(), tmpl_image.data() + tmpl_image.size());
+  t.age.assign(age.data(), age.data() + age.size());
+  t.tmpl_points = rows_of<2>(tmpl_pts, "tmpl_pts");
+  t.points = rows_of<2>(pts, "pts");
+  if (!angle.is_none()) {
+    arr a = angle.cast<arr>();
+    t.angles.assign(a.data(), a.data() + a.size());
+  }
+  if (!cov.is_none()) t.covariances = rows_of<3>(cov.cast<arr>(), "cov");
+  return t;
+}
+
+// one image's surviving tracks: (id, tmpl_image, tmpl_pts, age, pts, angle, cov or None, prev_pts, prev_cov or None,
+// src), trimmed to the retained rows -- the first offsets[1] rows of pnec_amd.retain_tracks
+py::tuple retain_tracks(iarr64 id, iarr32 tmpl_image, arr tmpl_pts, iarr32 age, arr pts, py::object cov, arr trk_pts,
+                        arr trk_angle, py::object trk_cov, iarr32 trk_status, int max_age) {
+  if (cov.is_none() != trk_cov.is_none()) throw std::invalid_argument("cov and trk_cov are given or None together");
+  const pnec::features::Tracks t = tracks_of(id, tmpl_image, tmpl_pts, age, pts, py::none(), cov);
+  pnec::features::PatchTracks r;
+  r.points = rows_of<2>(trk_pts, "trk_pts");
+  r.angles.assign(trk_angle.data(), trk_angle.data() + trk_angle.size());
+  if (!trk_cov.is_none()) r.covariances = rows_of<3>(trk_cov.cast<arr>(), "trk_cov");
+  r.status.assign(trk_status.data(), trk_status.data() + trk_status.size());
+  const pnec::features::Tracks o = pnec::features::RetainTracks(t, r, max_age);
+  const bool c = !cov.is_none();
+  return py::make_tuple(vector_of<int64_t>(o.id), vector_of<int32_t>(o.tmpl_image), array_of<2>(o.tmpl_points),
+                        vector_of<int32_t>(o.age), array_of<2>(o.points), vector_of<double>(o.angles),
+                        c ? py::object(array_of<3>(o.covariances)) : py::object(py::none()), array_of<2>(o.prev_points),
+                        c ? py::object(array_of<3>(o.prev_covariances)) : py::object(py::none()), vector_of<int64_t>(o.src));
+}
+
+// one image's refill: ((id, tmpl_image, tmpl_pts, age, pts, angle, cov or None), next_id after, dropped); `tracks` is
+// None or the tuple (id, tmpl_image, tmpl_pts, age, pts, angle, cov or None)
+py::tuple append_tracks(py::object tracks, arr det_pts, py::object det_cov, int tmpl_image, int64_t capacity, int64_t next_id) {
+  pnec::features::Tracks t;
+  const bool have = !tracks.is_none();
+  if (have) {
+    py::tuple s = tracks.cast<py::tuple>();
+    if (s.size() != 7) throw std::invalid_argument("tracks must be (id, tmpl_image, tmpl_pts, age, pts, angle, cov or None)");
+    t = tracks_of(s[0].cast<iarr64>(), s[1].cast<iarr32>(), s[2].cast<arr>(), s[3].cast<iarr32>(), s[4].cast<arr>(), s[5], s[6]);
+  }
+  pnec::features::Keypoints k;
+  k.points = rows_of<2>(det_pts, "det_pts");
+  std::vector<std::array<double, 3>> dc;
+  if (!det_cov.is_none()) dc = rows_of<3>(det_cov.cast<arr>(), "det_cov");
+  int64_t dropped = 0;
+  const pnec::features::Tracks o = pnec::features::AppendTracks(have ? &t : nullptr, k, det_cov.is_none() ? nullptr : &dc,
+                                                                tmpl_image, capacity, &next_id, &dropped);
+  const bool c = !o.covariances.empty() || (o.id.empty() && !det_cov.is_none());
+  return py::make_tuple(py::make_tuple(vector_of<int64_t>(o.id), vector_of<int32_t>(o.tmpl_image), array_of<2>(o.tmpl_points),
+                                       vector_of<int32_t>(o.age), array_of<2>(o.points), vector_of<double>(o.angles),
+                                       c ? py::object(array_of<3>(o.covariances)) : py::object(py::none())),
+                        next_id, dropped);
+}
+
 // (pts [N,2], score [N], cell_index [N], cell [n_cells]) of the grid FAST-9 corners of one uint8 / uint16 image
 py::tuple detect_keypoints(py::array image, int grid, int points_per_cell, int min_threshold, int edge, py::object current) {
   if (image.ndim() != 2) throw std::invalid_argument("image must be [h,w]");
@@ -527,6 +615,15 @@ PYBIND11_MODULE(pypnec, m) {
         "pnec::features::TrackPatches (addition; device): (pts [N,2], angle [N], cov [N,3], dist2 [N], status [N], "
         "lost_level [N]) of the Pattern52 patches at `points` of image1 tracked into image2 and back, in double -- "
         "include/pnec_hip.h pnec_hip_patch_track");
+  m.def("retain_tracks", &retain_tracks, py::arg("id"), py::arg("tmpl_image"), py::arg("tmpl_pts"), py::arg("age"),
+        py::arg("pts"), py::arg("cov"), py::arg("trk_pts"), py::arg("trk_angle"), py::arg("trk_cov"), py::arg("trk_status"),
+        py::arg("max_age") = 0,
+        "(id, tmpl_image, tmpl_pts, age, pts, angle, cov, prev_pts, prev_cov, src) of one image's tracks that came back OK "
+        "(and young enough), compacted in order; include/pnec_hip.h pnec_hip_tracks_retain");
+  m.def("append_tracks", &append_tracks, py::arg("tracks"), py::arg("det_pts"), py::arg("det_cov"), py::arg("tmpl_image"),
+        py::arg("capacity"), py::arg("next_id"),
+        "((id, tmpl_image, tmpl_pts, age, pts, angle, cov), next_id, dropped): one image's tracks refilled with detections "
+        "up to `capacity`; include/pnec_hip.h pnec_hip_tracks_append");
   m.def("detect_keypoints", &detect_keypoints, py::arg("image"), py::arg("grid") = 30, py::arg("points_per_cell") = 1,
         py::arg("min_threshold") = 5, py::arg("edge") = 19, py::arg("current") = py::none(),
         "pnec::features::DetectKeypoints (addition; device): (pts [N,2], score [N], cell_index [N], cell [n_cells]) -- the "

@@ -22,6 +22,7 @@
 #include "pnec_pose_cov.hpp"
 #include "pnec_residuals.hpp"
 #include "pnec_relative_scale.hpp"
+#include "pnec_tracks.hpp"
 #include "pnec_triangulate.hpp"
 #include "pnec_solve_kernel.hpp"
 #include "pnec_solve_group_kernel.hpp"
@@ -1336,53 +1337,67 @@ int pnec_hip_image_pyramid_level(const void *in, void *out, int pixel_type, int6
   return io.finish();
 }
 
-int pnec_hip_patch_track(const void *const *tmpl, const int64_t *tmpl_pitch, const void *const *prev,
-                         const int64_t *prev_pitch, const void *const *next, const int64_t *next_pitch,
-                         int32_t n_levels, int pixel_type, int64_t n_images, int32_t height, int32_t width,
-                         const int64_t *offsets, int64_t n_points, const double *tmpl_pts, const double *init_pts,
-                         const double *init_angle, double shift_x, double shift_y, const double *pattern,
-                         int32_t n_pattern, int32_t max_iterations, double max_recovered_dist2, uint32_t flags,
-                         double scaling, double *out_pts, double *out_angle, double *out_cov, double *out_dist2,
-                         int32_t *out_status, int32_t *out_lost_level, int space, int device, void *stream_) {
+// pnec_hip_patch_track (tmpl_image NULL, n_tmpl_images = n_images) and pnec_hip_patch_track_indexed: one body
+static int run_patch_track(const char *name, const void *const *tmpl, const int64_t *tmpl_pitch, const void *const *prev,
+                           const int64_t *prev_pitch, const void *const *next, const int64_t *next_pitch,
+                           int32_t n_levels, int pixel_type, int64_t n_images, int64_t n_tmpl_images, int32_t height,
+                           int32_t width, const int64_t *offsets, int64_t n_points, const double *tmpl_pts,
+                           const int32_t *tmpl_image, const double *init_pts, const double *init_angle, double shift_x,
+                           double shift_y, const double *pattern, int32_t n_pattern, int32_t max_iterations,
+                           double max_recovered_dist2, uint32_t flags, double scaling, double *out_pts,
+                           double *out_angle, double *out_cov, double *out_dist2, int32_t *out_status,
+                           int32_t *out_lost_level, int space, int device, void *stream_) {
+  const std::string pre = std::string(name) + ": ";
+  const bool prev_given = prev != nullptr;
   if (!prev) {
     prev = tmpl;
     prev_pitch = tmpl_pitch;
   }
   if (!tmpl || !tmpl_pitch || !prev_pitch || !next || !next_pitch || !offsets || !pattern || (!tmpl_pts && n_points > 0))
     return fail(PNEC_HIP_ERR_INVALID_ARGUMENT,
-                "patch_track: tmpl, next, a pitch array, offsets, tmpl_pts or pattern is NULL");
+                pre + "tmpl, next, a pitch array, offsets, tmpl_pts or pattern is NULL");
   if (!out_pts && !out_angle && !out_cov && !out_dist2 && !out_status && !out_lost_level)
-    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_track: every output is NULL");
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "every output is NULL");
   if (n_levels < 1 || n_levels > PNEC_HIP_TRACK_MAX_LEVELS)
-    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_track: n_levels must be 1 .. 8");
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "n_levels must be 1 .. 8");
   if (max_iterations < 1 || max_iterations > 255)
-    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_track: max_iterations must be 1 .. 255");
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "max_iterations must be 1 .. 255");
   if (n_pattern < 1 || n_pattern > PNEC_HIP_PATCH_MAX_POINTS)
-    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_track: n_pattern must be 1 .. 64");
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "n_pattern must be 1 .. 64");
   const size_t elem = pixel_bytes(pixel_type);
-  if (!elem) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_track: unknown pixel_type");
-  if (flags & ~PNEC_HIP_TRACK_NO_BACKWARD) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_track: unknown flags");
+  if (!elem) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "unknown pixel_type");
+  if (flags & ~PNEC_HIP_TRACK_NO_BACKWARD) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "unknown flags");
   if (n_images < 1 || n_points < 0)
-    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_track: n_images must be >= 1, n_points >= 0");
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "n_images must be >= 1, n_points >= 0");
+  // (the plain call passes n_tmpl_images = n_images and no tmpl_image: none of the three can fire for it)
+  if (n_tmpl_images < 1) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "n_tmpl_images must be >= 1");
+  if (!tmpl_image && n_tmpl_images != n_images)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "without tmpl_image, n_tmpl_images must equal n_images");
+  if (tmpl_image && !prev_given)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "with tmpl_image, prev must be given (tmpl is a stack of other images)");
   if (height < 1 || width < 1 || (height >> (n_levels - 1)) < 4 || (width >> (n_levels - 1)) < 4)
-    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_track: the smallest level is below 4 pixels in height or width");
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "the smallest level is below 4 pixels in height or width");
   for (int l = 0; l < n_levels; ++l) {
-    if (!tmpl[l] || !prev[l] || !next[l]) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_track: a level pointer is NULL");
+    if (!tmpl[l] || !prev[l] || !next[l]) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "a level pointer is NULL");
     if (tmpl_pitch[l] < (width >> l) || prev_pitch[l] < (width >> l) || next_pitch[l] < (width >> l))
-      return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_track: a pitch (in elements) is below its level's width");
+      return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "a pitch (in elements) is below its level's width");
   }
   if (!(max_recovered_dist2 >= 0.0))
-    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_track: max_recovered_dist2 must be >= 0");
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "max_recovered_dist2 must be >= 0");
   if (!std::isfinite(shift_x) || !std::isfinite(shift_y))
-    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_track: shift must be finite");
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "shift must be finite");
   if (!(scaling > 0.0) || !std::isfinite(scaling))
-    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "patch_track: scaling must be positive and finite");
-  if (int rc = check_space("patch_track: ", space)) return rc;
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "scaling must be positive and finite");
+  if (int rc = check_space(pre, space)) return rc;
   for (int l = 0; l < n_levels; ++l)
     for (const int64_t pitch : {tmpl_pitch[l], prev_pitch[l], next_pitch[l]})
-      if (int rc = check_images_fit("patch_track", n_images, height >> l, pitch, elem)) return rc;
+      if (int rc = check_images_fit(name, std::max(n_images, n_tmpl_images), height >> l, pitch, elem)) return rc;
   if (space == PNEC_HIP_MEM_HOST)
-    if (int rc = check_offsets("patch_track", "offsets", offsets, n_images, n_points, "n_points")) return rc;
+    if (int rc = check_offsets(name, "offsets", offsets, n_images, n_points, "n_points")) return rc;
+  if (space == PNEC_HIP_MEM_HOST && tmpl_image)
+    for (int64_t k = 0; k < n_points; ++k)
+      if (tmpl_image[k] < 0 || tmpl_image[k] >= n_tmpl_images)
+        return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "a tmpl_image entry lies outside 0 .. n_tmpl_images - 1");
   if (n_points == 0) return 0;
   hipStream_t stream = (hipStream_t)stream_;
   CallArrays io(device, space, stream);
@@ -1405,11 +1420,13 @@ int pnec_hip_patch_track(const void *const *tmpl, const int64_t *tmpl_pitch, con
     a.next.pitch[l] = next_pitch[l];
   }
   const int64_t M = n_points;
-  auto level_bytes = [&](int l, int64_t pitch) { return image_block_bytes(elem, n_images, height >> l, pitch, width >> l); };
+  auto level_bytes = [&](int l, int64_t pitch, int64_t n = -1) {
+    return image_block_bytes(elem, n < 0 ? n_images : n, height >> l, pitch, width >> l);
+  };
   // a level that two pyramids share (prev = tmpl) is staged once
-  auto shared = [&](int l) { return prev[l] == tmpl[l] && prev_pitch[l] == tmpl_pitch[l]; };
+  auto shared = [&](int l) { return !tmpl_image && prev[l] == tmpl[l] && prev_pitch[l] == tmpl_pitch[l]; };
   for (int l = 0; l < n_levels; ++l) {
-    io.in_bytes(a.tmpl.level[l], tmpl[l], level_bytes(l, tmpl_pitch[l]));
+    io.in_bytes(a.tmpl.level[l], tmpl[l], level_bytes(l, tmpl_pitch[l], n_tmpl_images));
     io.in_bytes(a.next.level[l], next[l], level_bytes(l, next_pitch[l]));
     if (!shared(l)) io.in_bytes(a.prev.level[l], prev[l], level_bytes(l, prev_pitch[l]));
   }
@@ -1417,6 +1434,8 @@ int pnec_hip_patch_track(const void *const *tmpl, const int64_t *tmpl_pitch, con
   io.in(a.tmpl_pts, tmpl_pts, 2 * M);
   io.in(a.init_pts, init_pts, 2 * M);
   io.in(a.init_angle, init_angle, M);
+  const int32_t *d_tmpl_image = nullptr;
+  io.in(d_tmpl_image, tmpl_image, M);
   io.in(a.pattern, pattern, 2 * (int64_t)n_pattern);
   io.out(a.out_pts, out_pts, 2 * M);
   io.out(a.out_angle, out_angle, M);
@@ -1427,7 +1446,204 @@ int pnec_hip_patch_track(const void *const *tmpl, const int64_t *tmpl_pitch, con
   if (int rc = io.commit()) return rc;
   for (int l = 0; l < n_levels; ++l)
     if (shared(l)) a.prev.level[l] = a.tmpl.level[l];
-  PNEC_HIP_TRY(launch_patch_track(pixel_type, a, stream));
+  if (tmpl_image) PNEC_HIP_TRY(launch_patch_track_indexed(pixel_type, a, d_tmpl_image, n_tmpl_images, stream));
+  else PNEC_HIP_TRY(launch_patch_track(pixel_type, a, stream));
+  return io.finish();
+}
+
+int pnec_hip_patch_track(const void *const *tmpl, const int64_t *tmpl_pitch, const void *const *prev,
+                         const int64_t *prev_pitch, const void *const *next, const int64_t *next_pitch,
+                         int32_t n_levels, int pixel_type, int64_t n_images, int32_t height, int32_t width,
+                         const int64_t *offsets, int64_t n_points, const double *tmpl_pts, const double *init_pts,
+                         const double *init_angle, double shift_x, double shift_y, const double *pattern,
+                         int32_t n_pattern, int32_t max_iterations, double max_recovered_dist2, uint32_t flags,
+                         double scaling, double *out_pts, double *out_angle, double *out_cov, double *out_dist2,
+                         int32_t *out_status, int32_t *out_lost_level, int space, int device, void *stream_) {
+  return run_patch_track("patch_track", tmpl, tmpl_pitch, prev, prev_pitch, next, next_pitch, n_levels, pixel_type,
+                         n_images, n_images, height, width, offsets, n_points, tmpl_pts, nullptr, init_pts, init_angle,
+                         shift_x, shift_y, pattern, n_pattern, max_iterations, max_recovered_dist2, flags, scaling,
+                         out_pts, out_angle, out_cov, out_dist2, out_status, out_lost_level, space, device, stream_);
+}
+
+int pnec_hip_patch_track_indexed(const void *const *tmpl, const int64_t *tmpl_pitch, int64_t n_tmpl_images,
+                                 const void *const *prev, const int64_t *prev_pitch, const void *const *next,
+                                 const int64_t *next_pitch, int32_t n_levels, int pixel_type, int64_t n_images,
+                                 int32_t height, int32_t width, const int64_t *offsets, int64_t n_points,
+                                 const double *tmpl_pts, const int32_t *tmpl_image, const double *init_pts,
+                                 const double *init_angle, double shift_x, double shift_y, const double *pattern,
+                                 int32_t n_pattern, int32_t max_iterations, double max_recovered_dist2, uint32_t flags,
+                                 double scaling, double *out_pts, double *out_angle, double *out_cov,
+                                 double *out_dist2, int32_t *out_status, int32_t *out_lost_level, int space, int device,
+                                 void *stream_) {
+  return run_patch_track("patch_track_indexed", tmpl, tmpl_pitch, prev, prev_pitch, next, next_pitch, n_levels,
+                         pixel_type, n_images, n_tmpl_images, height, width, offsets, n_points, tmpl_pts, tmpl_image,
+                         init_pts, init_angle, shift_x, shift_y, pattern, n_pattern, max_iterations, max_recovered_dist2,
+                         flags, scaling, out_pts, out_angle, out_cov, out_dist2, out_status, out_lost_level, space,
+                         device, stream_);
+}
+
+// the bookkeeping of tracks across frames: pnec_tracks.hip.  No batch and no images: staged like the patch covariances.
+// HOST space only (the array is read): a set's offsets run from 0 up to at most n_rows without a step down.
+static int check_set_offsets(const std::string &pre, const char *array, const int64_t *offsets, int64_t n, int64_t rows,
+                             const char *rows_name) {
+  bool ok = offsets[0] == 0 && offsets[n] <= rows;
+  for (int64_t f = 0; ok && f < n; ++f) ok = offsets[f] <= offsets[f + 1];
+  if (!ok)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT,
+                pre + array + " must be non-decreasing from 0 to at most " + rows_name);
+  return 0;
+}
+
+int pnec_hip_tracks_retain(int64_t n_images, const int64_t *offsets, int64_t n_rows, const int64_t *id,
+                           const int32_t *tmpl_image, const double *tmpl_pts, const int32_t *age, const double *pts,
+                           const double *cov, const double *trk_pts, const double *trk_angle, const double *trk_cov,
+                           const int32_t *trk_status, int32_t max_age, int64_t *out_offsets, int64_t *out_id,
+                           int32_t *out_tmpl_image, double *out_tmpl_pts, int32_t *out_age, double *out_pts,
+                           double *out_angle, double *out_cov, double *out_prev_pts, double *out_prev_cov,
+                           int64_t *out_src, int space, int device, void *stream_) {
+  const std::string pre = "tracks_retain: ";
+  if (n_images < 1 || n_rows < 0) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "n_images must be >= 1, n_rows >= 0");
+  if (!offsets || !out_offsets) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "offsets or out_offsets is NULL");
+  if (n_rows > 0 && (!id || !tmpl_image || !tmpl_pts || !age || !pts || !trk_pts || !trk_angle || !trk_status))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT,
+                pre + "id, tmpl_image, tmpl_pts, age, pts, trk_pts, trk_angle or trk_status is NULL");
+  if (n_rows > 0 && (!out_id || !out_tmpl_image || !out_tmpl_pts || !out_age || !out_pts || !out_angle))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT,
+                pre + "out_id, out_tmpl_image, out_tmpl_pts, out_age, out_pts or out_angle is NULL");
+  const int n_cov = (cov ? 1 : 0) + (trk_cov ? 1 : 0) + (out_cov ? 1 : 0) + (out_prev_cov ? 1 : 0);
+  if (n_cov != 0 && n_cov != 4)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "cov, trk_cov, out_cov and out_prev_cov are given or NULL together");
+  if (max_age < 0) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "max_age must be >= 0");
+  if (n_images > 0x7fffffffLL || n_rows > (int64_t)1 << 40)
+    return fail(PNEC_HIP_ERR_UNSUPPORTED, pre + "too many images or rows");
+  const void *ins[] = {offsets, id, tmpl_image, tmpl_pts, age, pts, cov, trk_pts, trk_angle, trk_cov, trk_status};
+  void *outs[] = {out_offsets, out_id, out_tmpl_image, out_tmpl_pts, out_age, out_pts, out_angle, out_cov,
+                  out_prev_pts, out_prev_cov, out_src};
+  for (void *o : outs)
+    for (const void *i : ins)
+      if (o && o == i) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "an output is an input (the outputs are fresh arrays)");
+  if (int rc = check_space(pre, space)) return rc;
+  if (space == PNEC_HIP_MEM_HOST)
+    if (int rc = check_set_offsets(pre, "offsets", offsets, n_images, n_rows, "n_rows")) return rc;
+  hipStream_t stream = (hipStream_t)stream_;
+  CallArrays io(device, space, stream);
+  TracksRetainArgs a{};
+  a.n_images = n_images;
+  a.in.n_rows = n_rows;
+  a.max_age = max_age;
+  const int64_t N = n_rows;
+  io.in(a.in.offsets, offsets, n_images + 1);
+  io.in(a.in.id, id, N);
+  io.in(a.in.tmpl_image, tmpl_image, N);
+  io.in(a.in.tmpl_pts, tmpl_pts, 2 * N);
+  io.in(a.in.age, age, N);
+  io.in(a.in.pts, pts, 2 * N);
+  io.in(a.in.cov, cov, 3 * N);
+  io.in(a.trk_pts, trk_pts, 2 * N);
+  io.in(a.trk_angle, trk_angle, N);
+  io.in(a.trk_cov, trk_cov, 3 * N);
+  io.in(a.trk_status, trk_status, N);
+  io.out(a.out.offsets, out_offsets, n_images + 1);
+  io.out(a.out.id, out_id, N);
+  io.out(a.out.tmpl_image, out_tmpl_image, N);
+  io.out(a.out.tmpl_pts, out_tmpl_pts, 2 * N);
+  io.out(a.out.age, out_age, N);
+  io.out(a.out.pts, out_pts, 2 * N);
+  io.out(a.out.angle, out_angle, N);
+  io.out(a.out.cov, out_cov, 3 * N);
+  io.out(a.out_prev_pts, out_prev_pts, 2 * N);
+  io.out(a.out_prev_cov, out_prev_cov, 3 * N);
+  io.out(a.out_src, out_src, N);
+  if (int rc = io.commit()) return rc;
+  PNEC_HIP_TRY(launch_tracks_retain(a, stream));
+  return io.finish();
+}
+
+int pnec_hip_tracks_append(int64_t n_images, const int64_t *offsets, int64_t n_rows, const int64_t *id,
+                           const int32_t *tmpl_image, const double *tmpl_pts, const int32_t *age, const double *pts,
+                           const double *angle, const double *cov, const int64_t *det_offsets, int64_t n_det,
+                           const double *det_pts, const double *det_cov, int32_t tmpl_image_base,
+                           int64_t per_image_capacity, int64_t *next_id, int64_t n_out, int64_t *out_offsets,
+                           int64_t *out_id, int32_t *out_tmpl_image, double *out_tmpl_pts, int32_t *out_age,
+                           double *out_pts, double *out_angle, double *out_cov, int64_t *out_dropped, int space,
+                           int device, void *stream_) {
+  const std::string pre = "tracks_append: ";
+  if (n_images < 1 || n_rows < 0 || n_det < 0 || n_out < 0)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "n_images must be >= 1, n_rows, n_det and n_out >= 0");
+  const bool no_set = !offsets;
+  if (no_set && (n_rows != 0 || id || tmpl_image || tmpl_pts || age || pts || angle || cov))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "without offsets (no set) every set pointer is NULL and n_rows is 0");
+  if (!no_set && n_rows > 0 && (!id || !tmpl_image || !tmpl_pts || !age || !pts || !angle))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "id, tmpl_image, tmpl_pts, age, pts or angle is NULL");
+  if (!det_offsets || (!det_pts && n_det > 0))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "det_offsets or det_pts is NULL");
+  if (!next_id || !out_offsets) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "next_id or out_offsets is NULL");
+  if (n_out > 0 && (!out_id || !out_tmpl_image || !out_tmpl_pts || !out_age || !out_pts || !out_angle))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT,
+                pre + "out_id, out_tmpl_image, out_tmpl_pts, out_age, out_pts or out_angle is NULL");
+  if (per_image_capacity < 1) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "per_image_capacity must be >= 1");
+  if (n_images > 0x7fffffffLL || n_rows > (int64_t)1 << 40 || n_det > (int64_t)1 << 40 || n_out > (int64_t)1 << 40)
+    return fail(PNEC_HIP_ERR_UNSUPPORTED, pre + "too many images or rows");
+  if (tmpl_image_base < 0 || (int64_t)tmpl_image_base + n_images - 1 > 0x7fffffffLL)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "tmpl_image_base must be >= 0 and tmpl_image_base + n_images - 1 fit int32");
+  // (an image takes at most every row there is: with the capacity cut there, n_images * capacity stays below 2^73)
+  const int64_t total_in = n_rows + n_det;
+  const __int128 all_full = (__int128)n_images * std::min(per_image_capacity, total_in);
+  if ((__int128)n_out < std::min(all_full, (__int128)total_in))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "n_out is below min(n_images * per_image_capacity, n_rows + n_det)");
+  const void *ins[] = {offsets, id, tmpl_image, tmpl_pts, age, pts, angle, cov, det_offsets, det_pts, det_cov};
+  void *outs[] = {out_offsets, out_id, out_tmpl_image, out_tmpl_pts, out_age, out_pts, out_angle, out_cov, out_dropped,
+                  next_id};
+  for (void *o : outs)
+    for (const void *i : ins)
+      if (o && o == i) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "an output is an input (the outputs are fresh arrays)");
+  if (int rc = check_space(pre, space)) return rc;
+  if (space == PNEC_HIP_MEM_HOST) {
+    if (!no_set)
+      if (int rc = check_set_offsets(pre, "offsets", offsets, n_images, n_rows, "n_rows")) return rc;
+    if (int rc = check_set_offsets(pre, "det_offsets", det_offsets, n_images, n_det, "n_det")) return rc;
+    int64_t total = 0;
+    for (int64_t f = 0; f < n_images; ++f) {
+      int64_t take_a, take_d;
+      tracks_take(no_set ? 0 : offsets[f + 1] - offsets[f], det_offsets[f + 1] - det_offsets[f], per_image_capacity,
+                  take_a, take_d);
+      total += take_a + take_d;
+    }
+    if (n_out < total) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "n_out is below the rows the call produces");
+  }
+  hipStream_t stream = (hipStream_t)stream_;
+  CallArrays io(device, space, stream);
+  TracksAppendArgs a{};
+  a.n_images = n_images;
+  a.in.n_rows = n_rows;
+  a.n_det = n_det;
+  a.tmpl_image_base = tmpl_image_base;
+  a.capacity = per_image_capacity;
+  a.n_out = n_out;
+  const int64_t N = n_rows, D = n_det, O = n_out;
+  io.in(a.in.offsets, offsets, n_images + 1);
+  io.in(a.in.id, id, N);
+  io.in(a.in.tmpl_image, tmpl_image, N);
+  io.in(a.in.tmpl_pts, tmpl_pts, 2 * N);
+  io.in(a.in.age, age, N);
+  io.in(a.in.pts, pts, 2 * N);
+  io.in(a.in.angle, angle, N);
+  io.in(a.in.cov, cov, 3 * N);
+  io.in(a.det_offsets, det_offsets, n_images + 1);
+  io.in(a.det_pts, det_pts, 2 * D);
+  io.in(a.det_cov, det_cov, 3 * D);
+  io.out(a.next_id, next_id, n_images, kPreload);
+  io.out(a.out.offsets, out_offsets, n_images + 1);
+  io.out(a.out.id, out_id, O);
+  io.out(a.out.tmpl_image, out_tmpl_image, O);
+  io.out(a.out.tmpl_pts, out_tmpl_pts, 2 * O);
+  io.out(a.out.age, out_age, O);
+  io.out(a.out.pts, out_pts, 2 * O);
+  io.out(a.out.angle, out_angle, O);
+  io.out(a.out.cov, out_cov, 3 * O);
+  io.out(a.out_dropped, out_dropped, n_images);
+  if (int rc = io.commit()) return rc;
+  PNEC_HIP_TRY(launch_tracks_append(a, stream));
   return io.finish();
 }
 

@@ -203,6 +203,9 @@ struct PatchTrackArgs {
 hipError_t launch_image_pyramid_level(int pixel_type, const PyramidLevelArgs &a, hipStream_t stream);
 // 16 keypoints per block of 256 threads
 hipError_t launch_patch_track(int pixel_type, const PatchTrackArgs &a, hipStream_t stream);
+// the same with a.tmpl a stack of n_tmpl_images images per level and keypoint k's templates built in image tmpl_image[k]
+hipError_t launch_patch_track_indexed(int pixel_type, const PatchTrackArgs &a, const int32_t *tmpl_image,
+                                      int64_t n_tmpl_images, hipStream_t stream);
 #endif
 
 }  // namespace pnec_hip

@@ -8,7 +8,8 @@ claimed.
 
 Patch tracking: ``image_pyramid`` (``pnec_hip_image_pyramid_level``) and ``patch_track`` (``pnec_hip_patch_track``), the
 pyramidal SE(2) KLT iteration with its forward-backward check (klt_patch_optical_flow.h:195-342) -- the producer of the
-positions and of ``angle`` above.  Keypoint ids and the view graph are not here.
+positions and of ``angle`` above.  Keypoint ids and the bookkeeping of tracks across frames are tracker.py's; the view
+graph is not here.
 
 Keypoint detection: ``detect_keypoints`` (``pnec_hip_detect_keypoints``), grid FAST-9 corners as
 KLTPatchOpticalFlow::addPoints gets them (klt_patch_optical_flow.h:344-385) -- the producer of ``tmpl_pts``.
@@ -236,13 +237,20 @@ def image_pyramid(images, levels: int) -> list:
 
 def patch_track(tmpl, next, tmpl_pts, offsets=None, prev=None, init_pts=None, init_angle=None, shift=(0.0, 0.0),
                 pattern=PATTERN52, max_iterations: int = 40, max_recovered_dist2: float = 0.04, backward: bool = True,
-                scaling: float = 10.0, outputs=("pts", "angle", "cov", "dist2", "status", "lost_level")) -> PatchTrack:
+                scaling: float = 10.0, outputs=("pts", "angle", "cov", "dist2", "status", "lost_level"),
+                tmpl_image=None) -> PatchTrack:
     """Tracks the patches built at `tmpl_pts` [M,2] (level-0 pixels, x = column, y = row) in the pyramid `tmpl` into the
     pyramid `next`, and back into `prev` (None: `tmpl`) for the forward-backward check.  A pyramid is a list of [F,h_l,w_l]
     batches as image_pyramid returns it; keypoints [offsets[f], offsets[f+1]) lie in image f.  `init_pts` / `init_angle`
     are the transform in `prev` (None: tmpl_pts / 0), `shift` is added to the forward start.  All pyramids in torch.cuda
     tensors -> everything stays on the device, asynchronous on torch's current stream, torch.cuda tensors out; numpy in
-    -> staged, numpy out."""
+    -> staged, numpy out.
+
+    `tmpl_image` int32 [M] (``pnec_hip_patch_track_indexed``): `tmpl` is then a stack of any number of images per level
+    and keypoint k builds its templates, and its `cov`, in image tmpl_image[k] of it; `prev` must be given, and `prev` /
+    `next` stay indexed by the keypoint's own image.  None: the keypoint's own image, `pnec_hip_patch_track` as before."""
+    if tmpl_image is not None and prev is None:
+        raise ValueError("with tmpl_image, prev must be given: tmpl is a stack of other images")
     pyrs = {"tmpl": tmpl, "next": next, "prev": prev}
     levels = len(tmpl)
     norm, on = {}, None
@@ -259,12 +267,14 @@ def patch_track(tmpl, next, tmpl_pts, offsets=None, prev=None, init_pts=None, in
     if not 1 <= levels <= TRACK_MAX_LEVELS:
         raise ValueError(f"a pyramid must have 1 .. {TRACK_MAX_LEVELS} levels")
     base = norm["tmpl"][0]
-    F, h, w = (int(x) for x in base.shape)
+    Ft, h, w = (int(x) for x in base.shape)
+    F = Ft if tmpl_image is None else int(norm["next"][0].shape[0])
     ptype = _ptype(base, on)
-    for pyr in norm.values():
+    for name, pyr in norm.items():
+        n = Ft if name == "tmpl" else F
         for l, lv in enumerate(pyr):
-            if tuple(int(x) for x in lv.shape) != (F, h >> l, w >> l) or _ptype(lv, on) != ptype:
-                raise ValueError(f"level {l} must be [{F},{h >> l},{w >> l}] of the pyramid's pixel type")
+            if tuple(int(x) for x in lv.shape) != (n, h >> l, w >> l) or _ptype(lv, on) != ptype:
+                raise ValueError(f"level {l} of {name} must be [{n},{h >> l},{w >> l}] of the pyramid's pixel type")
     space, device, stream = _where(base, on)
     if on:
         import torch
@@ -292,6 +302,10 @@ def patch_track(tmpl, next, tmpl_pts, offsets=None, prev=None, init_pts=None, in
     init_pts = None if init_pts is None else as_in(init_pts, F64)
     init_angle = None if init_angle is None else as_in(init_angle, F64)
     pattern_d = as_in(pattern, F64)
+    if tmpl_image is not None:
+        tmpl_image = as_in(tmpl_image, torch.int32 if on else np.int32)
+        if tuple(tmpl_image.shape) != (M,):
+            raise ValueError("tmpl_image must be [M]")
     if tuple(tmpl_pts.shape) != (M, 2) or (init_pts is not None and tuple(init_pts.shape) != (M, 2)):
         raise ValueError("tmpl_pts and init_pts must be [M,2] (x = column, y = row)")
     if init_angle is not None and tuple(init_angle.shape) != (M,):
@@ -316,6 +330,13 @@ def patch_track(tmpl, next, tmpl_pts, offsets=None, prev=None, init_pts=None, in
     tp, tq = table(norm["tmpl"])
     pp, pq = table(norm.get("prev"))
     np_, nq = table(norm["next"])
+    if tmpl_image is not None:
+        capi.check(capi.lib().pnec_hip_patch_track_indexed(
+            tp, tq, Ft, pp, pq, np_, nq, levels, ptype, F, h, w, p(offsets_d), M, p(tmpl_pts), p(tmpl_image), p(init_pts),
+            p(init_angle), float(shift[0]), float(shift[1]), p(pattern_d), int(pattern_d.shape[0]), int(max_iterations),
+            float(max_recovered_dist2), 0 if backward else TRACK_NO_BACKWARD, float(scaling), p(out["pts"]),
+            p(out["angle"]), p(out["cov"]), p(out["dist2"]), p(out["status"]), p(out["lost_level"]), space, device, stream))
+        return PatchTrack(out["pts"], out["angle"], out["cov"], out["dist2"], out["status"], out["lost_level"], offsets_d)
     capi.check(capi.lib().pnec_hip_patch_track(
         tp, tq, pp, pq, np_, nq, levels, ptype, F, h, w, p(offsets_d), M, p(tmpl_pts), p(init_pts), p(init_angle),
         float(shift[0]), float(shift[1]), p(pattern_d), int(pattern_d.shape[0]), int(max_iterations),

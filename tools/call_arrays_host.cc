@@ -294,6 +294,92 @@ void image_lists(int64_t F, int64_t elem, int64_t n_points) {
       }, (image_bytes + 7) / 8 + (have_cur ? F + 1 + 2 * Cn : 0) + (F + 1) + 2 * cap, F * n_cells + 2 * cap);
     }
   }
+
+  // the indexed tracker: pnec_hip_patch_track's list with a template stack of Ft images per level, never shared with
+  // prev, and the index array
+  for (int n_levels : {1, 3}) {
+    const int64_t Ft = 2 * F + 1;
+    auto level_bytes = [&](int lv, int64_t p, int64_t n) { return image_block_bytes(elem, n, h >> lv, p, w >> lv); };
+    int64_t pitches[3] = {pitch, 21, 11};
+    int64_t pixels8 = 0;
+    for (int lv = 0; lv < n_levels; ++lv)
+      pixels8 += (level_bytes(lv, pitches[lv], Ft) + 7) / 8 + (level_bytes(lv, pitches[lv] + 1, F) + 7) / 8 +
+                 (level_bytes(lv, pitches[lv] + 2, F) + 7) / 8;
+    run(tag("patch_track_indexed", {F, elem, M, n_levels}), [&](List &l) {
+      for (int lv = 0; lv < n_levels; ++lv) {
+        l.in(true, level_bytes(lv, pitches[lv], Ft), 1);      // tmpl: the stack
+        l.in(true, level_bytes(lv, pitches[lv] + 1, F), 1);   // next
+        l.in(true, level_bytes(lv, pitches[lv] + 2, F), 1);   // prev
+      }
+      l.in(true, F + 1, 8);
+      l.in(true, 2 * M, 8);
+      l.in(l.opt(), 2 * M, 8);   // init_pts
+      l.in(l.opt(), M, 8);       // init_angle
+      l.in(true, M, 4);          // tmpl_image
+      l.in(true, 2 * n_pattern, 8);
+      l.out(l.opt(), 2 * M, 8);
+      l.out(l.opt(), M, 8);
+      l.out(l.opt(), 3 * M, 8);
+      l.out(l.opt(), M, 8);
+      l.out(l.opt(), M, 4);
+      l.out(l.opt(), M, 4);
+    }, pixels8 + (F + 1) + 12 * M + 2 * n_pattern, 3 * M);
+  }
+
+  // the bookkeeping of tracks (no images): a set of N rows, D detections, O output rows
+  if (elem == 1) {
+    const int64_t N = M, D = M + 2, O = M + 5;
+    run(tag("tracks_retain", {F, N}), [&](List &l) {
+      l.in(true, F + 1, 8);      // offsets
+      l.in(true, N, 8);          // id
+      l.in(true, N, 4);          // tmpl_image
+      l.in(true, 2 * N, 8);      // tmpl_pts
+      l.in(true, N, 4);          // age
+      l.in(true, 2 * N, 8);      // pts
+      l.in(l.opt(), 3 * N, 8);   // cov
+      l.in(true, 2 * N, 8);      // trk_pts
+      l.in(true, N, 8);          // trk_angle
+      l.in(l.opt(), 3 * N, 8);   // trk_cov
+      l.in(true, N, 4);          // trk_status
+      l.out(true, F + 1, 8);
+      l.out(true, N, 8);
+      l.out(true, N, 4);
+      l.out(true, 2 * N, 8);
+      l.out(true, N, 4);
+      l.out(true, 2 * N, 8);
+      l.out(true, N, 8);
+      l.out(l.opt(), 3 * N, 8);  // out_cov
+      l.out(l.opt(), 2 * N, 8);  // out_prev_pts
+      l.out(l.opt(), 3 * N, 8);  // out_prev_cov
+      l.out(l.opt(), N, 8);      // out_src
+    }, 2 * (F + 1) + 29 * N, 5 * N);
+    for (bool have_set : {false, true}) {
+      const int64_t Ns = have_set ? N : 0;
+      run(tag("tracks_append", {F, Ns, D, O}), [&](List &l) {
+        l.in(have_set, F + 1, 8);
+        l.in(have_set, Ns, 8);
+        l.in(have_set, Ns, 4);
+        l.in(have_set, 2 * Ns, 8);
+        l.in(have_set, Ns, 4);
+        l.in(have_set, 2 * Ns, 8);
+        l.in(have_set, Ns, 8);
+        l.in(have_set && l.opt(), 3 * Ns, 8);   // cov
+        l.in(true, F + 1, 8);      // det_offsets
+        l.in(true, 2 * D, 8);
+        l.in(l.opt(), 3 * D, 8);   // det_cov
+        l.out(true, F, 8, kPreload);   // next_id
+        l.out(true, F + 1, 8);
+        l.out(true, O, 8);
+        l.out(true, O, 4);
+        l.out(true, 2 * O, 8);
+        l.out(true, O, 4);
+        l.out(true, 2 * O, 8);
+        l.out(true, O, 8);
+        l.out(l.opt(), 3 * O, 8);  // out_cov
+        l.out(l.opt(), F, 8);      // out_dropped
+      }, (have_set ? F + 1 + 9 * Ns : 0) + (F + 1) + 5 * D + F + (F + 1) + 9 * O + F, 2 * Ns + 2 * O);
+    }
+  }
 }
 
 }  // namespace
