@@ -205,6 +205,36 @@ int pnec_hip_problem_fill_keypoints(pnec_hip_problem *p, int64_t first_pair, int
                                     const double *pts2, const double *cov2, const double *cov1, const double *K_inv,
                                     double kappa, int camera_model, int space, void *stream);
 
+/* The same ingest, shaped by offsets that may live on the device (added within ABI 8: a pure addition,
+ * PNEC_HIP_ABI_VERSION is unchanged): what a tracker that reads nothing back hands over -- rows of keypoints, ragged by
+ * an offsets array only the device knows -- becomes a batch without the host ever learning the pair sizes.
+ *   p        a capacity batch (pnec_hip_problem_create_capacity).  Its current shape -- the last
+ *            pnec_hip_problem_reshape -- is read as BOUNDS: pair k may hold up to bound_k = (that shape's) offsets[k+1] -
+ *            offsets[k] correspondences, and its block keeps that room.  The bounds stay until the next reshape.
+ *   offsets  int64 [n_pairs + 1], in `space` like the other arrays: rows [offsets[k], offsets[k+1]) of pts1 / pts2 /
+ *            cov2 / cov1 are pair k's correspondences.  The range is cut to [0, n_rows] first (lo = clamp(offsets[k], 0,
+ *            n_rows), hi = clamp(offsets[k+1], lo, n_rows)); the pair takes its first cnt_k = min(hi - lo, bound_k) rows.
+ *            It must not be the batch's own offsets array.
+ *   n_rows   the rows of pts1, pts2 [n_rows,2], cov2, cov1 [n_rows,3]; at most 2^31-1
+ *   cov2 / cov1, K_inv, kappa, camera_model   as for pnec_hip_problem_fill_keypoints; cov2 must be NULL for a NEC batch
+ *            and given otherwise, cov1 given for a SYM batch and NULL otherwise, whatever the sizes turn out to be
+ *   out_dropped  int32 [n_pairs] or NULL: (hi - lo) - cnt_k, the rows the bound turned away
+ * It writes, per pair, the count cnt_k, the batch's own offsets (the exclusive scan of the counts: the positions the
+ * per-correspondence outputs of the other calls use) and the SoA planes with stride round_up(cnt_k, 64) at the start of
+ * the pair's bound-sized block, padding lanes zero: what pnec_hip_problem_fill_keypoints writes for the same rows, bit
+ * for bit.  The batch is then in the state pnec_hip_problem_select leaves its result in: launch geometries follow the
+ * bounds, the real sizes exist on the device only, and every DEVICE-space stage takes it as it is; the first call that
+ * needs host-side sizes (pnec_hip_problem_offsets, _num_correspondences, a HOST-space mask, ...) waits for `stream` and
+ * fetches them.  pnec_hip_problem_reshape makes it an exact batch again.
+ * DEVICE space: asynchronous on `stream`, no host synchronisation, and nothing is allocated after the first call (the
+ * first call after a reshape uploads the bounds and waits for the previous such upload, as reshape itself does); nothing
+ * but the cut above is validated.  HOST space: staged like the other calls, waits for the stream; offsets that decrease,
+ * start below 0 or end beyond n_rows are refused.  Refusals are PNEC_HIP_ERR_INVALID_ARGUMENT: a batch without capacity,
+ * NULL offsets or K_inv, a covariance array missing or present against the mode, a bad space, camera_model != 1. */
+int pnec_hip_problem_fill_keypoints_ragged(pnec_hip_problem *p, const int64_t *offsets, int64_t n_rows, const double *pts1,
+                                           const double *pts2, const double *cov2, const double *cov1, const double *K_inv,
+                                           double kappa, int camera_model, int32_t *out_dropped, int space, void *stream);
+
 /* The batch's SoA planes as stored in HBM (pair blocks of round_up(N_p, 64)-double planes; the layout in
  * pnec_internal.hpp / DESIGN.md): size in doubles, and a copy out (tests, debugging). */
 int64_t pnec_hip_problem_payload_doubles(const pnec_hip_problem *p);

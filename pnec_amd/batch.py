@@ -428,6 +428,15 @@ class Batch:
             if int(np.prod(a.shape)) != m * width:
                 raise ValueError(f"expected {m}x{width} values, got {tuple(a.shape)}")
             keep.append(a)
+        Kd, kp, space, stream = self._kinv_arg(K, on_device)
+        capi.check(self._lib.pnec_hip_problem_fill_keypoints(self._h, first_pair, n_pairs, ptrs[0], ptrs[1], ptrs[2],
+                                                             ptrs[3], kp, float(kappa), 1, space, stream))
+        return self
+
+    def _kinv_arg(self, K, on_device):
+        """K_inv [3,3] (None: the identity) as the keypoint ingests take it -> (the column-major array, kept alive by the
+        caller; its pointer; the memory space; the stream)."""
+        K = np.eye(3) if K is None else K
         if on_device:
             import torch
             # no host round trip per call (an upload from pageable memory waits for the stream): a CUDA K_inv is
@@ -442,12 +451,64 @@ class Batch:
                     if len(_kinv_on) >= 64:
                         _kinv_on.clear()
                     Kd = _kinv_on[key] = torch.as_tensor(K9, device=f"cuda:{self.device}")
-            kp, stream, space = Kd.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream, capi.MEM_DEVICE
+            return Kd, Kd.data_ptr(), capi.MEM_DEVICE, torch.cuda.current_stream(self.device).cuda_stream
+        Kd = np.ascontiguousarray(np.asarray(K, dtype=np.float64).T.reshape(9))
+        return Kd, Kd.ctypes.data, capi.MEM_HOST, None
+
+    def fill_keypoints_ragged(self, offsets, pts1, pts2, cov2=None, cov1=None, K_inv=None, kappa: float = 1.0,
+                              dropped=None) -> "Batch":
+        """fill_keypoints shaped by offsets that may live on the device (pnec_hip_problem_fill_keypoints_ragged): this
+        capacity batch's current shape -- its last reshape() -- gives the BOUNDS, pair k takes the first
+        min(offsets[k+1] - offsets[k], bound_k) of the rows [offsets[k], offsets[k+1]) of pts1 / pts2 [R,2], cov2 / cov1
+        [R,3] (or [R,2,2]), and the batch's own offsets become the scan of those counts.  What a Tracker hands over goes
+        in as it is: fill_keypoints_ragged(pairs.offsets, pairs.prev_pts, pairs.pts, pairs.cov).
+
+        torch.cuda tensors -> DEVICE space, asynchronous on torch's current stream, nothing read back (K_inv as for
+        fill_keypoints); numpy arrays -> HOST space, staged, the call waits.  `dropped`: an int32 [n_pairs] array of
+        the same kind that receives the rows each bound turned away.  Afterwards the batch is what select() returns:
+        solve, solve_pipeline (without want_inliers), cost_function and pose_covariance take it without a wait; `offsets`,
+        num_correspondences and the calls that size per-correspondence outputs (residuals, triangulate, relative_scale,
+        want_inliers) wait once for the stream and fetch the sizes.  reshape() makes it an exact batch again."""
+        on_device = _is_torch(pts1)
+        xp = __import__("torch") if on_device else np
+
+        def c3(a):
+            if a is not None and a.ndim == 3:  # [R,2,2] -> (xx, xy, yy)
+                a = xp.stack([a[:, 0, 0], a[:, 1, 0], a[:, 1, 1]], -1)
+            return a
+        P, R = self.n_pairs, int(pts1.shape[0])
+        ptrs, keep = [], []
+        for a, width in ((pts1, 2), (pts2, 2), (c3(cov2), 3), (c3(cov1), 3)):
+            if a is None:
+                ptrs.append(None)
+                continue
+            if on_device:
+                a = self._dev_tensor(a, "keypoint array")
+                ptrs.append(a.data_ptr())
+            else:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                ptrs.append(a.ctypes.data)
+            if int(np.prod(a.shape)) != R * width:
+                raise ValueError(f"expected {R}x{width} values, got {tuple(a.shape)}")
+            keep.append(a)
+        if on_device:
+            import torch
+            off = self._dev_tensor(offsets, "offsets", (P + 1,), dtype=torch.int64)
+            if dropped is not None:
+                self._dev_out(dropped, "dropped", (P,), torch.int32)
+            po, pd = off.data_ptr(), None if dropped is None else dropped.data_ptr()
         else:
-            Kd = np.ascontiguousarray(np.asarray(K, dtype=np.float64).T.reshape(9))
-            kp, stream, space = Kd.ctypes.data, None, capi.MEM_HOST
-        capi.check(self._lib.pnec_hip_problem_fill_keypoints(self._h, first_pair, n_pairs, ptrs[0], ptrs[1], ptrs[2],
-                                                             ptrs[3], kp, float(kappa), 1, space, stream))
+            off = np.ascontiguousarray(offsets, dtype=np.int64)
+            if off.shape != (P + 1,):
+                raise ValueError(f"offsets: expected shape ({P + 1},), got {off.shape}")
+            if dropped is not None and not (isinstance(dropped, np.ndarray) and dropped.dtype == np.int32
+                                            and dropped.shape == (P,) and dropped.flags.c_contiguous):
+                raise ValueError(f"dropped: need a C-contiguous int32 array of shape ({P},)")
+            po, pd = off.ctypes.data, None if dropped is None else dropped.ctypes.data
+        Kd, kp, space, stream = self._kinv_arg(K_inv, on_device)
+        capi.check(self._lib.pnec_hip_problem_fill_keypoints_ragged(self._h, po, R, ptrs[0], ptrs[1], ptrs[2], ptrs[3], kp,
+                                                                    float(kappa), 1, pd, space, stream))
+        self._offsets = None   # (the sizes are the device's: fetched from the library on first use, which waits)
         return self
 
     def export_payload(self) -> np.ndarray:

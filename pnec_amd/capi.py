@@ -47,6 +47,7 @@ SYMBOLS = [
     "pnec_hip_problem_destroy",
     "pnec_hip_problem_fill",
     "pnec_hip_problem_fill_keypoints",
+    "pnec_hip_problem_fill_keypoints_ragged",
     "pnec_hip_problem_payload_doubles",
     "pnec_hip_problem_export_payload",
     "pnec_hip_problem_num_pairs",
@@ -203,6 +204,8 @@ def lib() -> C.CDLL:
     L.pnec_hip_problem_fill.argtypes = [_vp, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, C.c_int, _vp]
     L.pnec_hip_problem_fill_keypoints.argtypes = [_vp, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_double,
                                                   C.c_int, C.c_int, _vp]
+    L.pnec_hip_problem_fill_keypoints_ragged.argtypes = [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_int,
+                                                         _vp, C.c_int, _vp]
     L.pnec_hip_problem_export_payload.argtypes = [_vp, _vp, C.c_int, _vp]
     for name in ("num_pairs", "num_correspondences", "max_correspondences", "payload_bytes", "payload_doubles"):
         f = getattr(L, "pnec_hip_problem_" + name)

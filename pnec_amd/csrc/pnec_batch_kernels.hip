@@ -298,6 +298,87 @@ __global__ __launch_bounds__(256) void ingest_keypoints_kernel(double *__restric
   }
 }
 
+// ---- the same ingest shaped on the device: pair p's rows are [src_offsets[p], src_offsets[p + 1]) of the caller's
+// arrays, cut to [0, n_rows] (as pnec_tracks.hpp's tracks_range cuts a set's), and the pair keeps the first
+// min(rows, bound[p]) of them inside the block its bound reserved.  It differs from ingest_keypoints_kernel in three
+// things: the source offsets are the caller's (the batch's own compact offsets come from the scan that follows), the
+// count is computed here, and one lane per pair stores it and what the bound turned away.  Every block derives the count
+// from src_offsets and bound: `count` and `out_dropped` are written and never read, so no lane reads a word that a lane
+// of this launch writes.  No wavefront-wide operation: lanes diverge freely.
+template <int NC>
+__global__ __launch_bounds__(256) void ingest_keypoints_ragged_kernel(double *__restrict__ data,
+                                                                      const int64_t *__restrict__ block_offset,
+                                                                      const int64_t *__restrict__ src_offsets,
+                                                                      const int32_t *__restrict__ bound,
+                                                                      int32_t *__restrict__ count,
+                                                                      int32_t *__restrict__ out_dropped, int64_t n_pairs,
+                                                                      int64_t n_rows, const double *__restrict__ pts1,
+                                                                      const double *__restrict__ pts2,
+                                                                      const double *__restrict__ cov2,
+                                                                      const double *__restrict__ cov1,
+                                                                      const double *__restrict__ K_inv_, double kappa) {
+  double K[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) K[k] = K_inv_[k];
+  const double zero3[3] = {0.0, 0.0, 0.0};
+  for (int64_t p = blockIdx.y; p < n_pairs; p += gridDim.y) {
+    int64_t lo = src_offsets[p], hi = src_offsets[p + 1];
+    lo = lo < 0 ? 0 : (lo > n_rows ? n_rows : lo);
+    hi = hi < lo ? lo : (hi > n_rows ? n_rows : hi);
+    const int64_t room = bound[p] > 0 ? bound[p] : 0;
+    const int n = (int)(hi - lo < room ? hi - lo : room);
+    const int stride = (n + kWave - 1) & ~(kWave - 1);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      count[p] = n;
+      if (out_dropped) out_dropped[p] = (int32_t)(hi - lo - n);
+    }
+    double *blk = data + block_offset[p];
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < stride; i += gridDim.x * blockDim.x) {
+      const bool in = i < n;
+      const int64_t j = in ? lo + i : lo;  // a valid address for the padding lanes (n > 0 here, so lo < n_rows)
+      double b1[3], b2[3], S2[9], S1[9];
+      {
+        const double m[3] = {pts2[2 * j], pts2[2 * j + 1], 1.0};
+        double c0[3], c1[3];
+        if constexpr (NC >= 12) pinhole_columns(cov2[3 * j], cov2[3 * j + 1], cov2[3 * j + 2], c0, c1);
+        else { c0[0] = c0[1] = c0[2] = c1[0] = c1[1] = c1[2] = 0.0; }
+        unscented_core(m, c0, c1, K, kappa, 1, b2, S2);
+      }
+      {
+        const double m[3] = {pts1[2 * j], pts1[2 * j + 1], 1.0};
+        if constexpr (NC >= 18) {
+          double c0[3], c1[3];
+          pinhole_columns(cov1[3 * j], cov1[3 * j + 1], cov1[3 * j + 2], c0, c1);
+          unscented_core(m, c0, c1, K, kappa, 1, b1, S1);
+        } else {
+          unscented_core(m, zero3, zero3, K, kappa, 1, b1, S1);  // only the bearing is kept
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        blk[(int64_t)c * stride + i] = in ? b1[c] : 0.0;
+        blk[(int64_t)(3 + c) * stride + i] = in ? b2[c] : 0.0;
+      }
+      if constexpr (NC >= 12) {
+        blk[(int64_t)6 * stride + i] = in ? S2[0] : 0.0;
+        blk[(int64_t)7 * stride + i] = in ? 0.5 * (S2[1] + S2[3]) : 0.0;
+        blk[(int64_t)8 * stride + i] = in ? 0.5 * (S2[2] + S2[6]) : 0.0;
+        blk[(int64_t)9 * stride + i] = in ? S2[4] : 0.0;
+        blk[(int64_t)10 * stride + i] = in ? 0.5 * (S2[5] + S2[7]) : 0.0;
+        blk[(int64_t)11 * stride + i] = in ? S2[8] : 0.0;
+      }
+      if constexpr (NC >= 18) {
+        blk[(int64_t)12 * stride + i] = in ? S1[0] : 0.0;
+        blk[(int64_t)13 * stride + i] = in ? 0.5 * (S1[1] + S1[3]) : 0.0;
+        blk[(int64_t)14 * stride + i] = in ? 0.5 * (S1[2] + S1[6]) : 0.0;
+        blk[(int64_t)15 * stride + i] = in ? S1[4] : 0.0;
+        blk[(int64_t)16 * stride + i] = in ? 0.5 * (S1[5] + S1[7]) : 0.0;
+        blk[(int64_t)17 * stride + i] = in ? S1[8] : 0.0;
+      }
+    }
+  }
+}
+
 // ---- inliers per pair from a correspondence mask ----------------------------------------------
 __global__ __launch_bounds__(kWave) void mask_count_kernel(const uint8_t *__restrict__ mask,
                                                            const int64_t *__restrict__ offsets,
@@ -519,6 +600,29 @@ hipError_t launch_ingest_keypoints(int nc, int32_t n_max, double *data, const in
     default:
       hipLaunchKernelGGL(ingest_keypoints_kernel<18>, grid, block, 0, stream, data, block_offset, offsets, count, first_pair,
                          n_pairs, pts1, pts2, cov2, cov1, K_inv, kappa);
+      break;
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_ingest_keypoints_ragged(int nc, int32_t n_max, double *data, const int64_t *block_offset,
+                                          const int64_t *src_offsets, const int32_t *bound, int32_t *count,
+                                          int32_t *out_dropped, int64_t n_pairs, int64_t n_rows, const double *pts1,
+                                          const double *pts2, const double *cov2, const double *cov1, const double *K_inv,
+                                          double kappa, hipStream_t stream) {
+  const dim3 block(256), grid = ingest_grid(n_max, n_pairs);
+  switch (nc) {
+    case 6:
+      hipLaunchKernelGGL(ingest_keypoints_ragged_kernel<6>, grid, block, 0, stream, data, block_offset, src_offsets, bound,
+                         count, out_dropped, n_pairs, n_rows, pts1, pts2, cov2, cov1, K_inv, kappa);
+      break;
+    case 12:
+      hipLaunchKernelGGL(ingest_keypoints_ragged_kernel<12>, grid, block, 0, stream, data, block_offset, src_offsets, bound,
+                         count, out_dropped, n_pairs, n_rows, pts1, pts2, cov2, cov1, K_inv, kappa);
+      break;
+    default:
+      hipLaunchKernelGGL(ingest_keypoints_ragged_kernel<18>, grid, block, 0, stream, data, block_offset, src_offsets, bound,
+                         count, out_dropped, n_pairs, n_rows, pts1, pts2, cov2, cov1, K_inv, kappa);
       break;
   }
   return hipGetLastError();

@@ -17,6 +17,14 @@ hipError_t launch_ingest_keypoints(int nc, int32_t n_max, double *data, const in
                                    const int32_t *count, int64_t first_pair, int64_t n_pairs, const double *pts1,
                                    const double *pts2, const double *cov2, const double *cov1, const double *K_inv,
                                    double kappa, hipStream_t stream);
+// the same shaped on the device, all n_pairs pairs: pair p takes the first min(rows, bound[p]) of the rows
+// [src_offsets[p], src_offsets[p + 1]) (cut to [0, n_rows]) and the kernel writes count[p] and out_dropped[p] (may be
+// null); n_max = the largest bound (sizes the grid).  n_pairs >= 1.
+hipError_t launch_ingest_keypoints_ragged(int nc, int32_t n_max, double *data, const int64_t *block_offset,
+                                          const int64_t *src_offsets, const int32_t *bound, int32_t *count,
+                                          int32_t *out_dropped, int64_t n_pairs, int64_t n_rows, const double *pts1,
+                                          const double *pts2, const double *cov2, const double *cov1, const double *K_inv,
+                                          double kappa, hipStream_t stream);
 hipError_t launch_unscented(int64_t n, const double *mu, const double *covs, const double *K_inv, double kappa,
                             int camera_model, double *out_bvs, double *out_covs, hipStream_t stream);
 // pnec::common::CostFunction of every pair of a TARGET-family batch at its pose

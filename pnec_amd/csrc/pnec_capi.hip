@@ -358,6 +358,7 @@ int problem_reshape_impl(pnec_hip_problem *p, int64_t n_pairs, const int64_t *of
   p->data_doubles = total;
   p->offsets.assign(offsets, offsets + n_pairs + 1);
   p->lazy = false;
+  p->bound_offsets.clear();  // (an exact shape again: pnec_hip_problem_fill_keypoints_ragged takes its bounds from this one)
   p->buckets.clear();
   if (p->d_bucket_pairs) (void)dev_free(p->d_bucket_pairs);  // (drains: only ragged multi-geometry shapes have one)
   p->d_bucket_pairs = nullptr;
@@ -680,6 +681,10 @@ int pnec_hip_problem_destroy(pnec_hip_problem *p) {
   if (p->meta_uploaded) {
     if (drained) pool_event_put(p->meta_uploaded, p->device); else (void)hipEventDestroy(p->meta_uploaded);
   }
+  if (p->bound_uploaded) {
+    if (drained) pool_event_put(p->bound_uploaded, p->device); else (void)hipEventDestroy(p->bound_uploaded);
+  }
+  release(p->d_bound);
   release(p->d_bucket_pairs);
   release(p->d_fill);
   delete p;
@@ -802,6 +807,77 @@ int pnec_hip_problem_fill_keypoints(pnec_hip_problem *p, int64_t first_pair, int
   }
   if (e != hipSuccess) return fail_hip(e, "ingest_keypoints_kernel");
   return 0;
+}
+
+int pnec_hip_problem_fill_keypoints_ragged(pnec_hip_problem *p, const int64_t *offsets, int64_t n_rows, const double *pts1,
+                                           const double *pts2, const double *cov2, const double *cov1, const double *K_inv,
+                                           double kappa, int camera_model, int32_t *out_dropped, int space, void *stream_) {
+  const char *name = "pnec_hip_problem_fill_keypoints_ragged";
+  const std::string pre = std::string(name) + ": ";
+  if (!p) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "problem is NULL");
+  if (p->cap_pairs <= 0 || !p->owns_data || !p->d_meta)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "not a capacity-shaped batch (pnec_hip_problem_create_capacity)");
+  if (camera_model != 1)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "keypoint ingest is pinhole only: camera_model must be 1");
+  if (int rc = check_space(pre, space)) return rc;
+  if (!offsets || !K_inv) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "offsets or K_inv is NULL");
+  if (n_rows < 0 || n_rows > 0x7fffffffLL) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "n_rows must be 0 .. 2^31-1");
+  if (n_rows > 0 && (!pts1 || !pts2)) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "pts1/pts2 is NULL");
+  // (whether a covariance array belongs does not depend on the rows offered: the sizes are the device's)
+  if ((p->nc >= 12) != (cov2 != nullptr))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "cov2 goes with TARGET, HOST and SYM batches and with no other");
+  if ((p->nc >= 18) != (cov1 != nullptr))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "cov1 goes with SYM batches and with no other");
+  const int64_t P = p->n_pairs;
+  if (P == 0) return 0;
+  if (space == PNEC_HIP_MEM_HOST) {
+    bool ok = offsets[0] >= 0 && offsets[P] <= n_rows;
+    for (int64_t k = 0; ok && k < P; ++k) ok = offsets[k] <= offsets[k + 1];
+    if (!ok) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "offsets must be non-decreasing within 0 .. n_rows");
+  }
+  hipStream_t stream = (hipStream_t)stream_;
+  struct {
+    const int64_t *offsets;
+    const double *pts1, *pts2, *cov2, *cov1, *K_inv;
+    int32_t *dropped;
+  } d;
+  CallArrays io(p, space, stream);
+  io.in(d.offsets, offsets, P + 1);
+  io.in(d.pts1, pts1, 2 * n_rows);
+  io.in(d.pts2, pts2, 2 * n_rows);
+  io.in(d.cov2, cov2, 3 * n_rows);
+  io.in(d.cov1, cov1, 3 * n_rows);
+  io.in(d.K_inv, K_inv, 9);
+  io.out(d.dropped, out_dropped, P);
+  // ---- the bounds: the shape pnec_hip_problem_reshape gave, on the host and (first call since) on the device
+  if (p->bound_offsets.empty()) {
+    if (!p->d_bound) PNEC_HIP_TRY(dev_alloc(&p->d_bound, sizeof(int32_t) * (size_t)p->cap_pairs));
+    if (p->bound_uploaded) PNEC_HIP_TRY(hipEventSynchronize(p->bound_uploaded));  // (the last upload has read bound_counts)
+    else PNEC_HIP_TRY(pool_event_get(&p->bound_uploaded));
+    p->bound_counts = p->host_counts;
+    PNEC_HIP_TRY(hipMemcpyAsync(p->d_bound, p->bound_counts.data(), sizeof(int32_t) * (size_t)P, hipMemcpyHostToDevice, stream));
+    PNEC_HIP_TRY(hipEventRecord(p->bound_uploaded, stream));
+    p->bound_offsets = p->offsets;
+  } else if (!p->lazy) {  // somebody asked for host-side sizes (materialize): back to the bounds, buckets included
+    p->offsets = p->bound_offsets;
+    p->host_counts = p->bound_counts;
+    p->n_corr = p->offsets[(size_t)P];
+    p->n_max = 0;
+    for (int32_t c : p->host_counts) p->n_max = std::max(p->n_max, c);
+    p->buckets.clear();
+    if (p->d_bucket_pairs) (void)dev_free(p->d_bucket_pairs);
+    p->d_bucket_pairs = nullptr;
+  }
+  if (int rc = io.commit()) return rc;
+  hipError_t e = launch_ingest_keypoints_ragged(p->nc, p->n_max, p->d_data, p->d_block_offset, d.offsets, p->d_bound, p->d_count,
+                                                d.dropped, P, n_rows, d.pts1, d.pts2, d.cov2, d.cov1, d.K_inv, kappa, stream);
+  if (e != hipSuccess) return fail_hip(e, "ingest_keypoints_ragged_kernel");
+  // the batch's own offsets: those of the rows kept
+  e = launch_offsets_scan(p->d_count, p->d_offsets, P, stream);
+  if (e != hipSuccess) return fail_hip(e, "offsets_scan_kernel");
+  p->lazy = true;
+  p->lazy_stream = stream;
+  return io.finish();
 }
 
 int64_t pnec_hip_problem_payload_doubles(const pnec_hip_problem *p) { return p ? p->data_doubles : 0; }

@@ -86,8 +86,17 @@ struct pnec_hip_problem {
   // the source's block layout (capacity) and its real pair sizes exist only in d_count until somebody
   // asks for host-side numbers.  While `lazy`, host_counts / n_max / n_corr / offsets hold the SOURCE's
   // values, i.e. upper bounds -- all the launch selection needs.
+  // A capacity batch filled by pnec_hip_problem_fill_keypoints_ragged is lazy in the same way: its shape (the last
+  // pnec_hip_problem_reshape) gives the bounds, the device-side offsets of the call the sizes.  bound_offsets keeps that
+  // shape (empty: no such call since the last reshape) so that a call after materialize() finds the bounds again;
+  // d_bound [cap_pairs] holds the bound per pair for the kernel, uploaded from bound_counts by the first call after a
+  // reshape (bound_uploaded: recorded behind that copy).
   bool lazy = false;
   hipStream_t lazy_stream = nullptr;   // the stream the device-side sizes were produced on
+  std::vector<int64_t> bound_offsets;
+  std::vector<int32_t> bound_counts;
+  int32_t *d_bound = nullptr;
+  hipEvent_t bound_uploaded = nullptr;
   bool owns_data = true;               // false: a re-typed view of another batch's buffers (NEC view of a TARGET batch)
   pnec_hip_problem *sel_view = nullptr;  // pipeline: cached InlierExtraction target (same capacity, reused)
   pnec_hip_problem *nec_view = nullptr;  // pipeline: this batch's bearings as a NEC-family batch (no copy)

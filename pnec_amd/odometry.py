@@ -1,0 +1,90 @@
+"""Images in, poses out: ``Odometry`` runs ``Tracker`` -> ``Batch.fill_keypoints_ragged`` -> ``Batch.solve_pipeline`` for F
+image sequences in lockstep, and no call of ``process`` reads anything back or waits.
+
+The tracker's correspondences are ragged by an offsets array only the device knows.  The batch is a capacity batch
+shaped ONCE, to the uniform bounds ``arange(F + 1) * capacity`` (a track set holds at most `capacity` rows per image);
+every frame the device-side offsets shape it inside those bounds (pnec_hip_problem_fill_keypoints_ragged), and the
+chain's launch geometries follow the bounds.
+
+The start pose of a pair is the reference's (frame_processing.cc:97-102): the previous pair's rotation with zero
+translation, the identity for the first pair -- and the identity wherever the previous result is not finite (an empty
+pair has no pose).
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import capi
+from .batch import Batch
+from .tracker import Tracker, TrackSet
+
+
+@dataclass
+class OdometryResult:
+    """One step of Odometry.process, everything torch.cuda on the tracker's device.  q, t, n_corr and init_q are fresh
+    tensors (the caller may keep them); `pairs` is the tracker's own buffer, overwritten by the next step."""
+    q: object        # [F,4] xyzw, the relative rotation of the pair (previous frame, this frame)
+    t: object        # [F,3] unit translation direction
+    n_corr: object   # int32 [F] correspondences per pair as the batch holds them: gate poses of empty or tiny pairs on it
+    pairs: TrackSet  # the correspondences (prev_pts, pts, cov, ragged by offsets): Tracker.process's result
+    init_q: object   # [F,4] the start rotation the chain was given
+
+
+def start_rotation(prev_q, identity):
+    """The rotation a pair's chain starts from: the previous pair's where every component is finite, else the identity.
+    prev_q [F,4] or None (the first pair), identity [F,4]; torch."""
+    import torch
+    if prev_q is None:
+        return identity.clone()
+    return torch.where(torch.isfinite(prev_q).all(dim=-1, keepdim=True), prev_q, identity)
+
+
+class Odometry:
+    """Tracker + one capacity Batch, all allocated in the constructor.
+
+    ``process(images)`` takes the next frame of every sequence ([F,h,w] torch.cuda) and returns None for the first frame,
+    then an OdometryResult per frame.  mode: capi.MODE_TARGET (the PNEC chain, covariances from the tracker) or
+    capi.MODE_NEC (bearings only; needs pipeline_options with use_nec).  K_inv [3,3]: host array or CUDA tensor.
+    tracker_kwargs go to Tracker (levels, ring, grid, capacity, ...).  Asynchronous on torch's current stream."""
+
+    def __init__(self, n_sequences: int, height: int, width: int, K_inv, mode: int = capi.MODE_TARGET,
+                 pipeline_options: capi.PipelineOptions | None = None, **tracker_kwargs):
+        import torch
+        if mode not in (capi.MODE_TARGET, capi.MODE_NEC):
+            raise ValueError("Odometry takes MODE_TARGET or MODE_NEC (what a tracker's covariances can fill)")
+        if mode == capi.MODE_NEC and (pipeline_options is None or not pipeline_options.use_nec):
+            raise ValueError("a MODE_NEC batch needs pipeline_options with use_nec")
+        self.tracker = Tracker(n_sequences, height, width, **tracker_kwargs)
+        F, cap, dev = self.tracker.n_sequences, self.tracker.capacity, self.tracker.device
+        self.n_sequences, self.capacity, self.mode, self.device = F, cap, int(mode), dev
+        self.pipeline_options = pipeline_options
+        with torch.cuda.device(dev):
+            self.batch = Batch.with_capacity(mode, F, F * cap, device=dev.index)
+            self.batch.reshape(np.arange(F + 1, dtype=np.int64) * cap)
+        f64 = dict(dtype=torch.float64, device=dev)
+        self._K_inv = torch.as_tensor(np.asarray(K_inv.cpu() if hasattr(K_inv, "cpu") else K_inv, dtype=np.float64), **f64)
+        if tuple(self._K_inv.shape) != (3, 3):
+            raise ValueError("K_inv must be [3,3]")
+        self._identity = torch.zeros((F, 4), **f64)
+        self._identity[:, 3] = 1.0
+        self._zero_t = torch.zeros((F, 3), **f64)
+        self._prev_q = None
+
+    def process(self, images):
+        import torch
+        pairs = self.tracker.process(images)
+        if pairs is None:
+            return None
+        with torch.cuda.device(self.device):
+            self.batch.fill_keypoints_ragged(pairs.offsets, pairs.prev_pts, pairs.pts,
+                                             pairs.cov if self.mode == capi.MODE_TARGET else None, K_inv=self._K_inv)
+            init_q = start_rotation(self._prev_q, self._identity)
+            q, t = self.batch.solve_pipeline(init_q, self._zero_t, self.pipeline_options)
+        n_corr = torch.diff(pairs.offsets).clamp(0, self.capacity).to(torch.int32)
+        self._prev_q = q
+        return OdometryResult(q, t, n_corr, pairs, init_q)
+
+    def close(self):
+        self.batch.close()

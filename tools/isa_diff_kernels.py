@@ -32,6 +32,13 @@ def kernels(path):
         if t and not t.endswith(":"):
             # branch offsets are relative: identical code has identical ones; keep the text as is
             out[cur].append(t)
+    for code in out.values():
+        # s_getpc_b64 s[N:N+1] / s_add_u32 sN, sN, <literal> is the address of a constant table: the literal is the
+        # distance from the instruction to the table, which moves whenever ANY kernel or descriptor is added to the file
+        for i in range(1, len(code)):
+            g = re.match(r"s_getpc_b64 s\[(\d+):\d+\]$", code[i - 1])
+            if g:
+                code[i] = re.sub(rf"^(s_add_u32 s{g.group(1)}, s{g.group(1)}, )\S+$", r"\1<pc-relative>", code[i])
     return out
 
 
