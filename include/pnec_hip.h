@@ -1069,6 +1069,73 @@ int pnec_hip_patch_track_indexed(const void *const *tmpl, const int64_t *tmpl_pi
                                  double *out_dist2, int32_t *out_status, int32_t *out_lost_level, int space, int device,
                                  void *stream);
 
+/* --- pnec_hip_tracks_keyframe: keyframe pairs -- skip frames that moved too little (added within ABI 8: a pure
+ * addition, PNEC_HIP_ABI_VERSION is unchanged).  The reference does not turn every frame into a pose:
+ * FrameProcessing::ProcessFrame (frame_processing.cc:87-93) asks TrackingMatcher::FindMatches (tracking_matcher.cc:68-85)
+ * for the mean pixel distance between the host frame's and the new frame's matched keypoints and skips the frame when
+ * that mean is below min_local_rad (5.0 at every caller); a skipped frame never enters the view graph, the next frame is
+ * matched by track id against the same host frame.  This call is that rule for n_images sequences in lockstep, after one
+ * step of the frame loop above, without a read-back.
+ *
+ * Per-track STATE, carried from call to call: key_pts double [n_key_rows, 2] and key_cov [n_key_rows, 3] hold where each
+ * row of the current set (the set after the last refill) was seen in its sequence's KEY FRAME, the last accepted frame --
+ * NaN for a track born after the key frame --, and span int32 [n_images] the number of frames between the key frame and
+ * the previous frame (0: the previous frame is the key frame; a negative span counts as 0).
+ * Inputs of one step:
+ *   the retained set B   offsets [n_images + 1], n_rows, pts [n_rows, 2], cov [n_rows, 3], src int64 [n_rows]:
+ *                        pnec_hip_tracks_retain's out_offsets, out_pts, out_cov, out_src -- src is the row of the set the
+ *                        track was retained from, which is the row of the state
+ *   the refilled set A'  new_offsets [n_images + 1], n_new, new_pts [n_new, 2], new_cov [n_new, 3]:
+ *                        pnec_hip_tracks_append's out_offsets, out_pts, out_cov when given B
+ *   the state, min_displacement >= 0 (finite), max_span >= 1.
+ * Row ranges of both sets are cut as everywhere: lo = clamp(offsets[f], 0, rows), hi = clamp(offsets[f+1], lo, rows).
+ * Per image f: a retained row k of its range is a MATCH iff 0 <= src[k] < n_key_rows, both words of key_pts[src[k]] are
+ * finite and both words of pts[k] are finite.  n_matches[f] is the count of matches; mean[f] the sum over the matches of
+ * sqrt(dx*dx + dy*dy), (dx, dy) = pts[k] - key_pts[src[k]], divided by n_matches -- NaN for n_matches == 0.
+ * THE ORDER OF THE SUM is fixed: with lo the first row of the image, lane l of 64 adds the displacements of the matches
+ * among rows lo + l, lo + l + 64, ... in that order, starting from +0.0; then six tree steps s = 32, 16, 8, 4, 2, 1, each
+ * v[l] += v[l + s] for l < s; the sum is v[0].  It is a function of the image's rows alone: not of the batch, of `space`,
+ * or of an atomic.
+ *   accepted[f] = !(mean < min_displacement) || span[f] + 1 >= max_span
+ * The first clause is the reference's comparison; a NaN mean (no match) is accepted, which moves the key frame on after
+ * every track was lost.  The second clause forces acceptance (DEVIATION below).
+ * PAIR outputs, arrays of n_rows rows: for an accepted image its matches in row order, compacted; for a skipped image
+ * nothing.  out_offsets int64 [n_images + 1] = the exclusive scan of accepted ? n_matches : 0; out_key_pts = key_pts[src],
+ * out_pts = pts, out_cov = cov, out_key_cov = key_cov[src] (for HOST / SYM batches), out_row int64 = the retained row k;
+ * rows at and beyond out_offsets[n_images] are padding, written to n_rows: NaN (0x7ff8000000000000) and out_row -1.
+ * pnec_hip_problem_fill_keypoints_ragged(offsets = out_offsets, pts1 = out_key_pts, pts2 = out_pts, cov2 = out_cov) takes
+ * them as they stand.  Per image, each may be NULL: out_accepted uint8 [n_images], out_mean double [n_images],
+ * out_n_matches int32 [n_images].
+ * NEXT STATE, laid out by A' (n_new rows; distinct arrays: double-buffer the state as the sets are): for image f,
+ * take = min(count_B[f], count_A'[f]) (pnec_hip_tracks_append's take_a, for every capacity).  Local row l < take of A' is
+ * retained row B.offsets[f] + l: of an accepted image it gets new_pts / new_cov of its own row, else key_pts[src] /
+ * key_cov[src] of that retained row, NaN for an src outside [0, n_key_rows).  Local row l >= take is a new detection: of
+ * an accepted image its own new_pts / new_cov, else NaN.  Rows at and beyond new_offsets[n_images] get NaN.
+ * next_span[f] = accepted ? 0 : span[f] + 1, saturating.
+ * FIRST-FRAME FORM: the retained set is absent (offsets, pts, cov, src NULL, n_rows == 0; key_pts, key_cov, span may be
+ * NULL and are not read).  Every image is accepted with n_matches 0 and mean NaN, all out_offsets are 0, the next state
+ * is A''s own new_pts / new_cov, next_span is 0.
+ * The covariance arrays cov, new_cov, key_cov, out_cov, out_key_cov, next_key_cov are given or NULL together (first-frame
+ * form: new_cov and next_key_cov); an array of no rows counts for neither side.
+ * DEVICE space: no allocation, no atomic, no wait; asynchronous on `stream`; offsets are not checked, only cut.  HOST
+ * space: staged, both offsets arrays are checked (from 0, non-decreasing, within their rows), the call blocks.
+ * PNEC_HIP_ERR_INVALID_ARGUMENT, before a device is touched: n_images < 1, a negative count, a retained set or a state
+ * given in part, the covariance arrays not given together, NULL new_offsets / new_pts / out_offsets / (n_rows > 0) a pair
+ * array, a NULL next-state array, min_displacement negative, NaN or infinite, max_span < 1, an output that is an input, a
+ * bad `space`; in HOST space also bad offsets.
+ * DEVIATION: pnec_amd.Tracker's ring retires a track at age R - 2, so a pair that spans more than R - 2 frames has no
+ * match: the caller caps the span (pnec_amd.KeyframeTracker: max_span defaults to R - 2 and more is refused), and a pair
+ * that spans s frames also lacks the tracks born before the key frame that aged out.  The reference keeps a track's
+ * patches for ever and has no such cap. */
+int pnec_hip_tracks_keyframe(int64_t n_images, const int64_t *offsets, int64_t n_rows, const double *pts,
+                             const double *cov, const int64_t *src, const int64_t *new_offsets, int64_t n_new,
+                             const double *new_pts, const double *new_cov, int64_t n_key_rows, const double *key_pts,
+                             const double *key_cov, const int32_t *span, double min_displacement, int32_t max_span,
+                             int64_t *out_offsets, double *out_key_pts, double *out_pts, double *out_cov,
+                             double *out_key_cov, int64_t *out_row, uint8_t *out_accepted, double *out_mean,
+                             int32_t *out_n_matches, double *next_key_pts, double *next_key_cov, int32_t *next_span,
+                             int space, int device, void *stream);
+
 /* Name and launch geometry the auto-tuner would pick for this problem (for logs / profiles). */
 int pnec_hip_describe_launch(const pnec_hip_problem *p, const pnec_hip_options *opt,
                              int32_t *corr_per_lane, int32_t *waves_per_pair,

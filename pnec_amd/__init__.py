@@ -6,6 +6,7 @@ Layout:
   batch.py         batches of frame pairs in HBM; numpy (host space) or torch.cuda (device space)
   patches.py       2x2 keypoint covariances from image patches (the cov input of Batch.fill_keypoints)
   tracker.py       tracks across frames: retain, refill, and the frame loop over F sequences in lockstep
+  keyframes.py     keyframe pairs: skip frames that moved too little against the last accepted frame
   odometry.py      images in, poses out: the tracker, a batch shaped from its device offsets, and the chain
   simulation.py    synthetic inputs following the reference simulator's distributions (harness)
   distributed.py   one-process-per-GPU sharding of independent pair batches + one RCCL gather
@@ -13,11 +14,12 @@ Layout:
 from . import capi  # noqa: F401
 from .batch import (Batch, PoseCovariance, RelativeScale, ResidualReport, SolveResult, Triangulation, gate_sigma,  # noqa: F401
                     select_best)
+from .keyframes import KeyframePairs, KeyframeState, KeyframeTracker, keyframe_pairs  # noqa: F401
 from .odometry import Odometry, OdometryResult  # noqa: F401
 from .patches import (PATTERN52, Keypoints, PatchCovariance, PatchTrack, detect_keypoints, image_pyramid,  # noqa: F401
                       patch_covariance, patch_track)
 from .tracker import Tracker, TrackSet, append_tracks, retain_tracks  # noqa: F401
 from .tracks import chain_scales  # noqa: F401
 
-__all__ = ["capi", "Batch", "Keypoints", "Odometry", "OdometryResult", "PATTERN52", "PatchCovariance", "PatchTrack", "PoseCovariance", "RelativeScale", "ResidualReport", "SolveResult",
-           "TrackSet", "Tracker", "Triangulation", "append_tracks", "chain_scales", "detect_keypoints", "gate_sigma", "image_pyramid", "patch_covariance", "patch_track", "retain_tracks", "select_best"]
+__all__ = ["capi", "Batch", "KeyframePairs", "KeyframeState", "KeyframeTracker", "Keypoints", "Odometry", "OdometryResult", "PATTERN52", "PatchCovariance", "PatchTrack", "PoseCovariance", "RelativeScale", "ResidualReport", "SolveResult",
+           "TrackSet", "Tracker", "Triangulation", "append_tracks", "chain_scales", "detect_keypoints", "gate_sigma", "image_pyramid", "keyframe_pairs", "patch_covariance", "patch_track", "retain_tracks", "select_best"]

@@ -74,6 +74,7 @@ SYMBOLS = [
     "pnec_hip_detect_keypoints",
     "pnec_hip_tracks_retain",
     "pnec_hip_tracks_append",
+    "pnec_hip_tracks_keyframe",
     "pnec_hip_patch_track_indexed",
     "pnec_hip_nec_eigensolver",
     "pnec_hip_ransac_eigensolver",
@@ -241,6 +242,8 @@ def lib() -> C.CDLL:
     L.pnec_hip_tracks_append.argtypes = [C.c_int64, _vp, C.c_int64] + [_vp] * 8 + [C.c_int64, _vp, _vp, C.c_int32, C.c_int64,
                                                                                  _vp, C.c_int64] + [_vp] * 9 + \
         [C.c_int, C.c_int, _vp]
+    L.pnec_hip_tracks_keyframe.argtypes = [C.c_int64, _vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp, _vp,
+                                           C.c_double, C.c_int32] + [_vp] * 12 + [C.c_int, C.c_int, _vp]
     L.pnec_hip_patch_track_indexed.argtypes = [_vp, _vp, C.c_int64] + [_vp] * 4 + [
         C.c_int32, C.c_int, C.c_int64, C.c_int32, C.c_int32, _vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp,
         C.c_int32, C.c_int32, C.c_double, C.c_uint32, C.c_double] + [_vp] * 6 + [C.c_int, C.c_int, _vp]

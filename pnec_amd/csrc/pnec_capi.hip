@@ -17,6 +17,7 @@
 #include "pnec_detect.hpp"
 #include "pnec_front_shared.hpp"
 #include "pnec_internal.hpp"
+#include "pnec_keyframe.hpp"
 #include "pnec_patch_cov.hpp"
 #include "pnec_patch_track.hpp"
 #include "pnec_pose_cov.hpp"
@@ -1720,6 +1721,105 @@ int pnec_hip_tracks_append(int64_t n_images, const int64_t *offsets, int64_t n_r
   io.out(a.out_dropped, out_dropped, n_images);
   if (int rc = io.commit()) return rc;
   PNEC_HIP_TRY(launch_tracks_append(a, stream));
+  return io.finish();
+}
+
+// keyframe pairs: pnec_keyframe.hip.  Staged like the two calls above.
+int pnec_hip_tracks_keyframe(int64_t n_images, const int64_t *offsets, int64_t n_rows, const double *pts,
+                             const double *cov, const int64_t *src, const int64_t *new_offsets, int64_t n_new,
+                             const double *new_pts, const double *new_cov, int64_t n_key_rows, const double *key_pts,
+                             const double *key_cov, const int32_t *span, double min_displacement, int32_t max_span,
+                             int64_t *out_offsets, double *out_key_pts, double *out_pts, double *out_cov,
+                             double *out_key_cov, int64_t *out_row, uint8_t *out_accepted, double *out_mean,
+                             int32_t *out_n_matches, double *next_key_pts, double *next_key_cov, int32_t *next_span,
+                             int space, int device, void *stream_) {
+  const std::string pre = "tracks_keyframe: ";
+  if (n_images < 1 || n_rows < 0 || n_new < 0 || n_key_rows < 0)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "n_images must be >= 1, n_rows, n_new and n_key_rows >= 0");
+  const bool no_set = !offsets;
+  if (no_set && (n_rows != 0 || pts || cov || src))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT,
+                pre + "a retained set given in part: without offsets (no set) pts, cov and src are NULL and n_rows is 0");
+  if (!no_set && n_rows > 0 && (!pts || !src))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "a retained set given in part: pts or src is NULL");
+  // the state: wanted with a retained set, optional (and not read) without one
+  const bool state = !no_set || key_pts || key_cov || span || n_key_rows > 0;
+  if (state && (!span || (n_key_rows > 0 && !key_pts) || (key_cov && !key_pts)))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "the state given in part: span or key_pts is NULL");
+  if (!new_offsets || (n_new > 0 && !new_pts))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "new_offsets or new_pts is NULL");
+  if (!out_offsets) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "out_offsets is NULL");
+  if (!next_span || (n_new > 0 && !next_key_pts))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "a next-state array (next_key_pts, next_span) is NULL");
+  if (n_rows > 0 && (!out_key_pts || !out_pts || !out_row))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "out_key_pts, out_pts or out_row is NULL");
+  {
+    // (an array of no rows says nothing: a caller's empty array may have no address)
+    int given = 0, absent = 0;
+    auto note = [&](const void *ptr, int64_t rows) { (ptr ? given : absent) += rows > 0; };
+    note(new_cov, n_new);
+    note(next_key_cov, n_new);
+    if (!no_set) {
+      note(cov, n_rows);
+      note(out_cov, n_rows);
+      note(out_key_cov, n_rows);
+      note(key_cov, n_key_rows);
+    }
+    if (given && absent)
+      return fail(PNEC_HIP_ERR_INVALID_ARGUMENT,
+                  pre + "cov, new_cov, key_cov, out_cov, out_key_cov and next_key_cov are given or NULL together");
+  }
+  if (!(min_displacement >= 0.0) || std::isinf(min_displacement))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "min_displacement must be finite and >= 0");
+  if (max_span < 1) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "max_span must be >= 1");
+  if (n_images > 0x7fffffffLL || n_rows > (int64_t)1 << 40 || n_new > (int64_t)1 << 40 || n_key_rows > (int64_t)1 << 40)
+    return fail(PNEC_HIP_ERR_UNSUPPORTED, pre + "too many images or rows");
+  const void *ins[] = {offsets, pts, cov, src, new_offsets, new_pts, new_cov, key_pts, key_cov, span};
+  void *outs[] = {out_offsets, out_key_pts, out_pts, out_cov, out_key_cov, out_row, out_accepted, out_mean,
+                  out_n_matches, next_key_pts, next_key_cov, next_span};
+  for (void *o : outs)
+    for (const void *i : ins)
+      if (o && o == i) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "an output is an input (the outputs are fresh arrays)");
+  if (int rc = check_space(pre, space)) return rc;
+  if (space == PNEC_HIP_MEM_HOST) {
+    if (!no_set)
+      if (int rc = check_set_offsets(pre, "offsets", offsets, n_images, n_rows, "n_rows")) return rc;
+    if (int rc = check_set_offsets(pre, "new_offsets", new_offsets, n_images, n_new, "n_new")) return rc;
+  }
+  hipStream_t stream = (hipStream_t)stream_;
+  CallArrays io(device, space, stream);
+  KeyframeArgs a{};
+  a.n_images = n_images;
+  a.n_rows = n_rows;
+  a.n_new = n_new;
+  a.n_key_rows = no_set ? 0 : n_key_rows;
+  a.min_displacement = min_displacement;
+  a.max_span = max_span;
+  const int64_t N = n_rows, A = n_new, S = a.n_key_rows;
+  io.in(a.offsets, offsets, n_images + 1);
+  io.in(a.pts, pts, 2 * N);
+  io.in(a.cov, cov, 3 * N);
+  io.in(a.src, src, N);
+  io.in(a.new_offsets, new_offsets, n_images + 1);
+  io.in(a.new_pts, new_pts, 2 * A);
+  io.in(a.new_cov, new_cov, 3 * A);
+  io.in(a.key_pts, no_set ? nullptr : key_pts, 2 * S);   // (the first-frame form reads no state)
+  io.in(a.key_cov, no_set ? nullptr : key_cov, 3 * S);
+  io.in(a.span, no_set ? nullptr : span, n_images);
+  io.out(a.out_offsets, out_offsets, n_images + 1);
+  io.out(a.out_key_pts, out_key_pts, 2 * N);
+  io.out(a.out_pts, out_pts, 2 * N);
+  io.out(a.out_cov, no_set ? nullptr : out_cov, 3 * N);
+  io.out(a.out_key_cov, no_set ? nullptr : out_key_cov, 3 * N);
+  io.out(a.out_row, out_row, N);
+  io.out(a.out_accepted, out_accepted, n_images);
+  io.out(a.out_mean, out_mean, n_images);
+  io.out(a.out_n_matches, out_n_matches, n_images);
+  io.out(a.next_key_pts, next_key_pts, 2 * A);
+  io.out(a.next_key_cov, next_key_cov, 3 * A);
+  io.out(a.next_span, next_span, n_images);
+  if (int rc = io.commit()) return rc;
+  PNEC_HIP_TRY(launch_tracks_keyframe(a, stream));
   return io.finish();
 }
 

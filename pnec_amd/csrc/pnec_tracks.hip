@@ -22,30 +22,6 @@
 
 namespace pnec_hip {
 
-// v[1 .. F] hold per-image counts (count(f) for f < F): the running sum in place, 256 images at a time, and v[0] = 0
-template <typename Count>
-__device__ __forceinline__ void tracks_block_scan(int64_t *v, int64_t F, Count count) {
-  __shared__ int64_t part[256];
-  int64_t carry = 0;
-  for (int64_t base = 0; base < F; base += 256) {
-    const int64_t f = base + threadIdx.x;
-    int64_t x = f < F ? count(f) : 0;
-    part[threadIdx.x] = x;
-    __syncthreads();
-    for (int s = 1; s < 256; s <<= 1) {
-      const int64_t o = (int)threadIdx.x >= s ? part[threadIdx.x - s] : 0;
-      __syncthreads();
-      x += o;
-      part[threadIdx.x] = x;
-      __syncthreads();
-    }
-    if (f < F) v[f + 1] = carry + x;
-    carry += part[255];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) v[0] = 0;
-}
-
 __global__ __launch_bounds__(kTracksBlock) void tracks_retain_count_kernel(const TracksRetainArgs a) {
   const int wave = threadIdx.x / kTracksLanes, lane = threadIdx.x & (kTracksLanes - 1);
   const int64_t f = (int64_t)blockIdx.x * kTracksWaves + wave;

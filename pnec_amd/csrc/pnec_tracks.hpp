@@ -257,6 +257,31 @@ PNEC_TRACKS_HD void tracks_append_row(const TracksAppendArgs &a, int64_t i) {
 }
 
 #if defined(__HIPCC__)
+// (shared by pnec_tracks.hip and pnec_keyframe.hip: one block of 256 lanes)
+// v[1 .. F] hold per-image counts (count(f) for f < F): the running sum in place, 256 images at a time, and v[0] = 0
+template <typename Count>
+__device__ __forceinline__ void tracks_block_scan(int64_t *v, int64_t F, Count count) {
+  __shared__ int64_t part[256];
+  int64_t carry = 0;
+  for (int64_t base = 0; base < F; base += 256) {
+    const int64_t f = base + threadIdx.x;
+    int64_t x = f < F ? count(f) : 0;
+    part[threadIdx.x] = x;
+    __syncthreads();
+    for (int s = 1; s < 256; s <<= 1) {
+      const int64_t o = (int)threadIdx.x >= s ? part[threadIdx.x - s] : 0;
+      __syncthreads();
+      x += o;
+      part[threadIdx.x] = x;
+      __syncthreads();
+    }
+    if (f < F) v[f + 1] = carry + x;
+    carry += part[255];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) v[0] = 0;
+}
+
 // four launches: count, scan, emit, pad
 hipError_t launch_tracks_retain(const TracksRetainArgs &a, hipStream_t stream);
 // three launches: scan (with out_dropped), emit, next_id

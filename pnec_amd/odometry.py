@@ -9,6 +9,10 @@ chain's launch geometries follow the bounds.
 The start pose of a pair is the reference's (frame_processing.cc:97-102): the previous pair's rotation with zero
 translation, the identity for the first pair -- and the identity wherever the previous result is not finite (an empty
 pair has no pose).
+
+With ``min_displacement > 0`` the pairs are keyframe pairs (keyframes.py): a sequence whose frame moved too little
+against its key frame is skipped -- its pose is NaN, its n_corr 0 -- and the chain of a later pair starts from the last
+ACCEPTED pair's rotation (the reference's PrevRelRotation).
 """
 from __future__ import annotations
 
@@ -18,6 +22,7 @@ import numpy as np
 
 from . import capi
 from .batch import Batch
+from .keyframes import KeyframeTracker
 from .tracker import Tracker, TrackSet
 
 
@@ -30,6 +35,10 @@ class OdometryResult:
     n_corr: object   # int32 [F] correspondences per pair as the batch holds them: gate poses of empty or tiny pairs on it
     pairs: TrackSet  # the correspondences (prev_pts, pts, cov, ragged by offsets): Tracker.process's result
     init_q: object   # [F,4] the start rotation the chain was given
+    # keyframes on (min_displacement > 0) only; `pairs` is then the KeyframePairs, and q / t of a skipped sequence are NaN
+    accepted: object = None           # uint8 [F]
+    mean_displacement: object = None  # [F] mean pixel distance of the matches against the key frame, NaN without a match
+    span: object = None               # int32 [F] frames between the key frame and this frame after the step (0: accepted)
 
 
 def start_rotation(prev_q, identity):
@@ -47,16 +56,27 @@ class Odometry:
     ``process(images)`` takes the next frame of every sequence ([F,h,w] torch.cuda) and returns None for the first frame,
     then an OdometryResult per frame.  mode: capi.MODE_TARGET (the PNEC chain, covariances from the tracker) or
     capi.MODE_NEC (bearings only; needs pipeline_options with use_nec).  K_inv [3,3]: host array or CUDA tensor.
-    tracker_kwargs go to Tracker (levels, ring, grid, capacity, ...).  Asynchronous on torch's current stream."""
+    tracker_kwargs go to Tracker (levels, ring, grid, capacity, ...).  Asynchronous on torch's current stream.
+
+    min_displacement > 0 turns keyframes on (KeyframeTracker: ring >= 4, max_span in 1 .. ring - 2, default ring - 2); with
+    the default 0 every consecutive pair is solved, as before, and nothing of the keyframe machinery is created."""
 
     def __init__(self, n_sequences: int, height: int, width: int, K_inv, mode: int = capi.MODE_TARGET,
-                 pipeline_options: capi.PipelineOptions | None = None, **tracker_kwargs):
+                 pipeline_options: capi.PipelineOptions | None = None, min_displacement: float = 0.0, max_span: int = None,
+                 **tracker_kwargs):
         import torch
         if mode not in (capi.MODE_TARGET, capi.MODE_NEC):
             raise ValueError("Odometry takes MODE_TARGET or MODE_NEC (what a tracker's covariances can fill)")
         if mode == capi.MODE_NEC and (pipeline_options is None or not pipeline_options.use_nec):
             raise ValueError("a MODE_NEC batch needs pipeline_options with use_nec")
-        self.tracker = Tracker(n_sequences, height, width, **tracker_kwargs)
+        if not float(min_displacement) >= 0.0:
+            raise ValueError("min_displacement must be >= 0")
+        self.keyframes = None
+        if float(min_displacement) > 0.0:
+            self.keyframes = KeyframeTracker(n_sequences, height, width, min_displacement, max_span, **tracker_kwargs)
+            self.tracker = self.keyframes.tracker
+        else:
+            self.tracker = Tracker(n_sequences, height, width, **tracker_kwargs)
         F, cap, dev = self.tracker.n_sequences, self.tracker.capacity, self.tracker.device
         self.n_sequences, self.capacity, self.mode, self.device = F, cap, int(mode), dev
         self.pipeline_options = pipeline_options
@@ -72,8 +92,28 @@ class Odometry:
         self._zero_t = torch.zeros((F, 3), **f64)
         self._prev_q = None
 
+    def _process_keyframes(self, images):
+        import torch
+        pairs = self.keyframes.process(images)
+        if pairs is None:
+            return None
+        with torch.cuda.device(self.device):
+            self.batch.fill_keypoints_ragged(pairs.offsets, pairs.key_pts, pairs.pts,
+                                             pairs.cov if self.mode == capi.MODE_TARGET else None, K_inv=self._K_inv)
+            init_q = start_rotation(self._prev_q, self._identity)
+            q, t = self.batch.solve_pipeline(init_q, self._zero_t, self.pipeline_options)
+        accepted = pairs.accepted.to(torch.bool)[:, None]
+        nan = torch.full_like(q[:, :1], float("nan"))
+        # the next chain starts from the last accepted pair's rotation (NaN before any: start_rotation's identity)
+        self._prev_q = torch.where(accepted, q, nan if self._prev_q is None else self._prev_q)
+        n_corr = torch.diff(pairs.offsets).clamp(0, self.capacity).to(torch.int32)
+        return OdometryResult(torch.where(accepted, q, nan), torch.where(accepted, t, nan), n_corr, pairs, init_q,
+                              pairs.accepted.clone(), pairs.mean_displacement.clone(), self.keyframes.state.span.clone())
+
     def process(self, images):
         import torch
+        if self.keyframes is not None:
+            return self._process_keyframes(images)
         pairs = self.tracker.process(images)
         if pairs is None:
             return None
