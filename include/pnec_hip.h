@@ -38,6 +38,8 @@
  *    (basalt's detectKeypoints on a grid + cv::FAST [EXT]: the detector only)
  *   KLTPatchOpticalFlow::processFrame klt_patch_optical_flow.h:121-191      pnec_hip_tracks_retain, pnec_hip_tracks_append,
  *    (ids, the surviving tracks, the refill, a template image per track)     pnec_hip_patch_track_indexed
+ *   OpticalFlowPatch kept per track klt_patch_optical_flow.h:344-385, :228     pnec_hip_patch_store_add,
+ *    (a slot per track filled at birth, the tracker reading its templates)   pnec_hip_patch_track_stored
  *   PNEC::Eigensolver (no RANSAC) / WeightedEigensolver  pnec.cc:231-348   pnec_hip_nec_eigensolver /
  *                                                               pnec_hip_weighted_eigensolver
  *
@@ -1042,7 +1044,8 @@ int pnec_hip_detect_keypoints(const void *images, int pixel_type, int64_t n_imag
  * tracks_retain (max_age = R - 2) -> detect_keypoints (current = the retained set) -> patch_covariance ->
  * tracks_append (tmpl_image_base = slot * n_images), none of which reads anything back.  DEVIATION: the reference keeps a
  * track's patch for ever; here a track is retired when its age would reach R - 1, the step before its birth frame's slot
- * is overwritten, and the pair loses that track's correspondence on that step. */
+ * is overwritten, and the pair loses that track's correspondence on that step.  The stored form below
+ * (pnec_hip_patch_store_add, pnec_hip_patch_track_stored; pnec_amd.Tracker(templates="patches")) lifts it. */
 int pnec_hip_tracks_retain(int64_t n_images, const int64_t *offsets, int64_t n_rows, const int64_t *id,
                            const int32_t *tmpl_image, const double *tmpl_pts, const int32_t *age, const double *pts,
                            const double *cov, const double *trk_pts, const double *trk_angle, const double *trk_cov,
@@ -1126,7 +1129,8 @@ int pnec_hip_patch_track_indexed(const void *const *tmpl, const int64_t *tmpl_pi
  * DEVIATION: pnec_amd.Tracker's ring retires a track at age R - 2, so a pair that spans more than R - 2 frames has no
  * match: the caller caps the span (pnec_amd.KeyframeTracker: max_span defaults to R - 2 and more is refused), and a pair
  * that spans s frames also lacks the tracks born before the key frame that aged out.  The reference keeps a track's
- * patches for ever and has no such cap. */
+ * patches for ever and has no such cap.  The stored form below lifts it: with pnec_amd.KeyframeTracker(templates=
+ * "patches") a track lives as long as it is tracked, any max_span >= 1 is taken and none forces no acceptance. */
 int pnec_hip_tracks_keyframe(int64_t n_images, const int64_t *offsets, int64_t n_rows, const double *pts,
                              const double *cov, const int64_t *src, const int64_t *new_offsets, int64_t n_new,
                              const double *new_pts, const double *new_cov, int64_t n_key_rows, const double *key_pts,
@@ -1135,6 +1139,85 @@ int pnec_hip_tracks_keyframe(int64_t n_images, const int64_t *offsets, int64_t n
                              double *out_key_cov, int64_t *out_row, uint8_t *out_accepted, double *out_mean,
                              int32_t *out_n_matches, double *next_key_pts, double *next_key_cov, int32_t *next_span,
                              int space, int device, void *stream);
+
+/* Stored patches: a track keeps its templates for as long as it lives (added within ABI 8: pure additions,
+ * PNEC_HIP_ABI_VERSION is unchanged).  The reference (klt_patch_optical_flow.h:344-385) builds an OpticalFlowPatch per
+ * pyramid level when a point is added -- the mean-normalised intensities `data`, the gain H_se2_inv_J_se2_T, the level's
+ * Hessian -- and keeps them until the track is lost (:228, :256-280).  A PATCH STORE is device (or, in HOST space, host)
+ * memory of n_slots slots of pnec_hip_patch_store_slot_bytes(n_levels) bytes each, one slot per track, filled when the
+ * track is born; the set's tmpl_image column then holds the track's slot instead of an image index, and
+ * pnec_hip_tracks_retain / _append carry it along unchanged.
+ *
+ * --- pnec_hip_patch_store_slot_bytes: the size of one slot, 8 (32 + 256 n_levels); 0 for n_levels outside 1 .. 8.
+ * Callers only allocate n_slots * slot_bytes (8-byte aligned; 256-byte aligned makes every plane start on a 128-byte line).
+ * The layout is the library's own, in 64-bit words:
+ *   word 0 int64 n, word 1 double S, words 2 .. 7 double H[6] (00 01 02 11 12 22): the level-0 template's sums, which the
+ *   covariance epilogue needs; word 8 + l int64 level l's template status (pnec_hip_patch_status of the template's full
+ *   inverse); word 16 + l uint64 level l's validity, bit i pattern point i's; words 24 .. 31 zero; then per level l, from
+ *   word 32 + 256 l, four planes of 64 doubles: the normalised value (n v_i) / S of each pattern point and the three
+ *   components of its gain K_i = H^-1 J_i'.  Storage is double: the tracker's bits are those of the rebuilt template.
+ *
+ * --- pnec_hip_patch_store_add: gives every new row of a refilled set a slot and fills it.
+ * Input: the current frame's pyramid cur / cur_pitch (n_levels levels in pnec_hip_patch_track's layout, pixel_type,
+ * n_images, height, width); carried_offsets int64 [n_images + 1], the offsets of the retained set the refill started from,
+ * or NULL on the first frame; the refilled set's offsets int64 [n_images + 1], n_rows, tmpl_pts [n_rows, 2] and its
+ * tmpl_image column `slot` int32 [n_rows], READ AND WRITTEN IN PLACE; per_image_capacity C; pattern / n_pattern; the
+ * store and n_slots >= n_images C.
+ * With a_f the count of image f in carried_offsets (0 when NULL; a negative one counts as 0) and c_f its count in offsets,
+ * take_f = min(a_f, c_f) (pnec_hip_tracks_append's take_a).  Rows with local index < take_f are CARRIED: their slot is
+ * read and left alone.  The others are NEW.  The occupied local slots of image f are slot[r] - f C over its carried rows;
+ * a value outside [0, C) is ignored in DEVICE space and refused in HOST space.  The i-th new row, in row order, gets the
+ * global slot f C + (the i-th smallest free local slot); a new row for which no slot is free (only when c_f > C) gets -1
+ * and no patch; rows at and beyond offsets[n_images] (padding) get -1.  The assignment is a function of the image's rows
+ * alone: no atomic on device memory decides a slot, nothing is allocated, nothing waits.
+ * Then, for every new row that has a slot, the templates of all levels are built at tmpl_pts / 2^l in the row's own image
+ * of `cur` and written into the slot: the terms pnec_hip_patch_track computes for a template, in its order of operations.
+ * Other slots of the store are not touched.
+ * DEVICE space: asynchronous on `stream`, offsets are not checked, only cut to the rows there are.  HOST space:
+ * everything is staged (the whole store travels up and back), offsets and carried slots are checked, the call blocks.
+ * n_rows = 0 returns at once.
+ * PNEC_HIP_ERR_INVALID_ARGUMENT, before a device is touched: NULL cur / cur_pitch / a level pointer / offsets / pattern /
+ * store / (n_rows > 0) tmpl_pts or slot, n_levels outside 1 .. 8, n_pattern outside 1 .. 64, an unknown pixel_type,
+ * n_images < 1, n_rows < 0, a level smaller than 4 pixels, a pitch below its level's width, C < 1,
+ * C > PNEC_HIP_PATCH_STORE_MAX_CAPACITY (65536: the assignment keeps an image's occupancy map in LDS), n_images C not
+ * fitting int32, n_slots < n_images C or not fitting int32, an output (slot, store) that is an input, a bad `space`; in
+ * HOST space also offsets or carried_offsets that do not run from 0 without decreasing (offsets: to at most n_rows) and
+ * a carried row whose slot is not one of its image's.
+ *
+ * --- pnec_hip_patch_track_stored: pnec_hip_patch_track with the templates read from the store.
+ * pnec_hip_patch_track_indexed's arguments with store, n_slots in place of tmpl, tmpl_pitch, n_tmpl_images, and slot int32
+ * [n_points] in place of tmpl_image; prev is required.  Everything that is not the template is pnec_hip_patch_track's
+ * definition, bit for bit, and a call whose slots were filled by pnec_hip_patch_store_add from the image, the point and
+ * the pattern an indexed call would build its templates from returns the indexed call's bits in every output.  The
+ * pattern must be the one the slots were built with (it still places the points in prev and next).  A row whose slot lies
+ * outside [0, n_slots) comes back as a template that is bad at the top level: status PNEC_HIP_TRACK_BAD_TEMPLATE,
+ * lost_level n_levels - 1, out_pts the start + shift, out_angle the start angle, out_cov and out_dist2 NaN -- what the
+ * indexed call returns for a set's NaN padding rows.  The row-to-image map is that of a track set: rows at and beyond
+ * offsets[n_images] are padding.  HOST space: offsets run from 0 to at most n_points without decreasing, and a slot
+ * outside [0, n_slots) on a row below offsets[n_images] is PNEC_HIP_ERR_INVALID_ARGUMENT; the store is staged whole.
+ * PNEC_HIP_ERR_INVALID_ARGUMENT: pnec_hip_patch_track's list, and NULL store / slot / prev, n_slots outside 1 .. 2^31 - 1,
+ * an output that is the store or the slot column.
+ *
+ * The frame loop with stored patches (pnec_amd.Tracker(templates="patches")): two pyramids suffice; per frame pyramid ->
+ * patch_track_stored (prev / next = the two pyramids, init = the set) -> tracks_retain (max_age = 0) -> detect_keypoints
+ * -> patch_covariance -> tracks_append -> patch_store_add (cur = this frame, carried_offsets = the retained set's), seven
+ * calls, none of which reads anything back.  A track keeps its slot until it is lost; the slot is free from the next
+ * patch_store_add on. */
+#define PNEC_HIP_PATCH_STORE_MAX_CAPACITY 65536
+int64_t pnec_hip_patch_store_slot_bytes(int32_t n_levels);
+int pnec_hip_patch_store_add(const void *const *cur, const int64_t *cur_pitch, int32_t n_levels, int pixel_type,
+                             int64_t n_images, int32_t height, int32_t width, const int64_t *carried_offsets,
+                             const int64_t *offsets, int64_t n_rows, const double *tmpl_pts, int32_t *slot,
+                             int64_t per_image_capacity, const double *pattern, int32_t n_pattern, double *store,
+                             int64_t n_slots, int space, int device, void *stream);
+int pnec_hip_patch_track_stored(const double *store, int64_t n_slots, const void *const *prev, const int64_t *prev_pitch,
+                                const void *const *next, const int64_t *next_pitch, int32_t n_levels, int pixel_type,
+                                int64_t n_images, int32_t height, int32_t width, const int64_t *offsets, int64_t n_points,
+                                const double *tmpl_pts, const int32_t *slot, const double *init_pts,
+                                const double *init_angle, double shift_x, double shift_y, const double *pattern,
+                                int32_t n_pattern, int32_t max_iterations, double max_recovered_dist2, uint32_t flags,
+                                double scaling, double *out_pts, double *out_angle, double *out_cov, double *out_dist2,
+                                int32_t *out_status, int32_t *out_lost_level, int space, int device, void *stream);
 
 /* Name and launch geometry the auto-tuner would pick for this problem (for logs / profiles). */
 int pnec_hip_describe_launch(const pnec_hip_problem *p, const pnec_hip_options *opt,

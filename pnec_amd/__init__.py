@@ -6,6 +6,7 @@ Layout:
   batch.py         batches of frame pairs in HBM; numpy (host space) or torch.cuda (device space)
   patches.py       2x2 keypoint covariances from image patches (the cov input of Batch.fill_keypoints)
   tracker.py       tracks across frames: retain, refill, and the frame loop over F sequences in lockstep
+  patch_store.py   stored patches: a slot per track that keeps its templates for as long as it lives
   keyframes.py     keyframe pairs: skip frames that moved too little against the last accepted frame
   odometry.py      images in, poses out: the tracker, a batch shaped from its device offsets, and the chain
   simulation.py    synthetic inputs following the reference simulator's distributions (harness)
@@ -19,7 +20,8 @@ from .odometry import Odometry, OdometryResult  # noqa: F401
 from .patches import (PATTERN52, Keypoints, PatchCovariance, PatchTrack, detect_keypoints, image_pyramid,  # noqa: F401
                       patch_covariance, patch_track)
 from .tracker import Tracker, TrackSet, append_tracks, retain_tracks  # noqa: F401
+from .patch_store import PatchStore, add_patches, new_patch_store, patch_track_stored  # noqa: F401
 from .tracks import chain_scales  # noqa: F401
 
-__all__ = ["capi", "Batch", "KeyframePairs", "KeyframeState", "KeyframeTracker", "Keypoints", "Odometry", "OdometryResult", "PATTERN52", "PatchCovariance", "PatchTrack", "PoseCovariance", "RelativeScale", "ResidualReport", "SolveResult",
-           "TrackSet", "Tracker", "Triangulation", "append_tracks", "chain_scales", "detect_keypoints", "gate_sigma", "image_pyramid", "keyframe_pairs", "patch_covariance", "patch_track", "retain_tracks", "select_best"]
+__all__ = ["capi", "Batch", "KeyframePairs", "KeyframeState", "KeyframeTracker", "Keypoints", "Odometry", "OdometryResult", "PATTERN52", "PatchCovariance", "PatchStore", "PatchTrack", "PoseCovariance", "RelativeScale", "ResidualReport", "SolveResult",
+           "TrackSet", "Tracker", "Triangulation", "add_patches", "append_tracks", "chain_scales", "detect_keypoints", "gate_sigma", "image_pyramid", "keyframe_pairs", "new_patch_store", "patch_covariance", "patch_track", "patch_track_stored", "retain_tracks", "select_best"]

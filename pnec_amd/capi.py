@@ -76,6 +76,9 @@ SYMBOLS = [
     "pnec_hip_tracks_append",
     "pnec_hip_tracks_keyframe",
     "pnec_hip_patch_track_indexed",
+    "pnec_hip_patch_store_slot_bytes",
+    "pnec_hip_patch_store_add",
+    "pnec_hip_patch_track_stored",
     "pnec_hip_nec_eigensolver",
     "pnec_hip_ransac_eigensolver",
     "pnec_hip_problem_select",
@@ -245,6 +248,13 @@ def lib() -> C.CDLL:
     L.pnec_hip_tracks_keyframe.argtypes = [C.c_int64, _vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp, _vp,
                                            C.c_double, C.c_int32] + [_vp] * 12 + [C.c_int, C.c_int, _vp]
     L.pnec_hip_patch_track_indexed.argtypes = [_vp, _vp, C.c_int64] + [_vp] * 4 + [
+        C.c_int32, C.c_int, C.c_int64, C.c_int32, C.c_int32, _vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp,
+        C.c_int32, C.c_int32, C.c_double, C.c_uint32, C.c_double] + [_vp] * 6 + [C.c_int, C.c_int, _vp]
+    L.pnec_hip_patch_store_slot_bytes.argtypes = [C.c_int32]
+    L.pnec_hip_patch_store_slot_bytes.restype = C.c_int64
+    L.pnec_hip_patch_store_add.argtypes = [_vp, _vp, C.c_int32, C.c_int, C.c_int64, C.c_int32, C.c_int32, _vp, _vp, C.c_int64,
+                                           _vp, _vp, C.c_int64, _vp, C.c_int32, _vp, C.c_int64, C.c_int, C.c_int, _vp]
+    L.pnec_hip_patch_track_stored.argtypes = [_vp, C.c_int64] + [_vp] * 4 + [
         C.c_int32, C.c_int, C.c_int64, C.c_int32, C.c_int32, _vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp,
         C.c_int32, C.c_int32, C.c_double, C.c_uint32, C.c_double] + [_vp] * 6 + [C.c_int, C.c_int, _vp]
     L.pnec_hip_describe_launch.argtypes = [_vp, C.POINTER(Options)] + [C.POINTER(C.c_int32)] * 5

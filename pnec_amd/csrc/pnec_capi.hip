@@ -19,6 +19,7 @@
 #include "pnec_internal.hpp"
 #include "pnec_keyframe.hpp"
 #include "pnec_patch_cov.hpp"
+#include "pnec_patch_store.hpp"
 #include "pnec_patch_track.hpp"
 #include "pnec_pose_cov.hpp"
 #include "pnec_residuals.hpp"
@@ -1414,8 +1415,11 @@ int pnec_hip_image_pyramid_level(const void *in, void *out, int pixel_type, int6
   return io.finish();
 }
 
-// pnec_hip_patch_track (tmpl_image NULL, n_tmpl_images = n_images) and pnec_hip_patch_track_indexed: one body
-static int run_patch_track(const char *name, const void *const *tmpl, const int64_t *tmpl_pitch, const void *const *prev,
+// pnec_hip_patch_track (tmpl_image NULL, n_tmpl_images = n_images), pnec_hip_patch_track_indexed and
+// pnec_hip_patch_track_stored (store given: tmpl is absent, tmpl_image is the slot column): one body
+static int check_set_offsets(const std::string &pre, const char *array, const int64_t *offsets, int64_t n, int64_t rows,
+                             const char *rows_name);
+static int run_patch_track(const char *name, bool stored, const double *store, int64_t n_slots, const void *const *tmpl, const int64_t *tmpl_pitch, const void *const *prev,
                            const int64_t *prev_pitch, const void *const *next, const int64_t *next_pitch,
                            int32_t n_levels, int pixel_type, int64_t n_images, int64_t n_tmpl_images, int32_t height,
                            int32_t width, const int64_t *offsets, int64_t n_points, const double *tmpl_pts,
@@ -1426,6 +1430,20 @@ static int run_patch_track(const char *name, const void *const *tmpl, const int6
                            int32_t *out_lost_level, int space, int device, void *stream_) {
   const std::string pre = std::string(name) + ": ";
   const bool prev_given = prev != nullptr;
+  if (stored) {
+    if (!store || !tmpl_image || !prev || !prev_pitch)
+      return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "store, slot, prev or its pitch array is NULL");
+    if (n_slots < 1 || n_slots > 0x7fffffffLL)
+      return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "n_slots must be 1 .. 2^31 - 1");
+    for (void *o : {(void *)out_pts, (void *)out_angle, (void *)out_cov, (void *)out_dist2, (void *)out_status,
+                    (void *)out_lost_level})
+      if (o && (o == (const void *)store || o == (const void *)tmpl_image))
+        return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "an output is an input (the store or the slot column)");
+    // (no template pyramid: the checks below see the previous frame in its place)
+    tmpl = prev;
+    tmpl_pitch = prev_pitch;
+    n_tmpl_images = n_images;
+  }
   if (!prev) {
     prev = tmpl;
     prev_pitch = tmpl_pitch;
@@ -1450,7 +1468,7 @@ static int run_patch_track(const char *name, const void *const *tmpl, const int6
   if (n_tmpl_images < 1) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "n_tmpl_images must be >= 1");
   if (!tmpl_image && n_tmpl_images != n_images)
     return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "without tmpl_image, n_tmpl_images must equal n_images");
-  if (tmpl_image && !prev_given)
+  if (tmpl_image && !stored && !prev_given)
     return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "with tmpl_image, prev must be given (tmpl is a stack of other images)");
   if (height < 1 || width < 1 || (height >> (n_levels - 1)) < 4 || (width >> (n_levels - 1)) < 4)
     return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "the smallest level is below 4 pixels in height or width");
@@ -1469,9 +1487,16 @@ static int run_patch_track(const char *name, const void *const *tmpl, const int6
   for (int l = 0; l < n_levels; ++l)
     for (const int64_t pitch : {tmpl_pitch[l], prev_pitch[l], next_pitch[l]})
       if (int rc = check_images_fit(name, std::max(n_images, n_tmpl_images), height >> l, pitch, elem)) return rc;
-  if (space == PNEC_HIP_MEM_HOST)
+  if (space == PNEC_HIP_MEM_HOST && stored) {
+    // (a track set: rows at and beyond offsets[n_images] are padding, whose slot is -1)
+    if (int rc = check_set_offsets(pre, "offsets", offsets, n_images, n_points, "n_points")) return rc;
+    for (int64_t k = 0; k < offsets[n_images]; ++k)
+      if (tmpl_image[k] < 0 || tmpl_image[k] >= n_slots)
+        return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "a slot entry below offsets[n_images] lies outside 0 .. n_slots - 1");
+  }
+  if (space == PNEC_HIP_MEM_HOST && !stored)
     if (int rc = check_offsets(name, "offsets", offsets, n_images, n_points, "n_points")) return rc;
-  if (space == PNEC_HIP_MEM_HOST && tmpl_image)
+  if (space == PNEC_HIP_MEM_HOST && tmpl_image && !stored)
     for (int64_t k = 0; k < n_points; ++k)
       if (tmpl_image[k] < 0 || tmpl_image[k] >= n_tmpl_images)
         return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "a tmpl_image entry lies outside 0 .. n_tmpl_images - 1");
@@ -1503,7 +1528,7 @@ static int run_patch_track(const char *name, const void *const *tmpl, const int6
   // a level that two pyramids share (prev = tmpl) is staged once
   auto shared = [&](int l) { return !tmpl_image && prev[l] == tmpl[l] && prev_pitch[l] == tmpl_pitch[l]; };
   for (int l = 0; l < n_levels; ++l) {
-    io.in_bytes(a.tmpl.level[l], tmpl[l], level_bytes(l, tmpl_pitch[l], n_tmpl_images));
+    if (!stored) io.in_bytes(a.tmpl.level[l], tmpl[l], level_bytes(l, tmpl_pitch[l], n_tmpl_images));
     io.in_bytes(a.next.level[l], next[l], level_bytes(l, next_pitch[l]));
     if (!shared(l)) io.in_bytes(a.prev.level[l], prev[l], level_bytes(l, prev_pitch[l]));
   }
@@ -1513,6 +1538,8 @@ static int run_patch_track(const char *name, const void *const *tmpl, const int6
   io.in(a.init_angle, init_angle, M);
   const int32_t *d_tmpl_image = nullptr;
   io.in(d_tmpl_image, tmpl_image, M);
+  const double *d_store = nullptr;
+  if (stored) io.in(d_store, store, n_slots * store_slot_doubles(n_levels));
   io.in(a.pattern, pattern, 2 * (int64_t)n_pattern);
   io.out(a.out_pts, out_pts, 2 * M);
   io.out(a.out_angle, out_angle, M);
@@ -1523,7 +1550,8 @@ static int run_patch_track(const char *name, const void *const *tmpl, const int6
   if (int rc = io.commit()) return rc;
   for (int l = 0; l < n_levels; ++l)
     if (shared(l)) a.prev.level[l] = a.tmpl.level[l];
-  if (tmpl_image) PNEC_HIP_TRY(launch_patch_track_indexed(pixel_type, a, d_tmpl_image, n_tmpl_images, stream));
+  if (stored) PNEC_HIP_TRY(launch_patch_track_stored(pixel_type, a, d_store, n_slots, d_tmpl_image, stream));
+  else if (tmpl_image) PNEC_HIP_TRY(launch_patch_track_indexed(pixel_type, a, d_tmpl_image, n_tmpl_images, stream));
   else PNEC_HIP_TRY(launch_patch_track(pixel_type, a, stream));
   return io.finish();
 }
@@ -1536,7 +1564,7 @@ int pnec_hip_patch_track(const void *const *tmpl, const int64_t *tmpl_pitch, con
                          int32_t n_pattern, int32_t max_iterations, double max_recovered_dist2, uint32_t flags,
                          double scaling, double *out_pts, double *out_angle, double *out_cov, double *out_dist2,
                          int32_t *out_status, int32_t *out_lost_level, int space, int device, void *stream_) {
-  return run_patch_track("patch_track", tmpl, tmpl_pitch, prev, prev_pitch, next, next_pitch, n_levels, pixel_type,
+  return run_patch_track("patch_track", false, nullptr, 0, tmpl, tmpl_pitch, prev, prev_pitch, next, next_pitch, n_levels, pixel_type,
                          n_images, n_images, height, width, offsets, n_points, tmpl_pts, nullptr, init_pts, init_angle,
                          shift_x, shift_y, pattern, n_pattern, max_iterations, max_recovered_dist2, flags, scaling,
                          out_pts, out_angle, out_cov, out_dist2, out_status, out_lost_level, space, device, stream_);
@@ -1552,11 +1580,124 @@ int pnec_hip_patch_track_indexed(const void *const *tmpl, const int64_t *tmpl_pi
                                  double scaling, double *out_pts, double *out_angle, double *out_cov,
                                  double *out_dist2, int32_t *out_status, int32_t *out_lost_level, int space, int device,
                                  void *stream_) {
-  return run_patch_track("patch_track_indexed", tmpl, tmpl_pitch, prev, prev_pitch, next, next_pitch, n_levels,
+  return run_patch_track("patch_track_indexed", false, nullptr, 0, tmpl, tmpl_pitch, prev, prev_pitch, next, next_pitch, n_levels,
                          pixel_type, n_images, n_tmpl_images, height, width, offsets, n_points, tmpl_pts, tmpl_image,
                          init_pts, init_angle, shift_x, shift_y, pattern, n_pattern, max_iterations, max_recovered_dist2,
                          flags, scaling, out_pts, out_angle, out_cov, out_dist2, out_status, out_lost_level, space,
                          device, stream_);
+}
+
+int pnec_hip_patch_track_stored(const double *store, int64_t n_slots, const void *const *prev, const int64_t *prev_pitch,
+                                const void *const *next, const int64_t *next_pitch, int32_t n_levels, int pixel_type,
+                                int64_t n_images, int32_t height, int32_t width, const int64_t *offsets, int64_t n_points,
+                                const double *tmpl_pts, const int32_t *slot, const double *init_pts,
+                                const double *init_angle, double shift_x, double shift_y, const double *pattern,
+                                int32_t n_pattern, int32_t max_iterations, double max_recovered_dist2, uint32_t flags,
+                                double scaling, double *out_pts, double *out_angle, double *out_cov, double *out_dist2,
+                                int32_t *out_status, int32_t *out_lost_level, int space, int device, void *stream_) {
+  return run_patch_track("patch_track_stored", true, store, n_slots, nullptr, nullptr, prev, prev_pitch, next, next_pitch,
+                         n_levels, pixel_type, n_images, 0, height, width, offsets, n_points, tmpl_pts, slot, init_pts,
+                         init_angle, shift_x, shift_y, pattern, n_pattern, max_iterations, max_recovered_dist2, flags,
+                         scaling, out_pts, out_angle, out_cov, out_dist2, out_status, out_lost_level, space, device,
+                         stream_);
+}
+
+// stored patches: pnec_patch_store.hip.  Staged like the tracker.
+int64_t pnec_hip_patch_store_slot_bytes(int32_t n_levels) {
+  if (n_levels < 1 || n_levels > PNEC_HIP_TRACK_MAX_LEVELS) return 0;
+  return 8 * store_slot_doubles(n_levels);
+}
+
+int pnec_hip_patch_store_add(const void *const *cur, const int64_t *cur_pitch, int32_t n_levels, int pixel_type,
+                             int64_t n_images, int32_t height, int32_t width, const int64_t *carried_offsets,
+                             const int64_t *offsets, int64_t n_rows, const double *tmpl_pts, int32_t *slot,
+                             int64_t per_image_capacity, const double *pattern, int32_t n_pattern, double *store,
+                             int64_t n_slots, int space, int device, void *stream_) {
+  const std::string pre = "patch_store_add: ";
+  if (!cur || !cur_pitch || !offsets || !pattern || !store || (n_rows > 0 && (!tmpl_pts || !slot)))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "cur, its pitch array, offsets, tmpl_pts, slot, pattern or store is NULL");
+  if (n_levels < 1 || n_levels > PNEC_HIP_TRACK_MAX_LEVELS)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "n_levels must be 1 .. 8");
+  if (n_pattern < 1 || n_pattern > PNEC_HIP_PATCH_MAX_POINTS)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "n_pattern must be 1 .. 64");
+  const size_t elem = pixel_bytes(pixel_type);
+  if (!elem) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "unknown pixel_type");
+  if (n_images < 1 || n_rows < 0) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "n_images must be >= 1, n_rows >= 0");
+  if (height < 1 || width < 1 || (height >> (n_levels - 1)) < 4 || (width >> (n_levels - 1)) < 4)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "the smallest level is below 4 pixels in height or width");
+  for (int l = 0; l < n_levels; ++l) {
+    if (!cur[l]) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "a level pointer is NULL");
+    if (cur_pitch[l] < (width >> l))
+      return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "a pitch (in elements) is below its level's width");
+  }
+  if (per_image_capacity < 1) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "per_image_capacity must be >= 1");
+  if (per_image_capacity > kStoreMaxCapacity)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT,
+                pre + "per_image_capacity is above 65536 (PNEC_HIP_PATCH_STORE_MAX_CAPACITY: the assignment's occupancy map)");
+  if ((__int128)n_images * per_image_capacity > 0x7fffffffLL)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "n_images * per_image_capacity does not fit int32 (a slot is an int32)");
+  if (n_slots < n_images * per_image_capacity)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "n_slots is below n_images * per_image_capacity");
+  if (n_slots > 0x7fffffffLL) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "n_slots must fit int32");
+  if (n_rows > (int64_t)1 << 40) return fail(PNEC_HIP_ERR_UNSUPPORTED, pre + "too many rows");
+  const void *ins[] = {carried_offsets, offsets, tmpl_pts, pattern};
+  for (const void *i : ins)
+    if (i && (i == (const void *)slot || i == (const void *)store))
+      return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "an output is an input (slot and store are written)");
+  if (slot && (const void *)slot == (const void *)store)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "an output is an input (slot and store are two arrays)");
+  if (int rc = check_space(pre, space)) return rc;
+  for (int l = 0; l < n_levels; ++l)
+    if (int rc = check_images_fit("patch_store_add", n_images, height >> l, cur_pitch[l], elem)) return rc;
+  if (space == PNEC_HIP_MEM_HOST) {
+    if (int rc = check_set_offsets(pre, "offsets", offsets, n_images, n_rows, "n_rows")) return rc;
+    if (carried_offsets) {
+      bool ok = carried_offsets[0] == 0;
+      for (int64_t f = 0; ok && f < n_images; ++f) ok = carried_offsets[f] <= carried_offsets[f + 1];
+      if (!ok) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "carried_offsets must be non-decreasing from 0");
+    }
+    for (int64_t f = 0; f < n_images; ++f) {
+      int64_t lo, c, take;
+      store_counts(carried_offsets, offsets, n_rows, f, lo, c, take);
+      for (int64_t r = 0; r < take; ++r)
+        if (store_local_slot(slot[lo + r], f, per_image_capacity) < 0)
+          return fail(PNEC_HIP_ERR_INVALID_ARGUMENT,
+                      pre + "a carried row's slot lies outside its image's f * C .. f * C + C - 1");
+    }
+  }
+  if (n_rows == 0) return 0;
+  hipStream_t stream = (hipStream_t)stream_;
+  CallArrays io(device, space, stream);
+  PatchStoreAssignArgs s{};
+  s.n_images = n_images;
+  s.n_rows = n_rows;
+  s.capacity = per_image_capacity;
+  PatchStoreBuildArgs a{};
+  a.n_levels = n_levels;
+  a.w = width;
+  a.h = height;
+  a.n_images = n_images;
+  a.n_rows = n_rows;
+  a.n_pattern = n_pattern;
+  a.n_slots = n_slots;
+  for (int l = 0; l < n_levels; ++l) {
+    a.cur.pitch[l] = cur_pitch[l];
+    io.in_bytes(a.cur.level[l], cur[l], image_block_bytes(elem, n_images, height >> l, cur_pitch[l], width >> l));
+  }
+  io.in(s.carried_offsets, carried_offsets, n_images + 1);
+  io.in(s.offsets, offsets, n_images + 1);
+  io.in(a.tmpl_pts, tmpl_pts, 2 * n_rows);
+  io.in(a.pattern, pattern, 2 * (int64_t)n_pattern);
+  io.out(s.slot, slot, n_rows, kPreload);
+  // (the whole store travels up first: the slots the call leaves alone come back as the caller had them)
+  io.out(a.store, store, n_slots * store_slot_doubles(n_levels), kPreload);
+  if (int rc = io.commit()) return rc;
+  a.carried_offsets = s.carried_offsets;
+  a.offsets = s.offsets;
+  a.slot = s.slot;
+  PNEC_HIP_TRY(launch_patch_store_assign(s, stream));
+  PNEC_HIP_TRY(launch_patch_store_build(pixel_type, a, stream));
+  return io.finish();
 }
 
 // the bookkeeping of tracks across frames: pnec_tracks.hip.  No batch and no images: staged like the patch covariances.

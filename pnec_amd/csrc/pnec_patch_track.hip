@@ -22,16 +22,7 @@
 
 namespace pnec_hip {
 
-constexpr int kTrackBlock = 256;
 constexpr int kPyrBlock = 256;
-
-__device__ __forceinline__ int track_row_sum_i(int x) {
-  x += __builtin_amdgcn_mov_dpp(x, 0xB1, 0xF, 0xF, true);    // quad_perm [1,0,3,2]
-  x += __builtin_amdgcn_mov_dpp(x, 0x4E, 0xF, 0xF, true);    // quad_perm [2,3,0,1]
-  x += __builtin_amdgcn_mov_dpp(x, 0x141, 0xF, 0xF, true);   // row_half_mirror
-  x += __builtin_amdgcn_mov_dpp(x, 0x140, 0xF, 0xF, true);   // row_mirror
-  return x;
-}
 
 template <typename T>
 __global__ __launch_bounds__(kPyrBlock) void image_pyramid_level_kernel(const PyramidLevelArgs a) {

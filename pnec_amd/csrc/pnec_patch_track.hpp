@@ -162,6 +162,18 @@ PNEC_PATCH_HD T pyr_pixel(const T *img, int64_t pitch, int32_t w, int32_t h, int
 }
 
 #if defined(__HIPCC__)
+// (shared with pnec_patch_store.hip, which compiles the tracker's body a third time)
+constexpr int kTrackBlock = 256;
+
+// the integer sum over the 16 lanes of a DPP row, in every lane
+__device__ __forceinline__ int track_row_sum_i(int x) {
+  x += __builtin_amdgcn_mov_dpp(x, 0xB1, 0xF, 0xF, true);    // quad_perm [1,0,3,2]
+  x += __builtin_amdgcn_mov_dpp(x, 0x4E, 0xF, 0xF, true);    // quad_perm [2,3,0,1]
+  x += __builtin_amdgcn_mov_dpp(x, 0x141, 0xF, 0xF, true);   // row_half_mirror
+  x += __builtin_amdgcn_mov_dpp(x, 0x140, 0xF, 0xF, true);   // row_mirror
+  return x;
+}
+
 struct PyramidLevelArgs {
   const void *in;
   void *out;

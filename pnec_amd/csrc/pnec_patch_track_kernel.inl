@@ -3,6 +3,9 @@
 // image, for pnec_hip_patch_track, and the clamped tmpl_image[k] for pnec_hip_patch_track_indexed.  Text, not a function
 // template: the plain kernel must keep the machine code it had before the indexed one existed, and handing the kernel's
 // argument block to a function by reference changed it (tools/isa_diff_kernels.py).
+// A third variant, with PNEC_TRACK_STORED defined (pnec_patch_store.hip), builds no template: it loads what
+// pnec_hip_patch_store_add kept of it from slot[k] of `store` (n_slots slots; pnec_patch_store.hpp has the layout), and a
+// keypoint without a slot gets a template that is bad at every level.  The text of the other two is what it was.
   PNEC_PATCH_NO_CONTRACT
   const int64_t g = ((int64_t)blockIdx.x * kTrackBlock + threadIdx.x) / kPatchLanes;
   const int j = threadIdx.x & (kPatchLanes - 1);
@@ -41,6 +44,11 @@
   double S0 = 0.0, H0[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   const int half = a.n_pattern / 2;
   const int n_dirs = a.backward ? 2 : 1;
+#if defined(PNEC_TRACK_STORED)
+  const int64_t slot_k = (int64_t)slot[k];
+  const bool has_slot = slot_k >= 0 && slot_k < n_slots;
+  const double *const slot_words = store + (has_slot ? slot_k : 0) * store_slot_doubles(a.n_levels);
+#endif
 
 #pragma unroll 1
   for (int dir = 0; dir < n_dirs; ++dir) {
@@ -53,6 +61,48 @@
     for (int l = a.n_levels - 1; l >= 0; --l) {
       const int32_t wl = a.w >> l, hl = a.h >> l;
       const double scale = (double)(1 << l);
+#if defined(PNEC_TRACK_STORED)
+      // ---- the template of this level, as pnec_hip_patch_store_add left it: lane j's slot s is element j + 16 s
+      double data[kPatchSlots], K[kPatchSlots][3];
+      bool tvalid[kPatchSlots];
+      {
+        int tstat = PNEC_HIP_PATCH_EMPTY;
+        uint64_t valid = 0ull;
+        const double *const plane = slot_words + kStoreHeader + l * kStoreLevel;
+#pragma unroll
+        for (int s = 0; s < kPatchSlots; ++s) {
+          data[s] = 0.0;
+          K[s][0] = 0.0;
+          K[s][1] = 0.0;
+          K[s][2] = 0.0;
+        }
+        if (has_slot) {
+          tstat = (int)reinterpret_cast<const int64_t *>(slot_words)[kStoreWordStatus + l];
+          valid = reinterpret_cast<const uint64_t *>(slot_words)[kStoreWordValid + l];
+#pragma unroll
+          for (int s = 0; s < kPatchSlots; ++s) {
+            const int i = j + kPatchLanes * s;
+            data[s] = plane[i];
+            K[s][0] = plane[kStorePlane + i];
+            K[s][1] = plane[2 * kStorePlane + i];
+            K[s][2] = plane[3 * kStorePlane + i];
+          }
+          if (l == 0) {
+            n0 = (int)reinterpret_cast<const int64_t *>(slot_words)[kStoreWordN];
+            S0 = slot_words[kStoreWordS];
+#pragma unroll
+            for (int c = 0; c < 6; ++c) H0[c] = slot_words[kStoreWordH + c];
+          }
+        }
+#pragma unroll
+        for (int s = 0; s < kPatchSlots; ++s) tvalid[s] = ((valid >> (j + kPatchLanes * s)) & 1ull) != 0ull;
+        if (alive && tstat != PNEC_HIP_PATCH_OK) {
+          alive = false;
+          status = PNEC_HIP_TRACK_BAD_TEMPLATE;
+          lost_level = l;
+        }
+      }
+#else
       // ---- the template of this level: pnec_patch_cov.hip's two phases, term by term
       const T *timg = reinterpret_cast<const T *>(a.tmpl.level[l]) + PNEC_TRACK_TMPL_IMAGE * (int64_t)hl * a.tmpl.pitch[l];
       const int64_t tpitch = a.tmpl.pitch[l];
@@ -109,6 +159,7 @@
           lost_level = l;
         }
       }
+#endif
       // ---- the iterations of this level
       const T *img = reinterpret_cast<const T *>(pyr.level[l]) + f * (int64_t)hl * pyr.pitch[l];
       const int64_t pitch = pyr.pitch[l];

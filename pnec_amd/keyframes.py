@@ -9,7 +9,8 @@ pixels against the key frame is skipped: it gives no pair, and the next frame is
 DEVIATION from the reference, which keeps a track's patch for ever and so matches against a key frame of any age:
 ``Tracker`` retires a track at age ring - 2, so a pair spanning more frames has no match.  `max_span` (default and at
 most ring - 2) forces acceptance when the pair would span that many frames; a pair that spans s frames also lacks the
-tracks born before the key frame that aged out on the way.
+tracks born before the key frame that aged out on the way.  ``KeyframeTracker(..., templates="patches")`` (stored
+patches) lifts it: a track lives as long as it is tracked, any max_span >= 1 is taken, and None forces no acceptance.
 """
 from __future__ import annotations
 
@@ -130,16 +131,23 @@ class KeyframeTracker:
     of process reads anything back or waits.  The pairs are this object's own buffer: the next call overwrites it.
 
     It needs ring >= 4 (default 4), and max_span must lie in 1 .. ring - 2 (default ring - 2): a track is retired at age
-    ring - 2, so a pair spanning more frames has no match -- see the module's DEVIATION."""
+    ring - 2, so a pair spanning more frames has no match -- see the module's DEVIATION.  With templates="patches" among
+    the tracker's keywords there is no such limit: ring >= 2, any max_span >= 1, and max_span None means that no
+    acceptance is forced (the call gets 2**31 - 1)."""
 
     def __init__(self, n_sequences: int, height: int, width: int, min_displacement: float = 5.0, max_span: int = None,
                  **tracker_kwargs):
         ring = int(tracker_kwargs.get("ring", 4))
-        if ring < 4:
-            raise ValueError("KeyframeTracker needs ring >= 4 (a pair must be able to span two frames)")
-        max_span = ring - 2 if max_span is None else int(max_span)
-        if not 1 <= max_span <= ring - 2:
-            raise ValueError("max_span must lie in 1 .. ring - 2 (a track is retired at age ring - 2)")
+        if tracker_kwargs.get("templates", "ring") == "patches":
+            max_span = 2 ** 31 - 1 if max_span is None else int(max_span)
+            if not 1 <= max_span <= 2 ** 31 - 1:
+                raise ValueError("max_span must be >= 1 (and fit int32)")
+        else:
+            if ring < 4:
+                raise ValueError("KeyframeTracker needs ring >= 4 (a pair must be able to span two frames)")
+            max_span = ring - 2 if max_span is None else int(max_span)
+            if not 1 <= max_span <= ring - 2:
+                raise ValueError("max_span must lie in 1 .. ring - 2 (a track is retired at age ring - 2)")
         min_displacement = float(min_displacement)
         if not (min_displacement >= 0.0 and np.isfinite(min_displacement)):
             raise ValueError("min_displacement must be finite and >= 0")

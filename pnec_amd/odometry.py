@@ -59,7 +59,8 @@ class Odometry:
     tracker_kwargs go to Tracker (levels, ring, grid, capacity, ...).  Asynchronous on torch's current stream.
 
     min_displacement > 0 turns keyframes on (KeyframeTracker: ring >= 4, max_span in 1 .. ring - 2, default ring - 2); with
-    the default 0 every consecutive pair is solved, as before, and nothing of the keyframe machinery is created."""
+    the default 0 every consecutive pair is solved, as before, and nothing of the keyframe machinery is created.
+    templates="patches" among the tracker_kwargs runs both on stored patches (no age limit, ring >= 2, any max_span)."""
 
     def __init__(self, n_sequences: int, height: int, width: int, K_inv, mode: int = capi.MODE_TARGET,
                  pipeline_options: capi.PipelineOptions | None = None, min_displacement: float = 0.0, max_span: int = None,

@@ -6,6 +6,8 @@ no host wait in the loop.  include/pnec_hip.h has the definitions.
 DEVIATION from the reference, which keeps a track's patch for ever: ``Tracker`` keeps a ring of R pyramids, a track's
 template is the frame it was born in, and a track is retired when its age would reach R - 1 (the step before its birth
 frame's slot is overwritten).  The pair loses that track's correspondence on the step it is retired.
+``Tracker(..., templates="patches")`` (stored patches, pnec_amd/patch_store.py) lifts it: a track keeps its templates for
+as long as it is tracked.
 """
 from __future__ import annotations
 
@@ -177,16 +179,28 @@ class Tracker:
     them.
 
     DEVIATION: the reference keeps a patch for ever; a track here is retired when its age would reach R - 1 (its birth
-    frame's slot is about to be overwritten), which costs the pair that track's correspondence on that step."""
+    frame's slot is about to be overwritten), which costs the pair that track's correspondence on that step.
+    `templates="patches"` lifts it: the constructor allocates a PatchStore of F * capacity slots (``store``), `ring` may be
+    2 (only the previous and this frame's pyramids are read), and every later call makes seven device calls: pyramid ->
+    patch_track_stored (the templates from the store) -> tracks_retain (max_age = 0: no age limit) -> detect_keypoints ->
+    patch_covariance -> tracks_append -> patch_store_add (a free slot and the templates for every new track).  Still
+    nothing is read back or allocated in process.  The sets' `tmpl_image` column is then the track's slot.
+    `templates="ring"`, the default, is the object described above in every respect."""
 
     def __init__(self, n_sequences: int, height: int, width: int, levels: int = 5, ring: int = 4, grid: int = 30,
                  capacity: int = None, points_per_cell: int = 1, min_threshold: int = 5, edge: int = 19,
                  max_iterations: int = 40, max_recovered_dist2: float = 0.04, scaling: float = 10.0, pattern=PATTERN52,
-                 dtype=None, device=None):
+                 dtype=None, device=None, templates: str = "ring"):
         import torch
         F, h, w, L, R = int(n_sequences), int(height), int(width), int(levels), int(ring)
-        if F < 1 or R < 3:
+        if templates not in ("ring", "patches"):
+            raise ValueError('templates must be "ring" or "patches"')
+        if templates == "patches":
+            if F < 1 or R < 2:
+                raise ValueError("n_sequences must be >= 1 and ring >= 2")
+        elif F < 1 or R < 3:
             raise ValueError("n_sequences must be >= 1 and ring >= 3")
+        self.templates = templates
         if not 1 <= L <= 8 or (h >> (L - 1)) < 4 or (w >> (L - 1)) < 4:
             raise ValueError("levels must be 1 .. 8 and the smallest level at least 4 pixels in each direction")
         G, K = int(grid), int(points_per_cell)
@@ -219,6 +233,10 @@ class Tracker:
                               torch.zeros((cap,), **i32), torch.zeros((F, n_cells), **i32))
         self._det_cov = torch.empty((cap, 3), **f64)
         self._pattern = torch.as_tensor(np.array(pattern), **f64).contiguous()
+        self.store = None
+        if templates == "patches":
+            from .patch_store import new_patch_store
+            self.store = new_patch_store(F, self.capacity, L, dev)
         self.next_id = torch.zeros((F,), dtype=torch.int64, device=dev)
         self.dropped = torch.zeros((F,), dtype=torch.int64, device=dev)
         self.frame = 0          # the number of frames processed
@@ -257,16 +275,23 @@ class Tracker:
         retained = None
         if n > 0:
             A, T, B = self._sets[self._cur], self.last_track, self._retained
-            tp, tq = self._tables(self._stack)
             pp, pq = self._tables(self._slot(n - 1))
             np_, nq = self._tables(cur)
-            capi.check(lib.pnec_hip_patch_track_indexed(
-                tp, tq, self.ring * F, pp, pq, np_, nq, L, ptype, F, h, w, p(A.offsets), N, p(A.tmpl_pts), p(A.tmpl_image),
-                p(A.pts), p(A.angle), 0.0, 0.0, p(pat), int(pat.shape[0]), self.max_iterations, self.max_recovered_dist2, 0,
-                self.scaling, p(T.pts), p(T.angle), p(T.cov), p(T.dist2), p(T.status), p(T.lost_level), capi.MEM_DEVICE,
-                device, stream))
+            if self.store is not None:
+                capi.check(lib.pnec_hip_patch_track_stored(
+                    p(self.store.data), self.store.n_slots, pp, pq, np_, nq, L, ptype, F, h, w, p(A.offsets), N, p(A.tmpl_pts),
+                    p(A.tmpl_image), p(A.pts), p(A.angle), 0.0, 0.0, p(pat), int(pat.shape[0]), self.max_iterations,
+                    self.max_recovered_dist2, 0, self.scaling, p(T.pts), p(T.angle), p(T.cov), p(T.dist2), p(T.status),
+                    p(T.lost_level), capi.MEM_DEVICE, device, stream))
+            else:
+                tp, tq = self._tables(self._stack)
+                capi.check(lib.pnec_hip_patch_track_indexed(
+                    tp, tq, self.ring * F, pp, pq, np_, nq, L, ptype, F, h, w, p(A.offsets), N, p(A.tmpl_pts), p(A.tmpl_image),
+                    p(A.pts), p(A.angle), 0.0, 0.0, p(pat), int(pat.shape[0]), self.max_iterations, self.max_recovered_dist2, 0,
+                    self.scaling, p(T.pts), p(T.angle), p(T.cov), p(T.dist2), p(T.status), p(T.lost_level), capi.MEM_DEVICE,
+                    device, stream))
             T.offsets = A.offsets
-            retained = retain_tracks(A, T, max_age=self.ring - 2, out=B)
+            retained = retain_tracks(A, T, max_age=0 if self.store is not None else self.ring - 2, out=B)
         det = detect_keypoints(cur[0], self.grid, self.points_per_cell, self.min_threshold, self.edge,
                                current=None if retained is None else (retained.offsets, retained.pts), capacity=True,
                                out=self._det)
@@ -277,6 +302,12 @@ class Tracker:
         nxt = self._sets[1 - self._cur]
         append_tracks(retained, det, self._det_cov, (n % self.ring) * F, self.capacity, self.next_id, rows=N, out=nxt,
                       dropped=self.dropped)
+        if self.store is not None:
+            cp, cq = self._tables(cur)
+            capi.check(lib.pnec_hip_patch_store_add(
+                cp, cq, L, ptype, F, h, w, None if retained is None else p(retained.offsets), p(nxt.offsets), N,
+                p(nxt.tmpl_pts), p(nxt.tmpl_image), self.capacity, p(pat), int(pat.shape[0]), p(self.store.data),
+                self.store.n_slots, capi.MEM_DEVICE, device, stream))
         self._cur = 1 - self._cur
         self.tracks = nxt
         self.frame = n + 1
