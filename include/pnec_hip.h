@@ -26,6 +26,8 @@
  *    would return for the problems of pnec_ceres.cc / nec_ceres.cc)
  *   (no counterpart: the structure a pose implies and the sign of t,   pnec_hip_triangulate
  *    which TranslationalDifference(..., both_directions = true) hides)
+ *   EMPoseEstimation(bvs1, bvs2, initial_pose, EIGHTPT, false) +     pnec_hip_eight_point
+ *    PoseFromEssentialMatrix  essential_matrix_methods.cc:45-126, common.cc:262-457
  *   (no counterpart: the length of one pair's baseline in units of    pnec_hip_relative_scale
  *    the previous pair's, from the tracks both see)
  *   POpticalFlowPatch::setFromImage (Cov) + KLTPatchOpticalFlow's     pnec_hip_patch_covariance
@@ -469,6 +471,61 @@ int pnec_hip_triangulate(pnec_hip_problem *p, const double *q, const double *t, 
                          double *out_point, double *out_depth1, double *out_depth2, double *out_parallax,
                          double *out_depth1_var, uint8_t *out_front, int32_t *out_n_front, int32_t *out_n_back,
                          int32_t *out_sign, double *out_t_oriented, double *out_parallax_mean, int space, void *stream);
+
+/* The eight-point baseline: essential matrix and pose of every pair from its correspondences alone, no start pose
+ * (added within ABI 8: a pure addition, PNEC_HIP_ABI_VERSION is unchanged).  It is the closed-form estimator behind the
+ * reference's `run_simulation -e`: EMPoseEstimation(..., EIGHTPT, ransac = false).  Conventions as everywhere here: R
+ * takes frame-2 vectors into frame 1, t is a direction in frame 1, the constraint is f1' E f2 = 0 with E = [t]x R.
+ *
+ * Steps 1-2 restate opengv::relative_pose::eightpt from memory ([EXT]: opengv is not in the reference tree); steps 3-5
+ * restate PoseFromEssentialMatrix, src/common/common.cc:262-457.  Per pair with N correspondences:
+ *  1 Normal matrix.  Row i of A holds the nine products f1_a f2_b in the row-major order of E; G = A'A is 9x9 symmetric
+ *    (45 distinct sums).  Bearings are used as stored: no Hartley normalisation (eightpt has none).
+ *  2 Null vector.  The eigenvector of G's smallest eigenvalue by cyclic Jacobi (rotations (0,1), (0,2), ... (7,8) per
+ *    sweep; stop when the Frobenius norm of the off-diagonal part is at or below 2^-58 trace, 16 sweeps at most).  e has
+ *    unit norm and the sign that makes its entry of largest magnitude positive (the lowest index wins a tie); E is e
+ *    row-major.  gap = (lambda_1 - lambda_0) / lambda_8 of G's ascending eigenvalues: small for a planar scene or a pure
+ *    rotation, where the null vector is not unique -- what a caller gates on.
+ *  3 Decomposition (common.cc:280-325).  E = U S V' through the Jacobi eigen-decomposition of E'E: its eigenvalues in
+ *    descending order are the squares of the singular values s0 >= s1 >= s2, its eigenvectors v0, v1, v2; v2 gets the
+ *    sign that makes its entry of largest magnitude positive (lowest index on a tie) and v1 the sign that makes
+ *    (v0, v1, v2) right-handed; u0 = E v0 / |E v0|, u1 = E v1 / |E v1|, u2 = u0 x u1 (so s2 ~ 0 costs nothing).  With
+ *    W = [[0,-1,0],[1,0,0],[0,0,1]]: Ra = U W V', Rb = U W' V', each negated if its determinant is negative; ta = u2.
+ *    The candidates are (Ra, ta), (Rb, ta), (Ra, -ta), (Rb, -ta), in that order.  The SET of candidates does not depend
+ *    on the sign of e, on the signs of the singular vectors or on the rotation of (v0, v1) within their plane when
+ *    s0 = s1 (only U and V enter; the singular values do not); the sign rules above fix their ORDER, so that out_choice
+ *    means the same on every implementation.  t comes back as a unit direction; the reference's `scale` is out_singular[0].
+ *  4 Choice (common.cc:342-406).  The first K = min(9, N) correspondences of the pair (the reference's sampleSize 8 + 1)
+ *    are triangulated at each candidate by the midpoint system of pnec_hip_triangulate (opengv's triangulate2); the point
+ *    is normalised in frame 1 (r1) and R'(point - t) in frame 2 (r2); quality = sum (1 - f1.r1) + (1 - f2.r2).  The
+ *    candidate of lowest quality wins by strict < from a start value of 1e6 (the lowest index wins a tie).  A non-finite
+ *    term (parallel rays: no midpoint) makes that candidate's quality +inf.  PNEC_HIP_EP_QUALITY_ALL sums over all N
+ *    instead: an extension, for batches whose first nine rows may be outliers.
+ *  5 Status, pnec_hip_ep_status.  TOO_FEW: N < 8.  NOT_FINITE: a NaN or an infinity in a bearing the pair holds (or
+ *    bearings so long that the sums overflow).  NO_CANDIDATE: no quality below 1e6.  A status other than OK writes NaN to
+ *    q, t and E and -1 to out_choice; TOO_FEW and NOT_FINITE write NaN to the other double outputs too.
+ *
+ * Outputs for P pairs; every pointer may be NULL (not wanted), not all of them.
+ *   out_q [P,4] xyzw   out_t [P,3] unit   out_E [P,9] row-major, sign and norm of step 2   out_singular [P,3]
+ *   out_gap [P]   out_quality [P,4]   out_choice, out_status int32 [P]
+ * A pair's bits depend on its own rows and on `flags` only (no atomics, fixed reduction order).
+ *
+ * All four problem modes (only the six bearing planes are read); batches made by pnec_hip_problem_select(_view) and
+ * reshaped capacity batches included.  DEVICE space: the pair sizes are read on the device, nothing waits, nothing is
+ * allocated, the call is asynchronous on `stream`.  HOST space: the outputs are staged on the device (24 doubles and two
+ * ints per pair) and the call blocks.
+ * NULL problem, all outputs NULL, a flag bit other than PNEC_HIP_EP_QUALITY_ALL or a bad `space`:
+ * PNEC_HIP_ERR_INVALID_ARGUMENT before the handle is read or any device is touched. */
+#define PNEC_HIP_EP_QUALITY_ALL 1
+typedef enum pnec_hip_ep_status {
+  PNEC_HIP_EP_OK = 0,
+  PNEC_HIP_EP_TOO_FEW = 1,
+  PNEC_HIP_EP_NOT_FINITE = 2,
+  PNEC_HIP_EP_NO_CANDIDATE = 3
+} pnec_hip_ep_status;
+int pnec_hip_eight_point(pnec_hip_problem *p, int32_t flags, double *out_q, double *out_t, double *out_E,
+                         double *out_singular, double *out_gap, double *out_quality, int32_t *out_choice,
+                         int32_t *out_status, int space, void *stream);
 
 /* Relative scale between consecutive pairs from linked tracks (added within ABI 8: a pure addition,
  * PNEC_HIP_ABI_VERSION is unchanged).  Every pose carries t as a direction, so each pair is reconstructed with a

@@ -13,7 +13,7 @@ Layout:
   distributed.py   one-process-per-GPU sharding of independent pair batches + one RCCL gather
 """
 from . import capi  # noqa: F401
-from .batch import (Batch, PoseCovariance, RelativeScale, ResidualReport, SolveResult, Triangulation, gate_sigma,  # noqa: F401
+from .batch import (Batch, EightPoint, PoseCovariance, RelativeScale, ResidualReport, SolveResult, Triangulation, gate_sigma,  # noqa: F401
                     select_best)
 from .keyframes import KeyframePairs, KeyframeState, KeyframeTracker, keyframe_pairs  # noqa: F401
 from .odometry import Odometry, OdometryResult  # noqa: F401
@@ -23,5 +23,5 @@ from .tracker import Tracker, TrackSet, append_tracks, retain_tracks  # noqa: F4
 from .patch_store import PatchStore, add_patches, new_patch_store, patch_track_stored  # noqa: F401
 from .tracks import chain_scales  # noqa: F401
 
-__all__ = ["capi", "Batch", "KeyframePairs", "KeyframeState", "KeyframeTracker", "Keypoints", "Odometry", "OdometryResult", "PATTERN52", "PatchCovariance", "PatchStore", "PatchTrack", "PoseCovariance", "RelativeScale", "ResidualReport", "SolveResult",
+__all__ = ["capi", "Batch", "EightPoint", "KeyframePairs", "KeyframeState", "KeyframeTracker", "Keypoints", "Odometry", "OdometryResult", "PATTERN52", "PatchCovariance", "PatchStore", "PatchTrack", "PoseCovariance", "RelativeScale", "ResidualReport", "SolveResult",
            "TrackSet", "Tracker", "Triangulation", "add_patches", "append_tracks", "chain_scales", "detect_keypoints", "gate_sigma", "image_pyramid", "keyframe_pairs", "new_patch_store", "patch_covariance", "patch_track", "patch_track_stored", "retain_tracks", "select_best"]

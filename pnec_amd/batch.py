@@ -188,6 +188,20 @@ class Triangulation:
 
 
 @dataclass
+class EightPoint:
+    """pnec_hip_eight_point's outputs (include/pnec_hip.h has the definitions): essential matrix and pose of every pair
+    from its correspondences alone.  Per pair [P]; where `status` is not capi.EP_OK, q, t and E are NaN and choice -1."""
+    q: object          # [P,4] xyzw; R takes frame-2 vectors into frame 1
+    t: object          # [P,3] unit direction in frame 1
+    E: object          # [P,9] row-major, unit norm, entry of largest magnitude positive; f1' E f2 = 0
+    singular: object   # [P,3] singular values of E, descending (the reference's scale is singular[:, 0])
+    gap: object        # [P] (lambda_1 - lambda_0) / lambda_8 of A'A: small for planar scenes and pure rotations
+    quality: object    # [P,4] of (Ra, ta), (Rb, ta), (Ra, -ta), (Rb, -ta); +inf where a term was not finite
+    choice: object     # [P] int32, the candidate taken
+    status: object     # [P] int32, capi.EP_OK / EP_TOO_FEW / EP_NOT_FINITE / EP_NO_CANDIDATE
+
+
+@dataclass
 class RelativeScale:
     """pnec_hip_relative_scale's outputs (include/pnec_hip.h has the definitions): the ratio of each pair's baseline to
     its previous pair's, from the tracks the two pairs share.  Per pair [P]: `scale` (the lower median of the used
@@ -355,7 +369,7 @@ class Batch:
             n_pairs = self.n_pairs - first_pair
         m = int(self.offsets[first_pair + n_pairs] - self.offsets[first_pair])
         arrays = [bvs1, bvs2, covs, covs_host]
-        on_device = _is_torch(bvs1)
+        on_device = self._on_device = _is_torch(bvs1)
         ptrs, keep = [], []
         for i, a in enumerate(arrays):
             if a is None:
@@ -403,7 +417,7 @@ class Batch:
         if n_pairs is None:
             n_pairs = self.n_pairs - first_pair
         m = int(self.offsets[first_pair + n_pairs] - self.offsets[first_pair])
-        on_device = _is_torch(pts1)
+        on_device = self._on_device = _is_torch(pts1)
         xp = __import__("torch") if on_device else np
 
         def c3(a):
@@ -469,7 +483,7 @@ class Batch:
         solve, solve_pipeline (without want_inliers), cost_function and pose_covariance take it without a wait; `offsets`,
         num_correspondences and the calls that size per-correspondence outputs (residuals, triangulate, relative_scale,
         want_inliers) wait once for the stream and fetch the sizes.  reshape() makes it an exact batch again."""
-        on_device = _is_torch(pts1)
+        on_device = self._on_device = _is_torch(pts1)
         xp = __import__("torch") if on_device else np
 
         def c3(a):
@@ -666,6 +680,7 @@ class Batch:
             capi.check(fn(self._h, m.ctypes.data, capi.MEM_HOST, None, C.byref(h)))
         out = Batch.__new__(Batch)
         out._borrowed = bool(view)
+        out._on_device = _is_torch(mask)
         out._lib, out.mode, out.device, out._h = self._lib, self.mode, self.device, h
         if view:
             # the view lives in this batch's cached target: keep the source alive as long as the view is, and retire
@@ -858,6 +873,37 @@ class Batch:
                                                   p(var), p(front), p(nf), p(nb), p(sign), p(to), p(mean), space, stream))
         return Triangulation(point, d1, d2, psi, var, front, nf, nb, sign, to, mean, offsets, n_hyp)
 
+    def eight_point(self, quality: str = "sample", on_device: bool | None = None) -> EightPoint:
+        """The eight-point baseline (pnec_hip_eight_point): essential matrix and pose of every pair from its
+        correspondences alone, no start pose.  quality="sample" scores the four decompositions on the pair's first
+        min(9, N) correspondences as the reference does, "all" on all of them (PNEC_HIP_EP_QUALITY_ALL).  A batch filled
+        or selected from torch.cuda tensors answers with torch.cuda tensors, asynchronous on torch's current stream; one
+        filled from numpy answers with numpy arrays (`on_device` overrides).  Nothing is read back to size the outputs,
+        also on a batch made by select()."""
+        if quality not in ("sample", "all"):
+            raise ValueError('quality must be "sample" or "all"')
+        flags = capi.EP_QUALITY_ALL if quality == "all" else 0
+        if on_device is None:
+            on_device = bool(getattr(self, "_on_device", False))
+        P = self.n_pairs
+        if on_device:
+            import torch
+            f64 = dict(dtype=torch.float64, device=f"cuda:{self.device}")
+            i32 = dict(dtype=torch.int32, device=f"cuda:{self.device}")
+            q, t, E, sing = (torch.empty((P, w), **f64) for w in (4, 3, 9, 3))
+            gap, qual = torch.empty((P,), **f64), torch.empty((P, 4), **f64)
+            choice, status = torch.empty((P,), **i32), torch.empty((P,), **i32)
+            p = lambda a: a.data_ptr()
+            space, stream = capi.MEM_DEVICE, torch.cuda.current_stream(self.device).cuda_stream
+        else:
+            q, t, E, sing = (np.empty((P, w)) for w in (4, 3, 9, 3))
+            gap, qual = np.empty(P), np.empty((P, 4))
+            choice, status = np.empty(P, dtype=np.int32), np.empty(P, dtype=np.int32)
+            p = lambda a: a.ctypes.data
+            space, stream = capi.MEM_HOST, None
+        capi.check(self._lib.pnec_hip_eight_point(self._h, flags, p(q), p(t), p(E), p(sing), p(gap), p(qual), p(choice),
+                                                  p(status), space, stream))
+        return EightPoint(q, t, E, sing, gap, qual, choice, status)
 
     def relative_scale(self, prev, prev_pair, link, q, t, q_prev, t_prev, min_parallax: float = 0.0,
                        per_link: bool = True) -> RelativeScale:

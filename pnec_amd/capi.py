@@ -16,6 +16,10 @@ ABI_VERSION = 8  # PNEC_HIP_ABI_VERSION of include/pnec_hip.h this binding was w
 MODE_NEC, MODE_TARGET, MODE_HOST, MODE_SYM = 0, 1, 2, 3
 MEM_HOST, MEM_DEVICE = 0, 1
 TRI_ORIENT = 1   # pnec_hip_triangulate flags: per-correspondence outputs at the oriented translation
+EP_QUALITY_ALL = 1   # pnec_hip_eight_point flags: the candidates' qualities over all correspondences, not the first nine
+# pnec_hip_ep_status (pnec_hip_eight_point's out_status)
+EP_OK, EP_TOO_FEW, EP_NOT_FINITE, EP_NO_CANDIDATE = 0, 1, 2, 3
+EP_NAMES = {EP_OK: "ok", EP_TOO_FEW: "too_few", EP_NOT_FINITE: "not_finite", EP_NO_CANDIDATE: "no_candidate"}
 # pnec_hip_eigensolver_scheme: which iteration stands in for opengv's eigenvalue minimisation (include/pnec_hip.h)
 ES_NEWTON, ES_DESCENT, ES_LM = 0, 1, 2
 # PNEC_HIP_RANSAC_* bits (pnec_hip_pipeline_options.ransac_flags, pnec_hip_problem_set_ransac_flags)
@@ -67,6 +71,7 @@ SYMBOLS = [
     "pnec_hip_pose_covariance",
     "pnec_hip_residuals",
     "pnec_hip_triangulate",
+    "pnec_hip_eight_point",
     "pnec_hip_relative_scale",
     "pnec_hip_patch_covariance",
     "pnec_hip_image_pyramid_level",
@@ -230,6 +235,7 @@ def lib() -> C.CDLL:
     L.pnec_hip_residuals.argtypes = [_vp, _vp, _vp, C.c_int32, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                      C.c_int, _vp]
     L.pnec_hip_triangulate.argtypes = [_vp, _vp, _vp, C.c_int32, C.c_int32] + [_vp] * 11 + [C.c_int, _vp]
+    L.pnec_hip_eight_point.argtypes = [_vp, C.c_int32] + [_vp] * 8 + [C.c_int, _vp]
     L.pnec_hip_relative_scale.argtypes = [_vp] * 8 + [C.c_double] + [_vp] * 5 + [C.c_int, _vp]
     L.pnec_hip_patch_covariance.argtypes = [_vp, C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_int64, _vp, C.c_int64, _vp, _vp,
                                             C.c_int32, C.c_double] + [_vp] * 6 + [C.c_int, C.c_int, _vp]

@@ -1217,5 +1217,28 @@ std::vector<SE3d> PNEC::CeresSolverBatch(const std::vector<FramePair> &pairs, co
   return out;
 }
 
+SE3d EMPoseEstimation(const bearingVectors_t &bvs1, const bearingVectors_t &bvs2, const SE3d &initial_pose,
+                      algorithm_t algorithm, bool ransac) {
+  static const char *const names[] = {"STEWENIUS", "NISTER", "SEVENPT", "EIGHTPT"};
+  if (algorithm < STEWENIUS || algorithm > EIGHTPT) throw std::invalid_argument("EMPoseEstimation: unknown algorithm");
+  if (algorithm != EIGHTPT)
+    throw std::invalid_argument(std::string("EMPoseEstimation: ") + names[algorithm] +
+                                " is not built (only EIGHTPT with ransac = false is)");
+  if (ransac)
+    throw std::invalid_argument("EMPoseEstimation: ransac = true (opengv's CentralRelativePoseSacProblem) is not built "
+                                "(only EIGHTPT with ransac = false is)");
+  if (bvs1.size() != bvs2.size()) throw std::invalid_argument("bvs1 and bvs2 differ in size");
+  if (bvs1.empty()) return initial_pose;
+  Problem batch(optimization::SolverOptions().device, PNEC_HIP_MODE_NEC, {0, (int64_t)bvs1.size()});
+  Check(pnec_hip_problem_fill(batch.p, 0, 1, bvs1[0].data(), bvs2[0].data(), nullptr, nullptr, PNEC_HIP_MEM_HOST, nullptr));
+  double q[4], t[3], singular[3];
+  int32_t status = PNEC_HIP_EP_OK;
+  Check(pnec_hip_eight_point(batch.p, 0, q, t, nullptr, singular, nullptr, nullptr, nullptr, &status, PNEC_HIP_MEM_HOST,
+                             nullptr));
+  if (status != PNEC_HIP_EP_OK) return initial_pose;
+  // (q comes back with unit norm: no second normalisation, so the matrix is a function of the call's bits alone)
+  return SE3d(Quaterniond(q[3], q[0], q[1], q[2]).toRotationMatrix(), Vector3d(t[0], t[1], t[2]) * singular[0]);
+}
+
 }  // namespace rel_pose_estimation
 }  // namespace pnec

@@ -460,6 +460,18 @@ class PNEC {
   int64_t multi_pairs_ = 0, multi_corr_ = 0, multi_pair_corr_ = 0;
 };
 
+// essential_matrix_methods.h: the closed-form baselines of `run_simulation -e`.  algorithm_t stands in for
+// opengv::sac_problems::relative_pose::CentralRelativePoseSacProblem::algorithm_t (same names, same order).
+enum algorithm_t { STEWENIUS = 0, NISTER = 1, SEVENPT = 2, EIGHTPT = 3 };
+// EMPoseEstimation (essential_matrix_methods.cc:45-126).  Built: EIGHTPT with ransac == false -- opengv's eightpt and
+// PoseFromEssentialMatrix (common.cc:262-457) on the device, pnec_hip_eight_point.  The rotation takes frame-2 vectors
+// into frame 1; the translation has the length of E's largest singular value, as the reference's has.  Returns
+// initial_pose when the call finds no pose (fewer than 8 correspondences, a non-finite bearing, no candidate), as
+// essential_matrix_methods.cc:118-124 does.  Every other combination (STEWENIUS, NISTER, SEVENPT, or ransac == true:
+// opengv's CentralRelativePoseSacProblem) throws std::invalid_argument naming what is not built.
+SE3d EMPoseEstimation(const bearingVectors_t &bvs1, const bearingVectors_t &bvs2, const SE3d &initial_pose,
+                      algorithm_t algorithm, bool ransac = true);
+
 }  // namespace rel_pose_estimation
 
 // thrown when the HIP side reports an error (no device, bad argument, launch failure)

@@ -267,6 +267,17 @@ arr orient_translation(arr bvs1, arr bvs2, arr pose) {
   return FromPose(pnec::common::OrientTranslation(ToBearings(bvs1, "bvs_1"), ToBearings(bvs2, "bvs_2"), ToPose(pose)));
 }
 
+// EMPoseEstimation(bvs1, bvs2, identity, EIGHTPT, ransac = false): 4x4, the translation of length s0
+arr eight_point(arr bvs1, arr bvs2) {
+  const auto b1 = ToBearings(bvs1, "bvs_1"), b2 = ToBearings(bvs2, "bvs_2");
+  pnec::SE3d result;
+  {
+    py::gil_scoped_release release;
+    result = pnec::rel_pose_estimation::EMPoseEstimation(b1, b2, pnec::SE3d(), pnec::rel_pose_estimation::EIGHTPT, false);
+  }
+  return FromPose(result);
+}
+
 // (scale, q25, q75, n_used, ratio [N]) of one frame against the previous one
 py::tuple relative_scale(arr bvs_prev1, arr bvs_prev2, arr pose_prev, arr bvs1, arr bvs2, arr pose,
                          const std::vector<int> &link, double min_parallax) {
@@ -601,6 +612,10 @@ PYBIND11_MODULE(pypnec, m) {
   m.def("orient_translation", &orient_translation, py::arg("bvs1"), py::arg("bvs2"), py::arg("pose"),
         "pnec::common::OrientTranslation (addition; device): `pose` with its translation multiplied by the cheirality "
         "vote's sign, so that the structure lies in front of both cameras");
+  m.def("eight_point", &eight_point, py::arg("bvs1"), py::arg("bvs2"),
+        "pnec::rel_pose_estimation::EMPoseEstimation(bvs1, bvs2, identity, EIGHTPT, ransac = false) (device): the 4x4 pose "
+        "of the eight-point baseline, translation of length s0; the identity when the pair gives no pose -- "
+        "include/pnec_hip.h pnec_hip_eight_point");
   m.def("relative_scale", &relative_scale, py::arg("bvs_prev1"), py::arg("bvs_prev2"), py::arg("pose_prev"),
         py::arg("bvs1"), py::arg("bvs2"), py::arg("pose"), py::arg("link"), py::arg("min_parallax") = 0.0,
         "pnec::common::RelativeScale (addition; device): (scale, q25, q75, n_used, ratio [N]) -- the baseline of `pose` in "

@@ -23,6 +23,7 @@
 #include "pnec_patch_track.hpp"
 #include "pnec_pose_cov.hpp"
 #include "pnec_residuals.hpp"
+#include "pnec_eight_point.hpp"
 #include "pnec_relative_scale.hpp"
 #include "pnec_tracks.hpp"
 #include "pnec_triangulate.hpp"
@@ -1259,6 +1260,38 @@ int pnec_hip_triangulate(pnec_hip_problem *p, const double *q, const double *t, 
   // n_max of a batch whose sizes still live on the device (select) is the source's: an upper bound, which is all the
   // block size needs (the wavefronts a pair uses follow from its own count)
   PNEC_HIP_TRY(launch_triangulate(p->mode, S, cov_waves(p->n_max), a, stream));
+  return io.finish();
+}
+
+// essential matrix and pose of every pair from its correspondences alone: pnec_eight_point.hip
+int pnec_hip_eight_point(pnec_hip_problem *p, int32_t flags, double *out_q, double *out_t, double *out_E,
+                         double *out_singular, double *out_gap, double *out_quality, int32_t *out_choice,
+                         int32_t *out_status, int space, void *stream_) {
+  if (!p) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "eight_point: problem is NULL");
+  if (flags & ~PNEC_HIP_EP_QUALITY_ALL) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "eight_point: unknown bit in flags");
+  if (!out_q && !out_t && !out_E && !out_singular && !out_gap && !out_quality && !out_choice && !out_status)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "eight_point: every output is NULL");
+  if (int rc = check_space("eight_point: ", space)) return rc;
+  const int64_t P = p->n_pairs;
+  if (P > 0x7fffffffLL) return fail(PNEC_HIP_ERR_UNSUPPORTED, "more than 2^31-1 pairs in one call");
+  if (P == 0) return 0;
+  hipStream_t stream = (hipStream_t)stream_;
+  CallArrays io(p, space, stream);
+  EightPointArgs a;
+  a.data = p->d_data;
+  a.block_offset = p->d_block_offset;
+  a.count = p->d_count;
+  a.flags = flags;
+  io.out(a.out_q, out_q, 4 * P);
+  io.out(a.out_t, out_t, 3 * P);
+  io.out(a.out_E, out_E, 9 * P);
+  io.out(a.out_singular, out_singular, 3 * P);
+  io.out(a.out_gap, out_gap, P);
+  io.out(a.out_quality, out_quality, 4 * P);
+  io.out(a.out_choice, out_choice, P);
+  io.out(a.out_status, out_status, P);
+  if (int rc = io.commit()) return rc;
+  PNEC_HIP_TRY(launch_eight_point(P, a, stream));
   return io.finish();
 }
 

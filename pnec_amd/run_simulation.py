@@ -8,7 +8,12 @@
     PNEC w/o LS    (the reference records the NEC result under this name, run_simulation.cc:171-174)
     PNEC           PNEC::CeresSolver from PNEC::WeightedEigensolver    pnec.cc:283-348
 
-and write r_error.csv / t_error.csv / cost.csv in the reference's format.  All experiments of the
+and write r_error.csv / t_error.csv / cost.csv in the reference's format.  With --em-methods (the reference's `-e`,
+run_simulation.cc:88-131) one more column follows the six:
+
+    8pt            EMPoseEstimation(..., EIGHTPT, ransac = false)      essential_matrix_methods.cc:45-126
+
+(the start pose where the pair gives no pose, as the reference returns it).  All experiments of the
 folder go through each stage in ONE device launch.  Input side as `ReadExperiments`
 (src/simulation/sim_common.cc:109-236): relative pose = pose_1^-1 pose_2, bearings = normalised
 points, frame-2 covariances through the unscented transform (K^-1 = I, kappa = 1), start pose = ground
@@ -16,7 +21,7 @@ truth perturbed by <= 0.01 rad / 0.01 (own RNG with a recorded seed: the C++ std
 uniform_real_distribution stream is not reproduced).
 
     python -m pnec_amd.run_simulation <experiment_folder> [--camera pinhole|omni] [--out DIR]
-                                      [--init-scaling 1.0] [--seed 1]
+                                      [--init-scaling 1.0] [--seed 1] [--em-methods]
 """
 from __future__ import annotations
 
@@ -33,6 +38,7 @@ from .frontend import CAMERA_OMNIDIRECTIONAL, CAMERA_PINHOLE, unscented_transfor
 from .io_formats import read_experiments, relative_poses, write_result_tables
 
 METHODS = ("NEC", "NEC-LS", "NEC PNEC-LS", "PNEC only LS", "PNEC w/o LS", "PNEC")
+EM_METHODS = ("8pt",)   # the essential-matrix baselines that are built (7pt, Nister, Stewenius and the RANSAC forms are not)
 
 
 def _quat_to_matrix(q):
@@ -87,7 +93,7 @@ def perturbed_start(R_gt, t_gt, rng, init_scaling=1.0):
     return R0, t0 / np.linalg.norm(t0, axis=1, keepdims=True)
 
 
-def run(folder: str, camera: str = "pinhole", init_scaling: float = 1.0, seed: int = 1):
+def run(folder: str, camera: str = "pinhole", init_scaling: float = 1.0, seed: int = 1, em_methods: bool = False):
     ex = read_experiments(folder)
     E = len(ex["points_1"])
     counts = np.array([len(p) for p in ex["points_1"]], dtype=np.int64)
@@ -118,8 +124,14 @@ def run(folder: str, camera: str = "pinhole", init_scaling: float = 1.0, seed: i
         sols["PNEC w/o LS"] = (q_nec, t_nec)   # sic: run_simulation.cc:171-174 stores nec_result here
         r = pb.solve(q_it, t_it, reg=1e-13)
         sols["PNEC"] = (r.q, r.t)
+        methods = METHODS
+        if em_methods:
+            ep = nb.eight_point(on_device=False)
+            ok = (ep.status == capi.EP_OK)[:, None]
+            sols["8pt"] = (np.where(ok, ep.q, q0), np.where(ok, ep.t, t0))
+            methods = METHODS + EM_METHODS
         results = {}
-        for m in METHODS:
+        for m in methods:
             q, t = sols[m]
             results[m] = {"r_error": rotational_difference_deg(R_gt, _quat_to_matrix(np.asarray(q))),
                           "t_error": translational_difference_deg(t_gt, np.asarray(t)),
@@ -127,18 +139,24 @@ def run(folder: str, camera: str = "pinhole", init_scaling: float = 1.0, seed: i
     return results
 
 
-def main(argv=None):
+def parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("folder")
     ap.add_argument("--camera", choices=("pinhole", "omni"), default="pinhole")
     ap.add_argument("--out", default=None, help="where to write r_error.csv / t_error.csv / cost.csv (default: the folder)")
     ap.add_argument("--init-scaling", type=float, default=1.0)
     ap.add_argument("--seed", type=int, default=1)
-    args = ap.parse_args(argv)
-    res = run(args.folder, args.camera, args.init_scaling, args.seed)
+    ap.add_argument("--em-methods", action="store_true",
+                    help="add the essential-matrix baselines that are built (8pt) after the six columns")
+    return ap
+
+
+def main(argv=None):
+    args = parser().parse_args(argv)
+    res = run(args.folder, args.camera, args.init_scaling, args.seed, args.em_methods)
     write_result_tables(args.out or args.folder, res)
     print(json.dumps({m: {"median_r_error_deg": float(np.median(res[m]["r_error"])),
-                          "median_t_error_deg": float(np.median(res[m]["t_error"]))} for m in METHODS}))
+                          "median_t_error_deg": float(np.median(res[m]["t_error"]))} for m in res}))
     return 0
 
 
