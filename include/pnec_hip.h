@@ -20,6 +20,7 @@
  *   ceres::Solver::Options (default-constructed, pnec_ceres.cc:47)   pnec_hip_options
  *   pnec::common::CostFunction  src/common/common.cc:237-259    pnec_hip_cost_function
  *   pnec::common::UnscentedTransform / Unproject  common.cc:460-525   pnec_hip_unscented_transform
+ *   pnec::common::Undistort  common.cc:67-93 (cv::undistortPoints [EXT])   pnec_hip_undistort_keypoints
  *   (no counterpart: what ceres::Covariance would give for the        pnec_hip_pose_covariance
  *    problems of pnec_ceres.cc / nec_ceres.cc)
  *   (no counterpart: the per-residual values ceres::Problem::Evaluate  pnec_hip_residuals
@@ -238,6 +239,73 @@ int pnec_hip_problem_fill_keypoints(pnec_hip_problem *p, int64_t first_pair, int
 int pnec_hip_problem_fill_keypoints_ragged(pnec_hip_problem *p, const int64_t *offsets, int64_t n_rows, const double *pts1,
                                            const double *pts2, const double *cov2, const double *cov1, const double *K_inv,
                                            double kappa, int camera_model, int32_t *out_dropped, int space, void *stream);
+
+/* Keypoint undistortion: the radial-tangential ("plumb bob") lens model inverted per tracked point (added within ABI 8: a
+ * pure addition, PNEC_HIP_ABI_VERSION is unchanged).  The ingest above is pinhole only; a tracker follows patches in the
+ * raw image, so its points and 2x2 covariances are in distorted pixels.  This call stands between the two: rows in the
+ * layout of pnec_hip_problem_fill_keypoints_ragged come in, rows in that layout go out.  It is what the reference does
+ * per observation, pnec::common::Undistort (src/common/common.cc:67-93, called from converter.cc:75-92): a call of
+ * cv::undistortPoints with Camera.k1, k2, p1, p2 and P = K.
+ *
+ *   pts1, pts2 [n_rows,2]   raw pixels of frame 1 / frame 2; either may be NULL (that frame is left out)
+ *   cov2, cov1 [n_rows,3]   (xx, xy, yy) of pts2 / pts1, or NULL; a covariance needs its points
+ *   camera [9]              fx fy cx cy k1 k2 p1 p2 k3, in `space` like the other arrays
+ *   out_pts1, out_pts2, out_cov2, out_cov1   given exactly where their input is given
+ *   out_status1, out_status2  uint8 [n_rows] or NULL (NULL where the points are NULL): pnec_hip_undistort_status
+ *
+ * The forward model, distort(x, y), in normalised coordinates:
+ *     r2 = x x + y y,  cdist = 1 + ((k3 r2 + k2) r2 + k1) r2,
+ *     dx = p1 (2 x y) + p2 (r2 + 2 x x),  dy = p1 (r2 + 2 y y) + p2 (2 x y),
+ *     distort(x, y) = (x cdist + dx, y cdist + dy)
+ * and its Jacobian J, with dc = (3 k3 r2 + 2 k2) r2 + k1 (the derivative of cdist by r2):
+ *     j00 = cdist + 2 x x dc + (2 p1 y + 6 p2 x),   j11 = cdist + 2 y y dc + (6 p1 y + 2 p2 x),
+ *     j01 = j10 = 2 x y dc + (2 p1 x + 2 p2 y).
+ * Per point (u, v), every operation in FP64, rounded one by one in the order written (no fused multiply-add):
+ *  1 Normalise.  x0 = (u - cx) / fx, y0 = (v - cy) / fy.  A u or v that is not finite gives NaN for both output
+ *    coordinates, status NOT_FINITE, and its covariance is copied.
+ *  2 Fixed point ([EXT]: cv::undistortPoints restated from memory, OpenCV is not in the reference tree; 5 steps are its
+ *    default termination).  Start at (x, y) = (x0, y0).  Repeat fixed_iterations times: r2 = x x + y y;
+ *    icdist = 1 / (1 + ((k3 r2 + k2) r2 + k1) r2); if icdist < 0 the point becomes (x0, y0), the status OUTSIDE, and the
+ *    iteration stops; else, with dx, dy as above at (x, y): x = (x0 - dx) icdist, y = (y0 - dy) icdist.
+ *  3 Newton, with PNEC_HIP_UNDISTORT_NEWTON (not in the reference) and only where step 2 did not end OUTSIDE.  Start
+ *    from step 2's result.  Before each of up to newton_iterations steps the forward residual e = distort(x, y) - (x0, y0)
+ *    and rho = sqrt(e0 e0 + e1 e1) are computed; rho <= 2^-46 max(1, sqrt(x0 x0 + y0 y0)) stops the iteration with OK.
+ *    Otherwise det = j00 j11 - j01 j10; a det that is zero or not finite ends the iteration; else
+ *    x -= (j11 e0 - j01 e1) / det, y -= (j00 e1 - j10 e0) / det.  rho is looked at once more after the last step.  If the
+ *    iteration ended without the stop, the status is NOT_CONVERGED and the point is step 2's result: never worse than
+ *    the reference's answer.
+ *  4 Back to pixels with the same K (the reference passes P = K): u' = fx x + cx, v' = fy y + cy.
+ *  5 Covariance.  Without PNEC_HIP_UNDISTORT_PROPAGATE_COV (the reference), or where the status is not OK, the three
+ *    doubles are copied bit for bit.  With it, J is taken at the returned (x, y), and with D = diag(fx, fy) the linear
+ *    map of pixels is A = D J^-1 D^-1: a00 = j11 / det, a01 = ((-j01 / det) fx) / fy, a10 = ((-j10 / det) fy) / fx,
+ *    a11 = j00 / det.  M = A S, S' = M A': xx' = m00 a00 + m01 a01, xy' = m00 a10 + m01 a11, yy' = m10 a10 + m11 a11.
+ *    (A det that is zero or not finite copies the covariance; the status stays OK.)
+ *  6 All five coefficients zero (compared with == 0.0): points and covariances are copied bit for bit with status OK,
+ *    whatever the flags and whatever the points hold; this is looked at first.  The kernel decides it from the camera
+ *    array, since in DEVICE space the host never sees it: "distortion given but zero" equals "no distortion".
+ * A row's bits depend on the row, the camera and the scalar arguments alone: not on n_rows, on the row's position or on
+ * the other rows.  Rows whose status is not OK pass through with their status, as in OpenCV; nothing is dropped.
+ *
+ * Aliasing: an output may be the very same pointer as its input (in place).  Any other overlap among the arrays is
+ * undefined.  DEVICE space: asynchronous on `stream`, no host wait, nothing allocated.  HOST space: staged on `device`
+ * like the other calls, waits for the stream.
+ * Refused with PNEC_HIP_ERR_INVALID_ARGUMENT before any device is touched: fixed_iterations or newton_iterations outside
+ * 0 .. 64 (newton_iterations is not looked at without the NEWTON flag), an unknown flag bit, n_rows < 0 or > 2^31-1,
+ * camera NULL, a bad space; and for n_rows > 0 an input without its output, an output (a status included) without its
+ * input, a covariance without its points.  n_rows == 0 returns 0. */
+#define PNEC_HIP_UNDISTORT_NEWTON 1u         /* polish the fixed-point result by Newton steps on the forward model */
+#define PNEC_HIP_UNDISTORT_PROPAGATE_COV 2u  /* out_cov = A cov A', else out_cov = cov bit for bit (the reference) */
+typedef enum pnec_hip_undistort_status {
+  PNEC_HIP_UNDISTORT_OK = 0,
+  PNEC_HIP_UNDISTORT_OUTSIDE = 1,
+  PNEC_HIP_UNDISTORT_NOT_CONVERGED = 2,
+  PNEC_HIP_UNDISTORT_NOT_FINITE = 3
+} pnec_hip_undistort_status;
+int pnec_hip_undistort_keypoints(int device, int64_t n_rows, const double *pts1, const double *pts2, const double *cov2,
+                                 const double *cov1, const double *camera, int32_t fixed_iterations,
+                                 int32_t newton_iterations, uint32_t flags, double *out_pts1, double *out_pts2,
+                                 double *out_cov2, double *out_cov1, uint8_t *out_status1, uint8_t *out_status2, int space,
+                                 void *stream);
 
 /* The batch's SoA planes as stored in HBM (pair blocks of round_up(N_p, 64)-double planes; the layout in
  * pnec_internal.hpp / DESIGN.md): size in doubles, and a copy out (tests, debugging). */

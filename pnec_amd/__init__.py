@@ -8,6 +8,7 @@ Layout:
   tracker.py       tracks across frames: retain, refill, and the frame loop over F sequences in lockstep
   patch_store.py   stored patches: a slot per track that keeps its templates for as long as it lives
   keyframes.py     keyframe pairs: skip frames that moved too little against the last accepted frame
+  undistort.py     keypoint undistortion: the radial-tangential lens model inverted per tracked point
   odometry.py      images in, poses out: the tracker, a batch shaped from its device offsets, and the chain
   simulation.py    synthetic inputs following the reference simulator's distributions (harness)
   distributed.py   one-process-per-GPU sharding of independent pair batches + one RCCL gather
@@ -22,6 +23,7 @@ from .patches import (PATTERN52, Keypoints, PatchCovariance, PatchTrack, detect_
 from .tracker import Tracker, TrackSet, append_tracks, retain_tracks  # noqa: F401
 from .patch_store import PatchStore, add_patches, new_patch_store, patch_track_stored  # noqa: F401
 from .tracks import chain_scales  # noqa: F401
+from .undistort import Undistorted, camera_array, undistort_keypoints  # noqa: F401
 
 __all__ = ["capi", "Batch", "EightPoint", "KeyframePairs", "KeyframeState", "KeyframeTracker", "Keypoints", "Odometry", "OdometryResult", "PATTERN52", "PatchCovariance", "PatchStore", "PatchTrack", "PoseCovariance", "RelativeScale", "ResidualReport", "SolveResult",
-           "TrackSet", "Tracker", "Triangulation", "add_patches", "append_tracks", "chain_scales", "detect_keypoints", "gate_sigma", "image_pyramid", "keyframe_pairs", "new_patch_store", "patch_covariance", "patch_track", "patch_track_stored", "retain_tracks", "select_best"]
+           "TrackSet", "Tracker", "Triangulation", "Undistorted", "add_patches", "append_tracks", "camera_array", "chain_scales", "detect_keypoints", "gate_sigma", "image_pyramid", "keyframe_pairs", "new_patch_store", "patch_covariance", "patch_track", "patch_track_stored", "retain_tracks", "select_best", "undistort_keypoints"]

@@ -20,6 +20,11 @@ EP_QUALITY_ALL = 1   # pnec_hip_eight_point flags: the candidates' qualities ove
 # pnec_hip_ep_status (pnec_hip_eight_point's out_status)
 EP_OK, EP_TOO_FEW, EP_NOT_FINITE, EP_NO_CANDIDATE = 0, 1, 2, 3
 EP_NAMES = {EP_OK: "ok", EP_TOO_FEW: "too_few", EP_NOT_FINITE: "not_finite", EP_NO_CANDIDATE: "no_candidate"}
+# pnec_hip_undistort_keypoints flags and pnec_hip_undistort_status (its out_status1 / out_status2)
+UNDISTORT_NEWTON, UNDISTORT_PROPAGATE_COV = 1, 2
+UNDISTORT_OK, UNDISTORT_OUTSIDE, UNDISTORT_NOT_CONVERGED, UNDISTORT_NOT_FINITE = 0, 1, 2, 3
+UNDISTORT_NAMES = {UNDISTORT_OK: "ok", UNDISTORT_OUTSIDE: "outside", UNDISTORT_NOT_CONVERGED: "not_converged",
+                   UNDISTORT_NOT_FINITE: "not_finite"}
 # pnec_hip_eigensolver_scheme: which iteration stands in for opengv's eigenvalue minimisation (include/pnec_hip.h)
 ES_NEWTON, ES_DESCENT, ES_LM = 0, 1, 2
 # PNEC_HIP_RANSAC_* bits (pnec_hip_pipeline_options.ransac_flags, pnec_hip_problem_set_ransac_flags)
@@ -52,6 +57,7 @@ SYMBOLS = [
     "pnec_hip_problem_fill",
     "pnec_hip_problem_fill_keypoints",
     "pnec_hip_problem_fill_keypoints_ragged",
+    "pnec_hip_undistort_keypoints",
     "pnec_hip_problem_payload_doubles",
     "pnec_hip_problem_export_payload",
     "pnec_hip_problem_num_pairs",
@@ -236,6 +242,8 @@ def lib() -> C.CDLL:
                                      C.c_int, _vp]
     L.pnec_hip_triangulate.argtypes = [_vp, _vp, _vp, C.c_int32, C.c_int32] + [_vp] * 11 + [C.c_int, _vp]
     L.pnec_hip_eight_point.argtypes = [_vp, C.c_int32] + [_vp] * 8 + [C.c_int, _vp]
+    L.pnec_hip_undistort_keypoints.argtypes = [C.c_int, C.c_int64] + [_vp] * 5 + [C.c_int32, C.c_int32, C.c_uint32] + \
+        [_vp] * 6 + [C.c_int, _vp]
     L.pnec_hip_relative_scale.argtypes = [_vp] * 8 + [C.c_double] + [_vp] * 5 + [C.c_int, _vp]
     L.pnec_hip_patch_covariance.argtypes = [_vp, C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_int64, _vp, C.c_int64, _vp, _vp,
                                             C.c_int32, C.c_double] + [_vp] * 6 + [C.c_int, C.c_int, _vp]

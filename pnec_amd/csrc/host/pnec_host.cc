@@ -202,6 +202,37 @@ Matrix3d UnscentedTransform(const Vector3d &mu, const Matrix3d &cov, const Matri
   return UnscentedTransform(std::vector<Vector3d>{mu}, std::vector<Matrix3d>{cov}, K_inv, kappa, camera_model)[0];
 }
 
+std::array<double, 9> UndistortCamera(const Matrix3d &K, const std::vector<double> &dist_coef) {
+  if (dist_coef.size() != 4 && dist_coef.size() != 5)
+    throw std::invalid_argument("Undistort: dist_coef takes 4 or 5 coefficients: k1 k2 p1 p2 [k3]");
+  if (K(0, 1) != 0.0 || K(1, 0) != 0.0 || K(2, 0) != 0.0 || K(2, 1) != 0.0 || K(2, 2) != 1.0)
+    throw std::invalid_argument("Undistort: K must be upper triangular with zero skew and last row (0, 0, 1)");
+  return {K(0, 0), K(1, 1), K(0, 2), K(1, 2), dist_coef[0], dist_coef[1], dist_coef[2], dist_coef[3],
+          dist_coef.size() == 5 ? dist_coef[4] : 0.0};
+}
+
+std::vector<uint8_t> Undistort(std::vector<Vector2d> &points, std::vector<Covariance2d> *covs, const Matrix3d &K,
+                               const std::vector<double> &dist_coef, const UndistortOptions &options) {
+  const std::array<double, 9> camera = UndistortCamera(K, dist_coef);
+  if (covs && covs->size() != points.size()) throw std::invalid_argument("Undistort: points and covs differ in size");
+  std::vector<uint8_t> status(points.size(), (uint8_t)PNEC_HIP_UNDISTORT_OK);
+  if (dist_coef[0] == 0.0 || points.empty()) return status;  // (the reference's rule, common.cc:74-76)
+  const uint32_t flags = (options.newton ? PNEC_HIP_UNDISTORT_NEWTON : 0u) |
+                         (options.propagate_cov ? PNEC_HIP_UNDISTORT_PROPAGATE_COV : 0u);
+  double *pts = points[0].data(), *cov = covs ? (*covs)[0].data() : nullptr;
+  // (frame 1's slots: in place, an output being its own input)
+  Check(pnec_hip_undistort_keypoints(optimization::SolverOptions().device, (int64_t)points.size(), pts, nullptr, nullptr, cov,
+                                     camera.data(), options.fixed_iterations, options.newton_iterations, flags, pts, nullptr,
+                                     nullptr, cov, status.data(), nullptr, PNEC_HIP_MEM_HOST, nullptr));
+  return status;
+}
+
+Vector2d Undistort(const Vector2d &point, const Matrix3d &K, const std::vector<double> &dist_coef) {
+  std::vector<Vector2d> points{point};
+  Undistort(points, nullptr, K, dist_coef);
+  return points[0];
+}
+
 double CostFunction(const bearingVectors_t &bvs_1, const bearingVectors_t &bvs_2,
                     const std::vector<Matrix3d> &covs, const SE3d &camera_pose) {
   if (bvs_1.size() != bvs_2.size() || bvs_1.size() != covs.size())

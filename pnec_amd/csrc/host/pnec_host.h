@@ -47,6 +47,27 @@ Matrix3d UnscentedTransform(const Vector3d &mu, const Matrix3d &cov, const Matri
 std::vector<Matrix3d> UnscentedTransform(const std::vector<Vector3d> &mus, const std::vector<Matrix3d> &covs,
                                          const Matrix3d &K_inv, double kappa, CameraModel camera_model);
 
+// common.cc:67-93: cv::undistortPoints with the camera's K, dist_coef and P = K, evaluated on the device
+// (pnec_hip_undistort_keypoints; include/pnec_hip.h has the definition).  The reference reads K and dist_coef from its
+// Camera singleton; here they are arguments.  K: upper triangular, zero skew, last row (0, 0, 1); dist_coef: k1 k2 p1 p2
+// and optionally k3 -- anything else throws std::invalid_argument.
+// THE REFERENCE'S QUIRK, reproduced by both overloads: dist_coef[0] == 0.0 returns the input untouched (common.cc:74-76),
+// whatever k2, p1 and p2 are.  The C ABI does not have it: there only all five coefficients zero mean "no distortion".
+typedef std::array<double, 2> Vector2d;  // layout of Eigen::Vector2d
+typedef std::array<double, 3> Covariance2d;  // (xx, xy, yy) of a 2x2 image covariance
+struct UndistortOptions {
+  bool newton = false;          // polish the five fixed-point steps by Newton steps on the forward model (not in the reference)
+  bool propagate_cov = false;   // covs become A cov A' (not in the reference, which hands them on unchanged)
+  int fixed_iterations = 5, newton_iterations = 20;
+};
+// fx fy cx cy k1 k2 p1 p2 k3 for the C ABI; throws as described above.  No device.
+std::array<double, 9> UndistortCamera(const Matrix3d &K, const std::vector<double> &dist_coef);
+Vector2d Undistort(const Vector2d &point, const Matrix3d &K, const std::vector<double> &dist_coef);
+// points (and covs, when not NULL: one per point, else std::invalid_argument) are undistorted in place; returns one
+// pnec_hip_undistort_status per point (all OK where the quirk above returns the input)
+std::vector<uint8_t> Undistort(std::vector<Vector2d> &points, std::vector<Covariance2d> *covs, const Matrix3d &K,
+                               const std::vector<double> &dist_coef, const UndistortOptions &options = UndistortOptions());
+
 // include/common/timing.h:48-67: per-frame stage timers in milliseconds
 struct FrameTiming {
   explicit FrameTiming(int id) : id_(id) {}

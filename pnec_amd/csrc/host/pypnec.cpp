@@ -278,6 +278,52 @@ arr eight_point(arr bvs1, arr bvs2) {
   return FromPose(result);
 }
 
+// pnec::common::Undistort, batched: (points [n,2], covs [n,3] or None, status uint8 [n])
+py::tuple undistort(arr points, arr K, std::vector<double> dist, py::object covs, bool newton, bool propagate_cov) {
+  if (points.ndim() != 2 || points.shape(1) != 2) throw std::invalid_argument("points must be [N,2]");
+  const size_t n = (size_t)points.shape(0);
+  std::vector<pnec::common::Vector2d> pts(n);
+  auto r = points.unchecked<2>();
+  for (size_t i = 0; i < n; ++i) pts[i] = {r((py::ssize_t)i, 0), r((py::ssize_t)i, 1)};
+  std::vector<pnec::common::Covariance2d> cv;
+  const bool with_cov = !covs.is_none();
+  if (with_cov) {
+    const arr c = covs.cast<arr>();
+    if (c.ndim() != 2 || c.shape(1) != 3 || (size_t)c.shape(0) != n)
+      throw std::invalid_argument("covs must be [N,3]: (xx, xy, yy) per point");
+    auto rc = c.unchecked<2>();
+    cv.resize(n);
+    for (size_t i = 0; i < n; ++i) cv[i] = {rc((py::ssize_t)i, 0), rc((py::ssize_t)i, 1), rc((py::ssize_t)i, 2)};
+  }
+  pnec::common::UndistortOptions options;
+  options.newton = newton;
+  options.propagate_cov = propagate_cov;
+  const pnec::Matrix3d Km = ToMatrix3(K, "K");
+  std::vector<uint8_t> status;
+  {
+    py::gil_scoped_release release;
+    status = pnec::common::Undistort(pts, with_cov ? &cv : nullptr, Km, dist, options);
+  }
+  arr out_pts({(py::ssize_t)n, (py::ssize_t)2});
+  py::array_t<uint8_t> out_status((py::ssize_t)n);
+  auto wp = out_pts.mutable_unchecked<2>();
+  auto ws = out_status.mutable_unchecked<1>();
+  for (size_t i = 0; i < n; ++i) {
+    wp((py::ssize_t)i, 0) = pts[i][0];
+    wp((py::ssize_t)i, 1) = pts[i][1];
+    ws((py::ssize_t)i) = status[i];
+  }
+  py::object out_cov = py::none();
+  if (with_cov) {
+    arr oc({(py::ssize_t)n, (py::ssize_t)3});
+    auto wc = oc.mutable_unchecked<2>();
+    for (size_t i = 0; i < n; ++i)
+      for (int k = 0; k < 3; ++k) wc((py::ssize_t)i, k) = cv[i][(size_t)k];
+    out_cov = oc;
+  }
+  return py::make_tuple(out_pts, out_cov, out_status);
+}
+
 // (scale, q25, q75, n_used, ratio [N]) of one frame against the previous one
 py::tuple relative_scale(arr bvs_prev1, arr bvs_prev2, arr pose_prev, arr bvs1, arr bvs2, arr pose,
                          const std::vector<int> &link, double min_parallax) {
@@ -616,6 +662,12 @@ PYBIND11_MODULE(pypnec, m) {
         "pnec::rel_pose_estimation::EMPoseEstimation(bvs1, bvs2, identity, EIGHTPT, ransac = false) (device): the 4x4 pose "
         "of the eight-point baseline, translation of length s0; the identity when the pair gives no pose -- "
         "include/pnec_hip.h pnec_hip_eight_point");
+  m.def("undistort", &undistort, py::arg("points"), py::arg("K"), py::arg("dist"), py::arg("covs") = py::none(),
+        py::arg("newton") = false, py::arg("propagate_cov") = false,
+        "pnec::common::Undistort, batched (device): cv::undistortPoints with K, dist = k1 k2 p1 p2 [k3] and P = K for "
+        "points [N,2] and optionally their covariances [N,3] (xx, xy, yy); returns (points, covs or None, status uint8 [N]). "
+        "newton polishes the five fixed-point steps, propagate_cov carries the covariances through the map (neither is in the "
+        "reference).  As in the reference, dist[0] == 0 returns the input -- include/pnec_hip.h pnec_hip_undistort_keypoints");
   m.def("relative_scale", &relative_scale, py::arg("bvs_prev1"), py::arg("bvs_prev2"), py::arg("pose_prev"),
         py::arg("bvs1"), py::arg("bvs2"), py::arg("pose"), py::arg("link"), py::arg("min_parallax") = 0.0,
         "pnec::common::RelativeScale (addition; device): (scale, q25, q75, n_used, ratio [N]) -- the baseline of `pose` in "

@@ -24,6 +24,7 @@
 #include "pnec_pose_cov.hpp"
 #include "pnec_residuals.hpp"
 #include "pnec_eight_point.hpp"
+#include "pnec_undistort.hpp"
 #include "pnec_relative_scale.hpp"
 #include "pnec_tracks.hpp"
 #include "pnec_triangulate.hpp"
@@ -880,6 +881,55 @@ int pnec_hip_problem_fill_keypoints_ragged(pnec_hip_problem *p, const int64_t *o
   if (e != hipSuccess) return fail_hip(e, "offsets_scan_kernel");
   p->lazy = true;
   p->lazy_stream = stream;
+  return io.finish();
+}
+
+// keypoint undistortion, the step before the two ingests above: pnec_undistort.hip.  No batch: HOST space stages in
+// buffers that live for the call only.
+int pnec_hip_undistort_keypoints(int device, int64_t n_rows, const double *pts1, const double *pts2, const double *cov2,
+                                 const double *cov1, const double *camera, int32_t fixed_iterations,
+                                 int32_t newton_iterations, uint32_t flags, double *out_pts1, double *out_pts2,
+                                 double *out_cov2, double *out_cov1, uint8_t *out_status1, uint8_t *out_status2, int space,
+                                 void *stream_) {
+  const std::string pre = "undistort_keypoints: ";
+  const bool newton = (flags & PNEC_HIP_UNDISTORT_NEWTON) != 0;
+  if (flags & ~(PNEC_HIP_UNDISTORT_NEWTON | PNEC_HIP_UNDISTORT_PROPAGATE_COV))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "unknown bit in flags");
+  if (fixed_iterations < 0 || fixed_iterations > 64)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "fixed_iterations must be 0 .. 64");
+  if (newton && (newton_iterations < 0 || newton_iterations > 64))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "newton_iterations must be 0 .. 64");
+  if (n_rows < 0 || n_rows > 0x7fffffffLL) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "n_rows must be 0 .. 2^31-1");
+  if (!camera) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "camera is NULL");
+  if (int rc = check_space(pre, space)) return rc;
+  if (n_rows == 0) return 0;   // (an array of no rows says nothing: a caller's empty array may have no address)
+  if ((pts1 != nullptr) != (out_pts1 != nullptr) || (pts2 != nullptr) != (out_pts2 != nullptr) ||
+      (cov2 != nullptr) != (out_cov2 != nullptr) || (cov1 != nullptr) != (out_cov1 != nullptr))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "an input and its output are given or NULL together");
+  if ((out_status1 && !pts1) || (out_status2 && !pts2))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "a status array without its points");
+  if ((cov1 && !pts1) || (cov2 && !pts2)) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "a covariance without its points");
+  if (!pts1 && !pts2) return 0;
+  hipStream_t stream = (hipStream_t)stream_;
+  CallArrays io(device, space, stream);
+  UndistortArgs a{};
+  a.n_rows = n_rows;
+  a.fixed_iterations = fixed_iterations;
+  a.newton_iterations = newton ? newton_iterations : 0;
+  a.flags = flags;
+  io.in(a.pts[0], pts1, 2 * n_rows);
+  io.in(a.pts[1], pts2, 2 * n_rows);
+  io.in(a.cov[1], cov2, 3 * n_rows);
+  io.in(a.cov[0], cov1, 3 * n_rows);
+  io.in(a.camera, camera, 9);
+  io.out(a.out_pts[0], out_pts1, 2 * n_rows);
+  io.out(a.out_pts[1], out_pts2, 2 * n_rows);
+  io.out(a.out_cov[1], out_cov2, 3 * n_rows);
+  io.out(a.out_cov[0], out_cov1, 3 * n_rows);
+  io.out(a.out_status[0], out_status1, n_rows);
+  io.out(a.out_status[1], out_status2, n_rows);
+  if (int rc = io.commit()) return rc;
+  PNEC_HIP_TRY(launch_undistort_keypoints(a, stream));
   return io.finish();
 }
 

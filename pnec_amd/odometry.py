@@ -13,6 +13,11 @@ pair has no pose).
 With ``min_displacement > 0`` the pairs are keyframe pairs (keyframes.py): a sequence whose frame moved too little
 against its key frame is skipped -- its pose is NaN, its n_corr 0 -- and the chain of a later pair starts from the last
 ACCEPTED pair's rotation (the reference's PrevRelRotation).
+
+With ``distortion`` the pair's rows go through ``undistort_keypoints`` (undistort.py) on their way from the tracker to
+the ingest; the tracker itself goes on from its raw positions.  DEVIATION from the reference, which measures the
+keyframe displacement after undistortion (its keypoints are undistorted when they are made): here it is measured in raw
+pixels, before this step.
 """
 from __future__ import annotations
 
@@ -24,6 +29,7 @@ from . import capi
 from .batch import Batch
 from .keyframes import KeyframeTracker
 from .tracker import Tracker, TrackSet
+from .undistort import camera_array, new_undistorted, undistort_keypoints
 
 
 @dataclass
@@ -50,6 +56,19 @@ def start_rotation(prev_q, identity):
     return torch.where(torch.isfinite(prev_q).all(dim=-1, keepdim=True), prev_q, identity)
 
 
+def _camera_from(K_inv, distortion):
+    """camera_array from K_inv [3,3] (host) and 4 or 5 distortion coefficients; ValueError unless K_inv is upper
+    triangular with zero skew and last row (0, 0, 1)."""
+    d = [float(x) for x in distortion]
+    if len(d) not in (4, 5):
+        raise ValueError("distortion takes 4 or 5 coefficients: k1 k2 p1 p2 [k3]")
+    a, b = K_inv[0, 0], K_inv[1, 1]
+    if K_inv[0, 1] != 0.0 or K_inv[1, 0] != 0.0 or K_inv[2, 0] != 0.0 or K_inv[2, 1] != 0.0 or K_inv[2, 2] != 1.0 or \
+            not (np.isfinite(K_inv).all() and a != 0.0 and b != 0.0):
+        raise ValueError("with a distortion K_inv must be upper triangular with zero skew and last row (0, 0, 1)")
+    return camera_array(1.0 / a, 1.0 / b, -K_inv[0, 2] / a, -K_inv[1, 2] / b, *d)
+
+
 class Odometry:
     """Tracker + one capacity Batch, all allocated in the constructor.
 
@@ -60,10 +79,18 @@ class Odometry:
 
     min_displacement > 0 turns keyframes on (KeyframeTracker: ring >= 4, max_span in 1 .. ring - 2, default ring - 2); with
     the default 0 every consecutive pair is solved, as before, and nothing of the keyframe machinery is created.
-    templates="patches" among the tracker_kwargs runs both on stored patches (no age limit, ring >= 2, any max_span)."""
+    templates="patches" among the tracker_kwargs runs both on stored patches (no age limit, ring >= 2, any max_span).
+
+    distortion: None (an ideal pinhole camera: nothing is created and process makes the calls it always made) or the 4 or
+    5 coefficients k1 k2 p1 p2 [k3] of the radial-tangential model.  K is then recovered from K_inv, which must be upper
+    triangular with zero skew and last row (0, 0, 1).  Each pair's rows are undistorted (the reference's five fixed-point
+    steps; undistort_newton polishes them, undistort_propagate_cov carries the covariances through the map) into buffers
+    made here, never in place; `undistorted` holds the rows and statuses of the last step, `OdometryResult.pairs` stays the
+    raw tracker result.  The keyframe displacement is measured in raw pixels (the reference: after undistortion)."""
 
     def __init__(self, n_sequences: int, height: int, width: int, K_inv, mode: int = capi.MODE_TARGET,
                  pipeline_options: capi.PipelineOptions | None = None, min_displacement: float = 0.0, max_span: int = None,
+                 *, distortion=None, undistort_newton: bool = False, undistort_propagate_cov: bool = False,
                  **tracker_kwargs):
         import torch
         if mode not in (capi.MODE_TARGET, capi.MODE_NEC):
@@ -72,6 +99,12 @@ class Odometry:
             raise ValueError("a MODE_NEC batch needs pipeline_options with use_nec")
         if not float(min_displacement) >= 0.0:
             raise ValueError("min_displacement must be >= 0")
+        K_inv_host = np.asarray(K_inv.cpu() if hasattr(K_inv, "cpu") else K_inv, dtype=np.float64)
+        if tuple(K_inv_host.shape) != (3, 3):
+            raise ValueError("K_inv must be [3,3]")
+        camera = None
+        if distortion is not None:
+            camera = _camera_from(K_inv_host, distortion)
         self.keyframes = None
         if float(min_displacement) > 0.0:
             self.keyframes = KeyframeTracker(n_sequences, height, width, min_displacement, max_span, **tracker_kwargs)
@@ -85,13 +118,26 @@ class Odometry:
             self.batch = Batch.with_capacity(mode, F, F * cap, device=dev.index)
             self.batch.reshape(np.arange(F + 1, dtype=np.int64) * cap)
         f64 = dict(dtype=torch.float64, device=dev)
-        self._K_inv = torch.as_tensor(np.asarray(K_inv.cpu() if hasattr(K_inv, "cpu") else K_inv, dtype=np.float64), **f64)
-        if tuple(self._K_inv.shape) != (3, 3):
-            raise ValueError("K_inv must be [3,3]")
+        self._K_inv = torch.as_tensor(K_inv_host, **f64)
+        self.undistorted = None   # the undistorted rows and statuses of the last step (distortion given)
+        self._camera = None
+        if camera is not None:
+            self._camera = torch.as_tensor(camera, **f64)
+            self._newton, self._propagate = bool(undistort_newton), bool(undistort_propagate_cov)
+            self._und = new_undistorted(F * cap, True, dev, cov2=mode == capi.MODE_TARGET)
         self._identity = torch.zeros((F, 4), **f64)
         self._identity[:, 3] = 1.0
         self._zero_t = torch.zeros((F, 3), **f64)
         self._prev_q = None
+
+    def _fill(self, offsets, pts1, pts2, cov):
+        """The pair's rows into the batch, through undistort_keypoints where a distortion was given."""
+        cov = cov if self.mode == capi.MODE_TARGET else None
+        if self._camera is not None:
+            u = self.undistorted = undistort_keypoints(self._camera, pts1, pts2, cov, newton=self._newton,
+                                                       propagate_cov=self._propagate, out=self._und)
+            pts1, pts2, cov = u.pts1, u.pts2, u.cov2
+        self.batch.fill_keypoints_ragged(offsets, pts1, pts2, cov, K_inv=self._K_inv)
 
     def _process_keyframes(self, images):
         import torch
@@ -99,8 +145,7 @@ class Odometry:
         if pairs is None:
             return None
         with torch.cuda.device(self.device):
-            self.batch.fill_keypoints_ragged(pairs.offsets, pairs.key_pts, pairs.pts,
-                                             pairs.cov if self.mode == capi.MODE_TARGET else None, K_inv=self._K_inv)
+            self._fill(pairs.offsets, pairs.key_pts, pairs.pts, pairs.cov)
             init_q = start_rotation(self._prev_q, self._identity)
             q, t = self.batch.solve_pipeline(init_q, self._zero_t, self.pipeline_options)
         accepted = pairs.accepted.to(torch.bool)[:, None]
@@ -119,8 +164,7 @@ class Odometry:
         if pairs is None:
             return None
         with torch.cuda.device(self.device):
-            self.batch.fill_keypoints_ragged(pairs.offsets, pairs.prev_pts, pairs.pts,
-                                             pairs.cov if self.mode == capi.MODE_TARGET else None, K_inv=self._K_inv)
+            self._fill(pairs.offsets, pairs.prev_pts, pairs.pts, pairs.cov)
             init_q = start_rotation(self._prev_q, self._identity)
             q, t = self.batch.solve_pipeline(init_q, self._zero_t, self.pipeline_options)
         n_corr = torch.diff(pairs.offsets).clamp(0, self.capacity).to(torch.int32)

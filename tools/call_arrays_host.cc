@@ -391,6 +391,24 @@ void image_lists(int64_t F, int64_t elem, int64_t n_points) {
         l.out(l.opt(), F, 8);      // out_dropped
       }, (have_set ? F + 1 + 9 * Ns : 0) + (F + 1) + 5 * D + F + (F + 1) + 9 * O + F, 2 * Ns + 2 * O);
     }
+    // keypoint undistortion (no images, no batch): N rows; either frame may be left out, a covariance goes with its
+    // points, and an output is there exactly when its input is
+    run(tag("undistort_keypoints", {N}), [&](List &l) {
+      const bool pts1 = l.opt(), pts2 = l.opt();
+      const bool cov2 = l.opt() && pts2, cov1 = l.opt() && pts1;
+      const bool status1 = l.opt() && pts1, status2 = l.opt() && pts2;
+      l.in(pts1, 2 * N, 8);
+      l.in(pts2, 2 * N, 8);
+      l.in(cov2, 3 * N, 8);
+      l.in(cov1, 3 * N, 8);
+      l.in(true, 9, 8);          // camera
+      l.out(pts1, 2 * N, 8);
+      l.out(pts2, 2 * N, 8);
+      l.out(cov2, 3 * N, 8);
+      l.out(cov1, 3 * N, 8);
+      l.out(status1, N, 1);
+      l.out(status2, N, 1);
+    }, 20 * N + 9 + 2 * d8(N), 0);
   }
 }
 
