@@ -200,7 +200,7 @@ __host__ __device__ constexpr int slot_corr(int k, int lane) {
 // (global_load_lds_dwordx4: memory -> LDS without passing through VGPRs): with the register file full
 // of payload there are no temporaries to stage them through, and staging them a few registers at a
 // time exposed the HBM latency once per batch (the load phase was 11 % of a wavefront's life).  One
-// instruction copies 512 B = one plane of one slot (lanes 0..31, 16 B each, landing linearly).
+// instruction copies 1 KiB = two planes of one slot (64 lanes, 16 B each, landing linearly).
 template <int NC, int CPL, int REGK>
 __device__ __forceinline__ void load_resident(const double *__restrict__ base, int n, int stride,
                                               int first_corr, int lane, double (&d)[REGK][NC],
@@ -241,13 +241,17 @@ __device__ __forceinline__ void load_resident(const double *__restrict__ base, i
     for (int k = REGK; k < CPL; ++k) {
       const int chunk = first_corr + kWave * k;  // 64 consecutive correspondences, 64-aligned
       if (chunk < stride) {                      // wave-uniform: the chunk is inside the plane or beyond it
-        if (lane < kWave / 2) {
+        // two planes per instruction: lanes 0..31 bring plane c, lanes 32..63 plane c + 1 (16 B each), and the 64 x 16 B
+        // land linearly from the destination of plane c -- planes c and c + 1 of a slot are neighbours in LDS.  Half
+        // the DMA instructions (and their m0 set-ups) of one plane per instruction, no EXEC narrowing; same bytes in
+        // the same places.
+        static_assert(NC % 2 == 0, "the LDS slots are loaded two planes at a time");
+        const int plane_half = lane >> 5, in_plane = 2 * (lane & (kWave / 2 - 1));
 #pragma unroll
-          for (int c = 0; c < NC; ++c)
-            __builtin_amdgcn_global_load_lds((global_void *)(base + (int64_t)c * stride + chunk + 2 * lane),
-                                             (lds_void *)(uintptr_t)(uint32_t)(uintptr_t)(lds + ((k - REGK) * NC + c) * kWave),
-                                             16, 0, 0);
-        }
+        for (int c = 0; c < NC; c += 2)
+          __builtin_amdgcn_global_load_lds((global_void *)(base + (int64_t)(c + plane_half) * stride + chunk + in_plane),
+                                           (lds_void *)(uintptr_t)(uint32_t)(uintptr_t)(lds + ((k - REGK) * NC + c) * kWave),
+                                           16, 0, 0);
       } else {
 #pragma unroll
         for (int c = 0; c < NC; ++c) lds[((k - REGK) * NC + c) * kWave + lane] = 0.0;

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Analyse a PNEC_HIP_TRACE file (last launch): phase durations per workgroup and the overlap of
-load phases between wavefronts sharing a CU / SIMD.  s_memtime ticks are converted with the clock
-given as argv[3] (MHz, default 100 = the constant reference clock on gfx9-family parts)."""
+load phases between wavefronts sharing a CU / SIMD, the lifetime per wavefront and the load phase's share of it.
+s_memtime ticks are converted with the clock given as argv[3] (MHz, default 100 = the constant reference clock on
+gfx9-family parts).  On MI355X the counter was seen to advance at the shader clock instead -- a 116 k-tick lifetime on
+the headline workload beside the 118 k clocks of SQ_WAVE_CYCLES, and 2.6 ms / (100 000 solves / 2 048 slots) = 53 us:
+about 2 150 MHz under that load; with the default the "us" columns are then ticks / 100."""
 import sys
 from collections import defaultdict
 import numpy as np
@@ -16,6 +19,9 @@ ld, cp = (t1 - t0) / mhz, (t2 - t1) / mhz
 print("ticks: load mean %.0f compute mean %.0f ; with %.0f MHz -> load %.2f us, compute %.2f us" %
       ((t1 - t0).mean(), (t2 - t1).mean(), mhz, ld.mean(), cp.mean()))
 print("load p10/p50/p90 us: %.2f %.2f %.2f" % tuple(np.percentile(ld, [10, 50, 90])))
+life = (t2 - t0) / mhz
+print("lifetime p10/p50/p90 us: %.2f %.2f %.2f" % tuple(np.percentile(life, [10, 50, 90])))
+print("load / lifetime: mean %.4f, p50 of the ratio %.4f" % (ld.sum() / life.sum(), np.median(ld / np.maximum(life, 1e-9))))
 print("distinct xcc %d se %d sh %d cu %d simd %d wave_id %s" % (len(set(xcc)), len(set(se)), len(set(sh)), len(set(cu)), len(set(simd)), sorted(set(wave_id))))
 groups = defaultdict(list)
 for i in range(len(a)):
