@@ -21,6 +21,9 @@
  *   pnec::common::CostFunction  src/common/common.cc:237-259    pnec_hip_cost_function
  *   pnec::common::UnscentedTransform / Unproject  common.cc:460-525   pnec_hip_unscented_transform
  *   pnec::common::Undistort  common.cc:67-93 (cv::undistortPoints [EXT])   pnec_hip_undistort_keypoints
+ *   matches_from_poses  scripts/pnec/visual_odometry/io/evaluate_run.py:118-129      pnec_hip_trajectory_compose
+ *    (the chain of relative poses and the pose correction)
+ *   rmse, l1_error, rpe_n, l1_rpe_n, r_t  in scripts/pnec/metrics                      pnec_hip_trajectory_metrics
  *   (no counterpart: what ceres::Covariance would give for the        pnec_hip_pose_covariance
  *    problems of pnec_ceres.cc / nec_ceres.cc)
  *   (no counterpart: the per-residual values ceres::Problem::Evaluate  pnec_hip_residuals
@@ -306,6 +309,92 @@ int pnec_hip_undistort_keypoints(int device, int64_t n_rows, const double *pts1,
                                  int32_t newton_iterations, uint32_t flags, double *out_pts1, double *out_pts2,
                                  double *out_cov2, double *out_cov1, uint8_t *out_status1, uint8_t *out_status2, int space,
                                  void *stream);
+
+/* Trajectory evaluation (added within ABI 8: a pure addition, PNEC_HIP_ABI_VERSION is unchanged): the relative poses of a
+ * run composed into a trajectory, and the five numbers the reference judges a run by.  Both calls take rows that are
+ * sequence-major and ragged by `offsets` int64 [n_seq + 1], in `space` like the other arrays; sequence f is the rows
+ * lo .. hi of the cut pnec_hip_problem_fill_keypoints_ragged makes: lo = clamp(offsets[f], 0, n_rows),
+ * hi = clamp(offsets[f + 1], lo, n_rows), L = hi - lo.  Rows of no sequence are neither read nor written (out_err_q
+ * aside, which is written for every row).  Quaternions are x, y, z, w; all arithmetic is FP64.
+ *
+ * Rules of both calls.  DEVICE space: asynchronous on `stream`, no host wait, nothing allocated, `offsets` is not read
+ * back; the launches are sized by n_rows and n_seq alone; the offsets must not step down after the cut (else the
+ * outputs are unspecified; every access stays inside the arrays).  No floating-point atomics: every sum runs in an order
+ * fixed by L, so the bits of a sequence's outputs depend on its own rows (and q0, p0) and on L alone, not on n_seq, on
+ * the sequence's position or on its neighbours.  HOST space: the arrays are staged on `device`, the offsets are checked
+ * (from 0, non-decreasing, within n_rows), and the call waits for the stream.
+ * Refused with PNEC_HIP_ERR_INVALID_ARGUMENT before any device is touched: n_seq < 1 or > 2^31-1, n_rows < 0 or
+ * > 2^31-1, offsets NULL, a bad space, an output that is also an input or another output (the same pointer; arrays that overlap
+ * otherwise are undefined), and what each call lists.
+ *
+ * pnec_hip_trajectory_compose: evaluate_run.py:118-120 (poses[i] = poses[i-1] * poses[i]) and :122-129 (the pose
+ * correction, a left factor) per sequence.
+ *   rel_q [n_rows,4]         the relative rotation of each row
+ *   rel_t [n_rows,3] | NULL  its translation
+ *   scale [n_rows] | NULL    multiplies rel_t (the output of pnec_hip_relative_scale chained); needs rel_t
+ *   q0 [n_seq,4] | NULL      the left factor's rotation per sequence (NULL: the identity); normalised as read
+ *   p0 [n_seq,3] | NULL      the left factor's position (NULL: zero); needs rel_t
+ *   out_q [n_rows,4]         the absolute rotations
+ *   out_p [n_rows,3]         the absolute positions, given exactly when rel_t is
+ *   out_valid [n_rows] uint8 | NULL   1 where the row was present
+ *  1 A row is present when every value given for it (rel_q, rel_t, scale, and the scaled translation) is finite and
+ *    |rel_q|^2 = x x + y y + z z + w w, as computed, is finite and > 0.  Its step is (rel_q / |rel_q|, scale rel_t).
+ *  2 A row that is not present acts as the identity step and gets out_valid 0: a frame the keyframe rule skipped or a
+ *    pair without correspondences, whose pose the odometry reports as NaN, carries the pose before it -- bit for bit
+ *    inside a lane's chunk of step 5, and to that step's rounding where the row is a chunk's first: the two rows then
+ *    come from products associated differently.
+ *  3 The first row of a sequence is a pose itself (the reference writes SE3() there): P_lo = (q0, p0) step_lo,
+ *    P_k = P_{k-1} step_k, with (q_a, p_a) (q_b, p_b) = (q_a q_b, p_a + R(q_a) p_b).
+ *  4 out_q is the product normalised once, where it is written; the running product is not normalised.  Its sign is
+ *    the product's: compare up to sign.  A q0 that is zero or not finite gives NaN for its sequence.
+ *  5 The definition is the sequential product from the left.  The kernel associates differently (the product is
+ *    associative): one wavefront per sequence, each lane multiplies ceil(L / 64) consecutive steps, a scan in a fixed
+ *    order joins the 64 partial products.  Against the sequential product in exact arithmetic: |dq| <= 8 (L + 2) u up
+ *    to sign and |dp| <= 16 (L + 2) u x (path length), u = 2^-53.
+ * Refused besides: rel_q or out_q NULL (n_rows > 0), scale or p0 without rel_t, out_p given without rel_t or missing
+ * with it.  n_rows == 0 returns 0. */
+int pnec_hip_trajectory_compose(int device, int64_t n_seq, const int64_t *offsets, int64_t n_rows, const double *rel_q,
+                                const double *rel_t, const double *scale, const double *q0, const double *p0,
+                                double *out_q, double *out_p, uint8_t *out_valid, int space, void *stream);
+
+/* pnec_hip_trajectory_metrics: RPE_1, RPE_n, L1RPE_1, L1RPE_n (scripts/pnec/metrics/rmse.py, l1_error.py, rpe_n.py,
+ * l1_rpe_n.py) and r_t (r_t.py:24-40) per sequence, in radians.
+ *   est_q, gt_q [n_rows,4]         absolute rotations, estimate and ground truth, in the reference's convention: the
+ *                                  relative pose of frames i, j is P_i^-1 P_j
+ *   est_p, gt_p [n_rows,3] | NULL  absolute positions, both or neither
+ *   out_metrics [n_seq,5]          RPE_1, RPE_n, L1RPE_1, L1RPE_n, r_t
+ *   out_err_q [n_rows,4], out_rmse_d [n_rows], out_l1_d [n_rows]   required: results, and the storage the call's
+ *                                  kernels hand on to one another, so that the call allocates nothing
+ *   out_angle1, out_rt1 [n_rows] | NULL   the angle and the translation error of consecutive rows; out_rt1 needs the
+ *                                  positions
+ *  1 e_i = normalise(normalise(est_i) conj(normalise(gt_i))) -> out_err_q, for every row.  The product a b has the vector
+ *    part (a_w b_x + a_x b_w) + (a_y b_z - a_z b_y) and its cyclic fellows and the scalar part (a_w b_w - a_x b_x) -
+ *    (a_y b_y + a_z b_z), every operation rounded on its own (no fused multiply-add): est_i == gt_i gives (0, 0, 0, 1).
+ *  2 angle(i, j) = 4 asin(min(1, |e_i - s e_j| / 2)), s = +1 if <e_i, e_j> >= 0, else -1.  It lies in [0, pi] and is the
+ *    reference's arccos((trace(rel) - 1) / 2) (rmse.py:19-25) of rel = (Est_j' Est_i)(Gt_i' Gt_j): the trace is cyclic,
+ *    so rel's angle is that of E_i' E_j with E = Est Gt'.
+ *  3 For d = 1 .. L-1: rmse_d = sqrt(sum_i angle(i, i+d)^2 / (L - d)), l1_d = sum_i angle(i, i+d) / (L - d), i = 0 ..
+ *    L-d-1, written at row lo + d; row lo gets 0.
+ *  4 out_angle1[lo + k] = angle(k-1, k); row lo gets 0.
+ *  5 RPE_1 = rmse_1, RPE_n = (sum_d rmse_d) / L, L1RPE_1 = l1_1, L1RPE_n = (sum_d l1_d) / L.  The divisor is L, not
+ *    L - 1: the reference's (rpe_n.py:39, l1_rpe_n.py:34).
+ *  6 r_t, for k = 1 .. L-1: u = R(gt_{k-1})' (p_gt,k - p_gt,k-1), normalised (gt_{k-1} normalised first), v likewise from
+ *    the estimate; rt_k = 2 asin(min(1, |u - s v| / 2)), s as in step 2: in [0, pi/2], the reference's
+ *    min(arccos(c), arccos(-c)).  A step of length zero gives NaN, as in the reference.  out_rt1[lo + k] = rt_k, row lo
+ *    gets 0; r_t is the mean of rt_k, and NaN without positions.
+ *  7 L < 2 gives NaN for all five metrics.  A row that is not finite (or a zero quaternion) gives NaN wherever it
+ *    enters, as in the reference; a caller drops such frames from both sides first, as the reference's join on
+ *    timestamps with dropna() does, so that the distance d counts matched rows.
+ * DEVIATION from the reference: an estimate that is exact gives 0 here, where arccos of a trace rounded past 3 gives
+ * NaN there; and small angles keep their digits (arccos loses half of them).
+ * Against exact arithmetic, u = 2^-53: out_err_q 16 u; any angle 64 u + 8 u angle; rmse_d, l1_d 64 u + (L - d + 8) u
+ * value; the _n metrics 64 u + (2 L + 8) u value.
+ * Refused besides: out_metrics NULL; for n_rows > 0 est_q, gt_q, out_err_q, out_rmse_d or out_l1_d NULL; one of est_p,
+ * gt_p without the other; out_rt1 without positions.  n_rows == 0 writes NaN to all of out_metrics and returns 0. */
+int pnec_hip_trajectory_metrics(int device, int64_t n_seq, const int64_t *offsets, int64_t n_rows, const double *est_q,
+                                const double *gt_q, const double *est_p, const double *gt_p, double *out_metrics,
+                                double *out_err_q, double *out_rmse_d, double *out_l1_d, double *out_angle1,
+                                double *out_rt1, int space, void *stream);
 
 /* The batch's SoA planes as stored in HBM (pair blocks of round_up(N_p, 64)-double planes; the layout in
  * pnec_internal.hpp / DESIGN.md): size in doubles, and a copy out (tests, debugging). */

@@ -9,6 +9,8 @@ Layout:
   patch_store.py   stored patches: a slot per track that keeps its templates for as long as it lives
   keyframes.py     keyframe pairs: skip frames that moved too little against the last accepted frame
   undistort.py     keypoint undistortion: the radial-tangential lens model inverted per tracked point
+  trajectory.py    trajectory evaluation: relative poses composed per sequence, RPE_1 / RPE_n / L1RPE_1 / L1RPE_n / r_t
+  evaluate.py      python -m pnec_amd.evaluate: a pose file against KITTI ground truth, the reference's metrics row
   odometry.py      images in, poses out: the tracker, a batch shaped from its device offsets, and the chain
   simulation.py    synthetic inputs following the reference simulator's distributions (harness)
   distributed.py   one-process-per-GPU sharding of independent pair batches + one RCCL gather
@@ -24,6 +26,8 @@ from .tracker import Tracker, TrackSet, append_tracks, retain_tracks  # noqa: F4
 from .patch_store import PatchStore, add_patches, new_patch_store, patch_track_stored  # noqa: F401
 from .tracks import chain_scales  # noqa: F401
 from .undistort import Undistorted, camera_array, undistort_keypoints  # noqa: F401
+from .trajectory import (Trajectory, TrajectoryMetrics, compose_trajectory, matched, stack_steps,  # noqa: F401
+                         trajectory_metrics)
 
 __all__ = ["capi", "Batch", "EightPoint", "KeyframePairs", "KeyframeState", "KeyframeTracker", "Keypoints", "Odometry", "OdometryResult", "PATTERN52", "PatchCovariance", "PatchStore", "PatchTrack", "PoseCovariance", "RelativeScale", "ResidualReport", "SolveResult",
-           "TrackSet", "Tracker", "Triangulation", "Undistorted", "add_patches", "append_tracks", "camera_array", "chain_scales", "detect_keypoints", "gate_sigma", "image_pyramid", "keyframe_pairs", "new_patch_store", "patch_covariance", "patch_track", "patch_track_stored", "retain_tracks", "select_best", "undistort_keypoints"]
+           "TrackSet", "Tracker", "Trajectory", "TrajectoryMetrics", "Triangulation", "Undistorted", "add_patches", "append_tracks", "camera_array", "chain_scales", "compose_trajectory", "detect_keypoints", "gate_sigma", "image_pyramid", "keyframe_pairs", "matched", "new_patch_store", "patch_covariance", "patch_track", "patch_track_stored", "retain_tracks", "select_best", "stack_steps", "trajectory_metrics", "undistort_keypoints"]

@@ -58,6 +58,8 @@ SYMBOLS = [
     "pnec_hip_problem_fill_keypoints",
     "pnec_hip_problem_fill_keypoints_ragged",
     "pnec_hip_undistort_keypoints",
+    "pnec_hip_trajectory_compose",
+    "pnec_hip_trajectory_metrics",
     "pnec_hip_problem_payload_doubles",
     "pnec_hip_problem_export_payload",
     "pnec_hip_problem_num_pairs",
@@ -244,6 +246,8 @@ def lib() -> C.CDLL:
     L.pnec_hip_eight_point.argtypes = [_vp, C.c_int32] + [_vp] * 8 + [C.c_int, _vp]
     L.pnec_hip_undistort_keypoints.argtypes = [C.c_int, C.c_int64] + [_vp] * 5 + [C.c_int32, C.c_int32, C.c_uint32] + \
         [_vp] * 6 + [C.c_int, _vp]
+    L.pnec_hip_trajectory_compose.argtypes = [C.c_int, C.c_int64, _vp, C.c_int64] + [_vp] * 8 + [C.c_int, _vp]
+    L.pnec_hip_trajectory_metrics.argtypes = [C.c_int, C.c_int64, _vp, C.c_int64] + [_vp] * 10 + [C.c_int, _vp]
     L.pnec_hip_relative_scale.argtypes = [_vp] * 8 + [C.c_double] + [_vp] * 5 + [C.c_int, _vp]
     L.pnec_hip_patch_covariance.argtypes = [_vp, C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_int64, _vp, C.c_int64, _vp, _vp,
                                             C.c_int32, C.c_double] + [_vp] * 6 + [C.c_int, C.c_int, _vp]

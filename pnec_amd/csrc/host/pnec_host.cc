@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstring>
 #include <fstream>
+#include <limits>
 
 namespace pnec {
 namespace {
@@ -1272,4 +1273,68 @@ SE3d EMPoseEstimation(const bearingVectors_t &bvs1, const bearingVectors_t &bvs2
 }
 
 }  // namespace rel_pose_estimation
+
+namespace odometry {
+namespace {
+// rows of the C ABI from poses: xyzw of the rotation (Shepperd, as Eigen) and the translation
+void PoseRows(const std::vector<SE3d> &poses, std::vector<double> &q, std::vector<double> &p) {
+  q.resize(4 * poses.size());
+  p.resize(3 * poses.size());
+  for (size_t i = 0; i < poses.size(); ++i) {
+    const Quaterniond r = poses[i].unit_quaternion();
+    for (int k = 0; k < 4; ++k) q[4 * i + (size_t)k] = r.coeffs()[k];
+    for (int k = 0; k < 3; ++k) p[3 * i + (size_t)k] = poses[i].translation()[k];
+  }
+}
+}  // namespace
+
+std::vector<SE3d> ComposeTrajectory(const std::vector<SE3d> &relative_poses, const SE3d &correction,
+                                    std::vector<uint8_t> *valid) {
+  const size_t n = relative_poses.size();
+  std::vector<SE3d> out(n);
+  if (valid) valid->assign(n, 0);
+  if (n == 0) return out;
+  std::vector<double> q, t, q0, p0, out_q(4 * n), out_p(3 * n);
+  std::vector<uint8_t> present(n);
+  PoseRows(relative_poses, q, t);
+  PoseRows({correction}, q0, p0);
+  const int64_t offsets[2] = {0, (int64_t)n};
+  Check(pnec_hip_trajectory_compose(optimization::SolverOptions().device, 1, offsets, (int64_t)n, q.data(), t.data(), nullptr,
+                                    q0.data(), p0.data(), out_q.data(), out_p.data(), present.data(), PNEC_HIP_MEM_HOST,
+                                    nullptr));
+  for (size_t i = 0; i < n; ++i) {
+    const double *r = &out_q[4 * i];
+    Vector3d p;
+    for (int k = 0; k < 3; ++k) p[k] = out_p[3 * i + (size_t)k];
+    out[i] = SE3d(Quaterniond(r[3], r[0], r[1], r[2]), p);
+  }
+  if (valid) *valid = present;
+  return out;
+}
+
+TrajectoryScore TrajectoryMetrics(const std::vector<SE3d> &estimated, const std::vector<SE3d> &ground_truth) {
+  if (estimated.size() != ground_truth.size())
+    throw std::invalid_argument("TrajectoryMetrics: estimated and ground_truth differ in size (match the frames first)");
+  const size_t n = estimated.size();
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  TrajectoryScore s{nan, nan, nan, nan, nan, std::vector<double>(n), std::vector<double>(n), std::vector<double>(n),
+                    std::vector<double>(n)};
+  if (n == 0) return s;
+  std::vector<double> eq, ep, gq, gp, err_q(4 * n);
+  PoseRows(estimated, eq, ep);
+  PoseRows(ground_truth, gq, gp);
+  const int64_t offsets[2] = {0, (int64_t)n};
+  double m[5];
+  Check(pnec_hip_trajectory_metrics(optimization::SolverOptions().device, 1, offsets, (int64_t)n, eq.data(), gq.data(),
+                                    ep.data(), gp.data(), m, err_q.data(), s.rmse_d.data(), s.l1_d.data(), s.angle1.data(),
+                                    s.rt1.data(), PNEC_HIP_MEM_HOST, nullptr));
+  s.RPE_1 = m[0];
+  s.RPE_n = m[1];
+  s.L1RPE_1 = m[2];
+  s.L1RPE_n = m[3];
+  s.r_t = m[4];
+  return s;
+}
+
+}  // namespace odometry
 }  // namespace pnec

@@ -495,6 +495,27 @@ SE3d EMPoseEstimation(const bearingVectors_t &bvs1, const bearingVectors_t &bvs2
 
 }  // namespace rel_pose_estimation
 
+namespace odometry {
+
+// Trajectory evaluation on the device over HOST space (pnec_hip_trajectory_compose, pnec_hip_trajectory_metrics;
+// include/pnec_hip.h has the definitions), one sequence per call.
+// ComposeTrajectory is scripts/pnec/visual_odometry/io/evaluate_run.py:118-129: poses[i] = poses[i-1] * poses[i], the first
+// relative pose being a pose itself, then correction * pose for every pose.  A relative pose that is not finite is an
+// identity step: the pose before it is carried, and `valid` (when not NULL: one byte per pose) says 0 there.
+std::vector<SE3d> ComposeTrajectory(const std::vector<SE3d> &relative_poses, const SE3d &correction = SE3d(),
+                                    std::vector<uint8_t> *valid = nullptr);
+// The five numbers of the reference's metrics.yaml (scripts/pnec/metrics), in RADIANS, and what they are made of.  The
+// two vectors hold matched frames and have one size, else std::invalid_argument.  Fewer than two frames: NaN.
+// DEVIATION: an exact estimate scores 0 (the reference: NaN).
+struct TrajectoryScore {
+  double RPE_1, RPE_n, L1RPE_1, L1RPE_n, r_t;
+  std::vector<double> rmse_d, l1_d;   // [d]: the RMSE / the mean of the angle over all pairs at distance d; [0] is 0
+  std::vector<double> angle1, rt1;    // [k]: rotation / translation error of the step k-1 -> k; [0] is 0
+};
+TrajectoryScore TrajectoryMetrics(const std::vector<SE3d> &estimated, const std::vector<SE3d> &ground_truth);
+
+}  // namespace odometry
+
 // thrown when the HIP side reports an error (no device, bad argument, launch failure)
 struct HipError : std::runtime_error {
   int code;

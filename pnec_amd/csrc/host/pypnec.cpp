@@ -324,6 +324,72 @@ py::tuple undistort(arr points, arr K, std::vector<double> dist, py::object covs
   return py::make_tuple(out_pts, out_cov, out_status);
 }
 
+// poses [N,4,4] -> SE3d; a pose that is not finite stays so (ToPose would normalise a NaN rotation just the same)
+std::vector<pnec::SE3d> ToPoses(const arr &a, const char *name) {
+  if (a.ndim() != 3 || a.shape(1) != 4 || a.shape(2) != 4) throw std::invalid_argument(std::string(name) + " must be [N,4,4]");
+  std::vector<pnec::SE3d> out((size_t)a.shape(0));
+  auto r = a.unchecked<3>();
+  for (py::ssize_t i = 0; i < a.shape(0); ++i) {
+    pnec::Matrix3d R;
+    for (int row = 0; row < 3; ++row)
+      for (int col = 0; col < 3; ++col) R(row, col) = r(i, row, col);
+    out[(size_t)i] = pnec::SE3d(R, pnec::Vector3d(r(i, 0, 3), r(i, 1, 3), r(i, 2, 3)));
+  }
+  return out;
+}
+
+arr FromDoubles(const std::vector<double> &v) {
+  arr out((py::ssize_t)v.size());
+  auto w = out.mutable_unchecked<1>();
+  for (size_t i = 0; i < v.size(); ++i) w((py::ssize_t)i) = v[i];
+  return out;
+}
+
+// pnec::odometry::ComposeTrajectory: (poses [N,4,4], valid uint8 [N])
+py::tuple compose_trajectory(arr relative_poses, py::object correction) {
+  const std::vector<pnec::SE3d> rel = ToPoses(relative_poses, "relative_poses");
+  const pnec::SE3d left = correction.is_none() ? pnec::SE3d() : ToPose(correction.cast<arr>());
+  std::vector<pnec::SE3d> poses;
+  std::vector<uint8_t> valid;
+  {
+    py::gil_scoped_release release;
+    poses = pnec::odometry::ComposeTrajectory(rel, left, &valid);
+  }
+  const py::ssize_t n = (py::ssize_t)poses.size();
+  arr out({n, (py::ssize_t)4, (py::ssize_t)4});
+  py::array_t<uint8_t> out_valid(n);
+  auto w = out.mutable_unchecked<3>();
+  auto wv = out_valid.mutable_unchecked<1>();
+  for (py::ssize_t i = 0; i < n; ++i) {
+    const pnec::Matrix4d M = poses[(size_t)i].matrix();
+    for (int r = 0; r < 4; ++r)
+      for (int c = 0; c < 4; ++c) w(i, r, c) = M[4 * r + c];
+    wv(i) = valid[(size_t)i];
+  }
+  return py::make_tuple(out, out_valid);
+}
+
+// pnec::odometry::TrajectoryMetrics: a dict of the five metrics (radians) and the per-distance / per-step arrays
+py::dict trajectory_metrics(arr estimated, arr ground_truth) {
+  const std::vector<pnec::SE3d> est = ToPoses(estimated, "estimated"), gt = ToPoses(ground_truth, "ground_truth");
+  pnec::odometry::TrajectoryScore s;
+  {
+    py::gil_scoped_release release;
+    s = pnec::odometry::TrajectoryMetrics(est, gt);
+  }
+  py::dict d;
+  d["RPE_1"] = s.RPE_1;
+  d["RPE_n"] = s.RPE_n;
+  d["L1RPE_1"] = s.L1RPE_1;
+  d["L1RPE_n"] = s.L1RPE_n;
+  d["r_t"] = s.r_t;
+  d["rmse_d"] = FromDoubles(s.rmse_d);
+  d["l1_d"] = FromDoubles(s.l1_d);
+  d["angle1"] = FromDoubles(s.angle1);
+  d["rt1"] = FromDoubles(s.rt1);
+  return d;
+}
+
 // (scale, q25, q75, n_used, ratio [N]) of one frame against the previous one
 py::tuple relative_scale(arr bvs_prev1, arr bvs_prev2, arr pose_prev, arr bvs1, arr bvs2, arr pose,
                          const std::vector<int> &link, double min_parallax) {
@@ -668,6 +734,15 @@ PYBIND11_MODULE(pypnec, m) {
         "points [N,2] and optionally their covariances [N,3] (xx, xy, yy); returns (points, covs or None, status uint8 [N]). "
         "newton polishes the five fixed-point steps, propagate_cov carries the covariances through the map (neither is in the "
         "reference).  As in the reference, dist[0] == 0 returns the input -- include/pnec_hip.h pnec_hip_undistort_keypoints");
+  m.def("compose_trajectory", &compose_trajectory, py::arg("relative_poses"), py::arg("correction") = py::none(),
+        "pnec::odometry::ComposeTrajectory (device): the relative poses [N,4,4] of one run chained into absolute poses, the "
+        "first being a pose itself, with `correction` (4x4) as the left factor -- evaluate_run.py:118-129.  Returns (poses "
+        "[N,4,4], valid uint8 [N]); a relative pose that is not finite carries the pose before it and gets valid 0 -- "
+        "include/pnec_hip.h pnec_hip_trajectory_compose");
+  m.def("trajectory_metrics", &trajectory_metrics, py::arg("estimated"), py::arg("ground_truth"),
+        "pnec::odometry::TrajectoryMetrics (device): RPE_1, RPE_n, L1RPE_1, L1RPE_n, r_t in radians of the matched absolute "
+        "poses estimated / ground_truth [N,4,4], with rmse_d, l1_d, angle1, rt1 [N], as a dict; an exact estimate scores 0 "
+        "where the reference gives NaN -- include/pnec_hip.h pnec_hip_trajectory_metrics");
   m.def("relative_scale", &relative_scale, py::arg("bvs_prev1"), py::arg("bvs_prev2"), py::arg("pose_prev"),
         py::arg("bvs1"), py::arg("bvs2"), py::arg("pose"), py::arg("link"), py::arg("min_parallax") = 0.0,
         "pnec::common::RelativeScale (addition; device): (scale, q25, q75, n_used, ratio [N]) -- the baseline of `pose` in "

@@ -25,6 +25,7 @@
 #include "pnec_residuals.hpp"
 #include "pnec_eight_point.hpp"
 #include "pnec_undistort.hpp"
+#include "pnec_trajectory.hpp"
 #include "pnec_relative_scale.hpp"
 #include "pnec_tracks.hpp"
 #include "pnec_triangulate.hpp"
@@ -930,6 +931,101 @@ int pnec_hip_undistort_keypoints(int device, int64_t n_rows, const double *pts1,
   io.out(a.out_status[1], out_status2, n_rows);
   if (int rc = io.commit()) return rc;
   PNEC_HIP_TRY(launch_undistort_keypoints(a, stream));
+  return io.finish();
+}
+
+// trajectory evaluation: pnec_trajectory.hip.  No batch: HOST space stages in buffers that live for the call only.
+namespace {
+int check_trajectory_shape(const std::string &pre, int64_t n_seq, const int64_t *offsets, int64_t n_rows, int space) {
+  if (n_seq < 1 || n_seq > 0x7fffffffLL) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "n_seq must be 1 .. 2^31-1");
+  if (n_rows < 0 || n_rows > 0x7fffffffLL) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "n_rows must be 0 .. 2^31-1");
+  if (!offsets) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "offsets is NULL");
+  if (int rc = check_space(pre, space)) return rc;
+  if (space == PNEC_HIP_MEM_HOST) {
+    bool ok = offsets[0] == 0 && offsets[n_seq] <= n_rows;
+    for (int64_t f = 0; ok && f < n_seq; ++f) ok = offsets[f] <= offsets[f + 1];
+    if (!ok) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "offsets must be non-decreasing from 0 within n_rows");
+  }
+  return 0;
+}
+// an output that is also an input, or given twice
+bool trajectory_alias(std::initializer_list<const void *> outs, std::initializer_list<const void *> ins) {
+  for (const void *const *o = outs.begin(); o != outs.end(); ++o) {
+    if (!*o) continue;
+    for (const void *i : ins)
+      if (*o == i) return true;
+    for (const void *const *other = outs.begin(); other != o; ++other)
+      if (*o == *other) return true;
+  }
+  return false;
+}
+}  // namespace
+
+int pnec_hip_trajectory_compose(int device, int64_t n_seq, const int64_t *offsets, int64_t n_rows, const double *rel_q,
+                                const double *rel_t, const double *scale, const double *q0, const double *p0,
+                                double *out_q, double *out_p, uint8_t *out_valid, int space, void *stream_) {
+  const std::string pre = "trajectory_compose: ";
+  if (int rc = check_trajectory_shape(pre, n_seq, offsets, n_rows, space)) return rc;
+  if ((scale || p0) && !rel_t) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "scale and p0 need rel_t");
+  if ((rel_t != nullptr) != (out_p != nullptr))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "out_p is given exactly when rel_t is");
+  if (n_rows > 0 && (!rel_q || !out_q)) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "rel_q or out_q is NULL");
+  if (trajectory_alias({out_q, out_p, out_valid}, {offsets, rel_q, rel_t, scale, q0, p0}))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "an output is also an input or another output");
+  if (n_rows == 0) return 0;
+  hipStream_t stream = (hipStream_t)stream_;
+  CallArrays io(device, space, stream);
+  TrajectoryComposeArgs a{};
+  a.n_seq = n_seq;
+  a.n_rows = n_rows;
+  io.in(a.offsets, offsets, n_seq + 1);
+  io.in(a.rel_q, rel_q, 4 * n_rows);
+  io.in(a.rel_t, rel_t, 3 * n_rows);
+  io.in(a.scale, scale, n_rows);
+  io.in(a.q0, q0, 4 * n_seq);
+  io.in(a.p0, p0, 3 * n_seq);
+  // (HOST space: rows of no sequence are not written, so the caller's content travels up first)
+  io.out(a.out_q, out_q, 4 * n_rows, kPreload);
+  io.out(a.out_p, out_p, 3 * n_rows, kPreload);
+  io.out(a.out_valid, out_valid, n_rows, kPreload);
+  if (int rc = io.commit()) return rc;
+  PNEC_HIP_TRY(launch_trajectory_compose(a, stream));
+  return io.finish();
+}
+
+int pnec_hip_trajectory_metrics(int device, int64_t n_seq, const int64_t *offsets, int64_t n_rows, const double *est_q,
+                                const double *gt_q, const double *est_p, const double *gt_p, double *out_metrics,
+                                double *out_err_q, double *out_rmse_d, double *out_l1_d, double *out_angle1,
+                                double *out_rt1, int space, void *stream_) {
+  const std::string pre = "trajectory_metrics: ";
+  if (int rc = check_trajectory_shape(pre, n_seq, offsets, n_rows, space)) return rc;
+  if (!out_metrics) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "out_metrics is NULL");
+  if (n_rows > 0 && (!est_q || !gt_q || !out_err_q || !out_rmse_d || !out_l1_d))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "est_q, gt_q, out_err_q, out_rmse_d or out_l1_d is NULL");
+  if ((est_p != nullptr) != (gt_p != nullptr))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "est_p and gt_p are given or NULL together");
+  if (out_rt1 && !est_p) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "out_rt1 needs the positions");
+  if (trajectory_alias({out_metrics, out_err_q, out_rmse_d, out_l1_d, out_angle1, out_rt1},
+                       {offsets, est_q, gt_q, est_p, gt_p}))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "an output is also an input or another output");
+  hipStream_t stream = (hipStream_t)stream_;
+  CallArrays io(device, space, stream);
+  TrajectoryMetricsArgs a{};
+  a.n_seq = n_seq;
+  a.n_rows = n_rows;
+  io.in(a.offsets, offsets, n_seq + 1);
+  io.in(a.est_q, est_q, 4 * n_rows);
+  io.in(a.gt_q, gt_q, 4 * n_rows);
+  io.in(a.est_p, est_p, 3 * n_rows);
+  io.in(a.gt_p, gt_p, 3 * n_rows);
+  io.out(a.out_metrics, out_metrics, 5 * n_seq);
+  io.out(a.out_err_q, out_err_q, 4 * n_rows);
+  io.out(a.out_rmse_d, out_rmse_d, n_rows, kPreload);
+  io.out(a.out_l1_d, out_l1_d, n_rows, kPreload);
+  io.out(a.out_angle1, out_angle1, n_rows, kPreload);
+  io.out(a.out_rt1, out_rt1, n_rows, kPreload);
+  if (int rc = io.commit()) return rc;
+  PNEC_HIP_TRY(launch_trajectory_metrics(a, stream));
   return io.finish();
 }
 

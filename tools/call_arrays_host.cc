@@ -409,6 +409,36 @@ void image_lists(int64_t F, int64_t elem, int64_t n_points) {
       l.out(status1, N, 1);
       l.out(status2, N, 1);
     }, 20 * N + 9 + 2 * d8(N), 0);
+    // trajectory evaluation (no images, no batch): N rows in F sequences.  compose: the translation's arrays go with
+    // rel_t; rows of no sequence are not written, so the outputs travel up first
+    run(tag("trajectory_compose", {F, N}), [&](List &l) {
+      const bool rel_t = l.opt();
+      const bool scale = l.opt() && rel_t, q0 = l.opt(), p0 = l.opt() && rel_t, valid = l.opt();
+      l.in(true, F + 1, 8);      // offsets
+      l.in(true, 4 * N, 8);      // rel_q
+      l.in(rel_t, 3 * N, 8);
+      l.in(scale, N, 8);
+      l.in(q0, 4 * F, 8);
+      l.in(p0, 3 * F, 8);
+      l.out(true, 4 * N, 8, kPreload);
+      l.out(rel_t, 3 * N, 8, kPreload);
+      l.out(valid, N, 1, kPreload);
+    }, (F + 1) + 15 * N + 7 * F + d8(N), 0);
+    // metrics: the positions go together, out_rt1 needs them
+    run(tag("trajectory_metrics", {F, N}), [&](List &l) {
+      const bool positions = l.opt(), angle1 = l.opt(), rt1 = l.opt() && positions;
+      l.in(true, F + 1, 8);      // offsets
+      l.in(true, 4 * N, 8);      // est_q
+      l.in(true, 4 * N, 8);      // gt_q
+      l.in(positions, 3 * N, 8);
+      l.in(positions, 3 * N, 8);
+      l.out(true, 5 * F, 8);     // out_metrics
+      l.out(true, 4 * N, 8);     // out_err_q
+      l.out(true, N, 8, kPreload);
+      l.out(true, N, 8, kPreload);
+      l.out(angle1, N, 8, kPreload);
+      l.out(rt1, N, 8, kPreload);
+    }, (F + 1) + 22 * N + 5 * F, 0);
   }
 }
 
