@@ -32,6 +32,8 @@
  *    which TranslationalDifference(..., both_directions = true) hides)
  *   EMPoseEstimation(bvs1, bvs2, initial_pose, EIGHTPT, false) +     pnec_hip_eight_point
  *    PoseFromEssentialMatrix  essential_matrix_methods.cc:45-126, common.cc:262-457
+ *   opengv's fivept_nister / sevenpt [EXT] + PoseFromEssentialMatrix  pnec_hip_essential_minimal
+ *    (EMPoseEstimation(..., NISTER | SEVENPT, false))
  *   (no counterpart: the length of one pair's baseline in units of    pnec_hip_relative_scale
  *    the previous pair's, from the tracks both see)
  *   POpticalFlowPatch::setFromImage (Cov) + KLTPatchOpticalFlow's     pnec_hip_patch_covariance
@@ -683,6 +685,71 @@ typedef enum pnec_hip_ep_status {
 int pnec_hip_eight_point(pnec_hip_problem *p, int32_t flags, double *out_q, double *out_t, double *out_E,
                          double *out_singular, double *out_gap, double *out_quality, int32_t *out_choice,
                          int32_t *out_status, int space, void *stream);
+
+/* The minimal baselines: Nister's five-point and the seven-point solver, every solution and the chosen pose of every
+ * pair (added within ABI 8: a pure addition, PNEC_HIP_ABI_VERSION is unchanged).  They are the `Nister5pt` and `7pt`
+ * columns of the reference's `run_simulation -e`: EMPoseEstimation(..., NISTER | SEVENPT, ransac = false).  Steps 1-2
+ * restate opengv's fivept_nister and sevenpt from memory ([EXT], as eightpt was); the conventions and steps 3-4 are those
+ * of pnec_hip_eight_point.  Per pair with N correspondences:
+ *  1 Sums and eigenvectors.  G = A'A and its cyclic Jacobi exactly as in the eight-point (same order, same stop, same
+ *    skip rule).  The eigenvalues ascend as lambda_0..lambda_8 (the lowest index first among equal ones) with
+ *    eigenvectors v0..v8.  NISTER: W = v0, Z = v1, Y = v2, X = v3, gap = (lambda_4 - lambda_3) / lambda_8.  SEVENPT:
+ *    W = v0, X = v1, gap = (lambda_2 - lambda_1) / lambda_8.  W is the smallest eigenvalue's vector, as opengv's constant
+ *    term is the last column of V: for noise-free pairs with N above the minimal count the true E lies in the span of the
+ *    zero eigenvalues, and the parametrisation below would put it at infinity if W were the last vector of the basis.
+ *  2a NISTER.  E(x, y, z) = xX + yY + zZ + W.  The ten cubics det E = 0 and the nine entries of 2 E E'E - tr(E E') E = 0
+ *    give a 10 x 20 matrix in Nister's monomial order
+ *      x3 y3 x2y xy2 x2z x2 y2z y2 xyz xy | xz2 xz x yz2 yz y z3 z2 z 1
+ *    (rows: the nine entries row-major, then det E).  Gauss-Jordan with partial pivoting on the first ten columns, the
+ *    lowest row wins a tie.  The rows k = <x2z> - z <x2>, l = <y2z> - z <y2>, m = <xyz> - z <xy> form the 3 x 3 matrix
+ *    B(z) on (x, y, 1), entries of degree 3, 3, 4; p(z) = det B(z) has degree 10.  Its real roots come from a Sturm chain
+ *    (p, p', negated remainders, each scaled by its largest coefficient; a polynomial whose leading coefficients are
+ *    zero is taken at its actual degree): the roots lie within Cauchy's bound 1 + max |p_i / p_n|, their count is the
+ *    difference of the sign changes at the two ends, root i is isolated by bisection on the count, 64 halvings in the
+ *    integer order of the doubles.  x and y are the null vector of B(z): the cross product of two rows, the pair whose
+ *    product is longest.  Polish: two Gauss-Newton steps on the ten cubics in (x, y, z), evaluated from E directly -- the
+ *    derivative of det E along X is tr(adj(E) X), that of the nine entries 2 (X E'E + E X'E + E E'X) - 2 tr(E X') E -
+ *    tr(E E') X; the 3 x 3 normal equations are solved by the adjugate.
+ *  2b SEVENPT.  E(a) = W + aX, det E(a) = det W + tr(adj(W) X) a + tr(adj(X) W) a2 + det X a3; the real roots of the
+ *    cubic by the same Sturm chain, each polished by two Newton steps on det.  1 or 3 solutions; they are fundamental
+ *    matrices (s0 != s1), which the reference decomposes all the same.
+ *  2c Every solution: e of unit norm with the sign that makes its entry of largest magnitude positive; the solutions in
+ *    ascending order of e[0], then e[1], and so on (this does not depend on the basis of the null space, which is
+ *    arbitrary when N is the minimal count).  out_n_solutions is their count, at most PNEC_HIP_EM_MAX_SOLUTIONS.
+ *  3-4 Every solution i is decomposed as in step 3 of the eight-point into candidates j = 0..3; the quality of each over
+ *    the first K = min(S, N) correspondences, S = 8 for NISTER and 9 for SEVENPT (common.cc:352-373), or over all N with
+ *    PNEC_HIP_EM_QUALITY_ALL.  The lowest quality wins by strict < from 1e6 in the order (i, j); out_choice = 4 i + j.
+ *  5 Status, pnec_hip_em_status.  TOO_FEW: N < 5 (NISTER), N < 7 (SEVENPT).  NOT_FINITE: as in the eight-point.
+ *    NO_SOLUTION: no real root.  NO_CANDIDATE: no quality below 1e6.  A status other than OK writes NaN to q, t, E and
+ *    singular and -1 to out_choice; TOO_FEW and NOT_FINITE write NaN to the other double outputs too and NO_SOLUTION to
+ *    all but the gap; out_n_solutions is 0 for those three.
+ *
+ * Outputs for P pairs; every pointer may be NULL (not wanted), not all of them.
+ *   out_q [P,4] xyzw   out_t [P,3] unit   out_E [P,9] the chosen solution   out_singular [P,3] of the chosen solution
+ *   out_gap [P]   out_n_solutions int32 [P]   out_E_all [P,10,9], NaN beyond n_solutions
+ *   out_quality [P,10,4], NaN beyond   out_choice int32 [P] = 4 i + j, or -1   out_status int32 [P]
+ * A pair's bits depend on its own rows, on `algorithm` and on `flags` only (no atomics, fixed reduction order).
+ *
+ * All four problem modes, batches made by pnec_hip_problem_select(_view) and reshaped capacity batches included.  DEVICE
+ * space: nothing waits, nothing is allocated, the call is asynchronous on `stream`.  HOST space: the outputs are staged
+ * on the device (150 doubles and three ints per pair) and the call blocks.
+ * NULL problem, an `algorithm` other than the two, a flag bit other than PNEC_HIP_EM_QUALITY_ALL, all outputs NULL or a
+ * bad `space`: PNEC_HIP_ERR_INVALID_ARGUMENT before the handle is read or any device is touched. */
+#define PNEC_HIP_EM_NISTER 1
+#define PNEC_HIP_EM_SEVENPT 2
+#define PNEC_HIP_EM_MAX_SOLUTIONS 10
+#define PNEC_HIP_EM_QUALITY_ALL 1
+typedef enum pnec_hip_em_status {
+  PNEC_HIP_EM_OK = 0,
+  PNEC_HIP_EM_TOO_FEW = 1,
+  PNEC_HIP_EM_NOT_FINITE = 2,
+  PNEC_HIP_EM_NO_CANDIDATE = 3,
+  PNEC_HIP_EM_NO_SOLUTION = 4
+} pnec_hip_em_status;
+int pnec_hip_essential_minimal(pnec_hip_problem *p, int32_t algorithm, int32_t flags, double *out_q, double *out_t,
+                               double *out_E, double *out_singular, double *out_gap, int32_t *out_n_solutions,
+                               double *out_E_all, double *out_quality, int32_t *out_choice, int32_t *out_status,
+                               int space, void *stream);
 
 /* Relative scale between consecutive pairs from linked tracks (added within ABI 8: a pure addition,
  * PNEC_HIP_ABI_VERSION is unchanged).  Every pose carries t as a direction, so each pair is reconstructed with a

@@ -202,6 +202,23 @@ class EightPoint:
 
 
 @dataclass
+class MinimalPose:
+    """pnec_hip_essential_minimal's outputs (include/pnec_hip.h has the definitions): every solution of the five-point or
+    the seven-point solver and the pose chosen among their decompositions.  Per pair [P]; where `status` is not
+    capi.EM_OK, q, t, E and singular are NaN and choice -1."""
+    q: object            # [P,4] xyzw; R takes frame-2 vectors into frame 1
+    t: object            # [P,3] unit direction in frame 1
+    E: object            # [P,9] the chosen solution, row-major, unit norm, entry of largest magnitude positive
+    singular: object     # [P,3] singular values of the chosen solution, descending
+    gap: object          # [P] the eigenvalue gap above the null space, over lambda_8
+    n_solutions: object  # [P] int32, at most capi.EM_MAX_SOLUTIONS
+    E_all: object        # [P,10,9] every solution in lexicographic order, NaN beyond n_solutions
+    quality: object      # [P,10,4] of the four candidates of every solution; +inf where a term was not finite, NaN beyond
+    choice: object       # [P] int32, 4 * solution + candidate
+    status: object       # [P] int32, capi.EM_OK / EM_TOO_FEW / EM_NOT_FINITE / EM_NO_CANDIDATE / EM_NO_SOLUTION
+
+
+@dataclass
 class RelativeScale:
     """pnec_hip_relative_scale's outputs (include/pnec_hip.h has the definitions): the ratio of each pair's baseline to
     its previous pair's, from the tracks the two pairs share.  Per pair [P]: `scale` (the lower median of the used
@@ -904,6 +921,42 @@ class Batch:
         capi.check(self._lib.pnec_hip_eight_point(self._h, flags, p(q), p(t), p(E), p(sing), p(gap), p(qual), p(choice),
                                                   p(status), space, stream))
         return EightPoint(q, t, E, sing, gap, qual, choice, status)
+
+    def _essential_minimal(self, algorithm: int, quality: str, on_device) -> MinimalPose:
+        if quality not in ("sample", "all"):
+            raise ValueError('quality must be "sample" or "all"')
+        flags = capi.EM_QUALITY_ALL if quality == "all" else 0
+        if on_device is None:
+            on_device = bool(getattr(self, "_on_device", False))
+        P, S = self.n_pairs, capi.EM_MAX_SOLUTIONS
+        shapes = ((P, 4), (P, 3), (P, 9), (P, 3), (P,), (P,), (P, S, 9), (P, S, 4), (P,), (P,))
+        ints = (5, 8, 9)
+        if on_device:
+            import torch
+            out = [torch.empty(sh, dtype=torch.int32 if i in ints else torch.float64, device=f"cuda:{self.device}")
+                   for i, sh in enumerate(shapes)]
+            ptrs = [o.data_ptr() for o in out]
+            space, stream = capi.MEM_DEVICE, torch.cuda.current_stream(self.device).cuda_stream
+        else:
+            out = [np.empty(sh, dtype=np.int32 if i in ints else np.float64) for i, sh in enumerate(shapes)]
+            ptrs = [o.ctypes.data for o in out]
+            space, stream = capi.MEM_HOST, None
+        capi.check(self._lib.pnec_hip_essential_minimal(self._h, algorithm, flags, *ptrs, space, stream))
+        return MinimalPose(*out)
+
+    def five_point(self, quality: str = "sample", on_device: bool | None = None) -> MinimalPose:
+        """Nister's five-point solver (pnec_hip_essential_minimal with PNEC_HIP_EM_NISTER): up to ten essential matrices
+        per pair and the pose chosen among their forty decompositions, no start pose.  quality="sample" scores them on
+        the pair's first min(8, N) correspondences as the reference does, "all" on all of them.  Spaces as eight_point:
+        torch.cuda tensors, asynchronous on torch's current stream, from a batch filled or selected from them, numpy
+        arrays otherwise (`on_device` overrides); nothing is read back to size the outputs."""
+        return self._essential_minimal(capi.EM_NISTER, quality, on_device)
+
+    def seven_point(self, quality: str = "sample", on_device: bool | None = None) -> MinimalPose:
+        """The seven-point solver (PNEC_HIP_EM_SEVENPT): one or three fundamental matrices per pair from the cubic
+        det(W + aX) = 0 and the pose chosen among their decompositions; the sample is min(9, N).  Otherwise as
+        five_point."""
+        return self._essential_minimal(capi.EM_SEVENPT, quality, on_device)
 
     def relative_scale(self, prev, prev_pair, link, q, t, q_prev, t_prev, min_parallax: float = 0.0,
                        per_link: bool = True) -> RelativeScale:

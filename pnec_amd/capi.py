@@ -25,6 +25,13 @@ UNDISTORT_NEWTON, UNDISTORT_PROPAGATE_COV = 1, 2
 UNDISTORT_OK, UNDISTORT_OUTSIDE, UNDISTORT_NOT_CONVERGED, UNDISTORT_NOT_FINITE = 0, 1, 2, 3
 UNDISTORT_NAMES = {UNDISTORT_OK: "ok", UNDISTORT_OUTSIDE: "outside", UNDISTORT_NOT_CONVERGED: "not_converged",
                    UNDISTORT_NOT_FINITE: "not_finite"}
+# pnec_hip_essential_minimal: algorithms, flags, the bound on out_n_solutions and pnec_hip_em_status
+EM_NISTER, EM_SEVENPT = 1, 2
+EM_QUALITY_ALL = 1
+EM_MAX_SOLUTIONS = 10
+EM_OK, EM_TOO_FEW, EM_NOT_FINITE, EM_NO_CANDIDATE, EM_NO_SOLUTION = 0, 1, 2, 3, 4
+EM_NAMES = {EM_OK: "ok", EM_TOO_FEW: "too_few", EM_NOT_FINITE: "not_finite", EM_NO_CANDIDATE: "no_candidate",
+            EM_NO_SOLUTION: "no_solution"}
 # pnec_hip_eigensolver_scheme: which iteration stands in for opengv's eigenvalue minimisation (include/pnec_hip.h)
 ES_NEWTON, ES_DESCENT, ES_LM = 0, 1, 2
 # PNEC_HIP_RANSAC_* bits (pnec_hip_pipeline_options.ransac_flags, pnec_hip_problem_set_ransac_flags)
@@ -80,6 +87,7 @@ SYMBOLS = [
     "pnec_hip_residuals",
     "pnec_hip_triangulate",
     "pnec_hip_eight_point",
+    "pnec_hip_essential_minimal",
     "pnec_hip_relative_scale",
     "pnec_hip_patch_covariance",
     "pnec_hip_image_pyramid_level",
@@ -244,6 +252,7 @@ def lib() -> C.CDLL:
                                      C.c_int, _vp]
     L.pnec_hip_triangulate.argtypes = [_vp, _vp, _vp, C.c_int32, C.c_int32] + [_vp] * 11 + [C.c_int, _vp]
     L.pnec_hip_eight_point.argtypes = [_vp, C.c_int32] + [_vp] * 8 + [C.c_int, _vp]
+    L.pnec_hip_essential_minimal.argtypes = [_vp, C.c_int32, C.c_int32] + [_vp] * 10 + [C.c_int, _vp]
     L.pnec_hip_undistort_keypoints.argtypes = [C.c_int, C.c_int64] + [_vp] * 5 + [C.c_int32, C.c_int32, C.c_uint32] + \
         [_vp] * 6 + [C.c_int, _vp]
     L.pnec_hip_trajectory_compose.argtypes = [C.c_int, C.c_int64, _vp, C.c_int64] + [_vp] * 8 + [C.c_int, _vp]

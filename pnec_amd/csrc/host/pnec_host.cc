@@ -1272,6 +1272,23 @@ SE3d EMPoseEstimation(const bearingVectors_t &bvs1, const bearingVectors_t &bvs2
   return SE3d(Quaterniond(q[3], q[0], q[1], q[2]).toRotationMatrix(), Vector3d(t[0], t[1], t[2]) * singular[0]);
 }
 
+SE3d MinimalEMPoseEstimation(const bearingVectors_t &bvs1, const bearingVectors_t &bvs2, const SE3d &initial_pose,
+                             algorithm_t algorithm) {
+  if (algorithm != NISTER && algorithm != SEVENPT)
+    throw std::invalid_argument("MinimalEMPoseEstimation: the algorithm is neither NISTER nor SEVENPT");
+  if (bvs1.size() != bvs2.size()) throw std::invalid_argument("bvs1 and bvs2 differ in size");
+  if (bvs1.empty()) return initial_pose;
+  Problem batch(optimization::SolverOptions().device, PNEC_HIP_MODE_NEC, {0, (int64_t)bvs1.size()});
+  Check(pnec_hip_problem_fill(batch.p, 0, 1, bvs1[0].data(), bvs2[0].data(), nullptr, nullptr, PNEC_HIP_MEM_HOST, nullptr));
+  double q[4], t[3], singular[3];
+  int32_t status = PNEC_HIP_EM_OK;
+  Check(pnec_hip_essential_minimal(batch.p, algorithm == NISTER ? PNEC_HIP_EM_NISTER : PNEC_HIP_EM_SEVENPT, 0, q, t,
+                                   nullptr, singular, nullptr, nullptr, nullptr, nullptr, nullptr, &status,
+                                   PNEC_HIP_MEM_HOST, nullptr));
+  if (status != PNEC_HIP_EM_OK) return initial_pose;
+  return SE3d(Quaterniond(q[3], q[0], q[1], q[2]).toRotationMatrix(), Vector3d(t[0], t[1], t[2]) * singular[0]);
+}
+
 }  // namespace rel_pose_estimation
 
 namespace odometry {

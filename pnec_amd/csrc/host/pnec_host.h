@@ -492,6 +492,12 @@ enum algorithm_t { STEWENIUS = 0, NISTER = 1, SEVENPT = 2, EIGHTPT = 3 };
 // opengv's CentralRelativePoseSacProblem) throws std::invalid_argument naming what is not built.
 SE3d EMPoseEstimation(const bearingVectors_t &bvs1, const bearingVectors_t &bvs2, const SE3d &initial_pose,
                       algorithm_t algorithm, bool ransac = true);
+// The minimal baselines without RANSAC, under a name of their own (EMPoseEstimation keeps throwing for them): NISTER is
+// opengv's fivept_nister, SEVENPT its sevenpt, each followed by PoseFromEssentialMatrix over every solution, on the
+// device -- pnec_hip_essential_minimal.  Rotation, translation (of length s0 of the chosen solution) and the return of
+// initial_pose where the call finds no pose as EMPoseEstimation; any other algorithm throws std::invalid_argument.
+SE3d MinimalEMPoseEstimation(const bearingVectors_t &bvs1, const bearingVectors_t &bvs2, const SE3d &initial_pose,
+                             algorithm_t algorithm);
 
 }  // namespace rel_pose_estimation
 

@@ -390,6 +390,19 @@ py::dict trajectory_metrics(arr estimated, arr ground_truth) {
   return d;
 }
 
+// MinimalEMPoseEstimation(bvs1, bvs2, identity, NISTER | SEVENPT): 4x4, the translation of length s0
+arr minimal_pose(arr bvs1, arr bvs2, pnec::rel_pose_estimation::algorithm_t algorithm) {
+  const auto b1 = ToBearings(bvs1, "bvs_1"), b2 = ToBearings(bvs2, "bvs_2");
+  pnec::SE3d result;
+  {
+    py::gil_scoped_release release;
+    result = pnec::rel_pose_estimation::MinimalEMPoseEstimation(b1, b2, pnec::SE3d(), algorithm);
+  }
+  return FromPose(result);
+}
+arr five_point(arr bvs1, arr bvs2) { return minimal_pose(bvs1, bvs2, pnec::rel_pose_estimation::NISTER); }
+arr seven_point(arr bvs1, arr bvs2) { return minimal_pose(bvs1, bvs2, pnec::rel_pose_estimation::SEVENPT); }
+
 // (scale, q25, q75, n_used, ratio [N]) of one frame against the previous one
 py::tuple relative_scale(arr bvs_prev1, arr bvs_prev2, arr pose_prev, arr bvs1, arr bvs2, arr pose,
                          const std::vector<int> &link, double min_parallax) {
@@ -743,6 +756,13 @@ PYBIND11_MODULE(pypnec, m) {
         "pnec::odometry::TrajectoryMetrics (device): RPE_1, RPE_n, L1RPE_1, L1RPE_n, r_t in radians of the matched absolute "
         "poses estimated / ground_truth [N,4,4], with rmse_d, l1_d, angle1, rt1 [N], as a dict; an exact estimate scores 0 "
         "where the reference gives NaN -- include/pnec_hip.h pnec_hip_trajectory_metrics");
+  m.def("five_point", &five_point, py::arg("bvs1"), py::arg("bvs2"),
+        "pnec::rel_pose_estimation::MinimalEMPoseEstimation(bvs1, bvs2, identity, NISTER) (device): the 4x4 pose of "
+        "Nister's five-point solver, translation of length s0; the identity when the pair gives no pose -- "
+        "include/pnec_hip.h pnec_hip_essential_minimal");
+  m.def("seven_point", &seven_point, py::arg("bvs1"), py::arg("bvs2"),
+        "pnec::rel_pose_estimation::MinimalEMPoseEstimation(bvs1, bvs2, identity, SEVENPT) (device): the same of the "
+        "seven-point solver");
   m.def("relative_scale", &relative_scale, py::arg("bvs_prev1"), py::arg("bvs_prev2"), py::arg("pose_prev"),
         py::arg("bvs1"), py::arg("bvs2"), py::arg("pose"), py::arg("link"), py::arg("min_parallax") = 0.0,
         "pnec::common::RelativeScale (addition; device): (scale, q25, q75, n_used, ratio [N]) -- the baseline of `pose` in "

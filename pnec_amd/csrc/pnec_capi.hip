@@ -24,6 +24,7 @@
 #include "pnec_pose_cov.hpp"
 #include "pnec_residuals.hpp"
 #include "pnec_eight_point.hpp"
+#include "pnec_essential_minimal.hpp"
 #include "pnec_undistort.hpp"
 #include "pnec_trajectory.hpp"
 #include "pnec_relative_scale.hpp"
@@ -1438,6 +1439,45 @@ int pnec_hip_eight_point(pnec_hip_problem *p, int32_t flags, double *out_q, doub
   io.out(a.out_status, out_status, P);
   if (int rc = io.commit()) return rc;
   PNEC_HIP_TRY(launch_eight_point(P, a, stream));
+  return io.finish();
+}
+
+// every solution of the five-point / seven-point solver and the chosen pose of every pair: pnec_essential_minimal.hip
+int pnec_hip_essential_minimal(pnec_hip_problem *p, int32_t algorithm, int32_t flags, double *out_q, double *out_t,
+                               double *out_E, double *out_singular, double *out_gap, int32_t *out_n_solutions,
+                               double *out_E_all, double *out_quality, int32_t *out_choice, int32_t *out_status,
+                               int space, void *stream_) {
+  if (!p) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "essential_minimal: problem is NULL");
+  if (algorithm != PNEC_HIP_EM_NISTER && algorithm != PNEC_HIP_EM_SEVENPT)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "essential_minimal: algorithm is neither NISTER nor SEVENPT");
+  if (flags & ~PNEC_HIP_EM_QUALITY_ALL) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "essential_minimal: unknown bit in flags");
+  if (!out_q && !out_t && !out_E && !out_singular && !out_gap && !out_n_solutions && !out_E_all && !out_quality &&
+      !out_choice && !out_status)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "essential_minimal: every output is NULL");
+  if (int rc = check_space("essential_minimal: ", space)) return rc;
+  const int64_t P = p->n_pairs;
+  if (P > 0x7fffffffLL) return fail(PNEC_HIP_ERR_UNSUPPORTED, "more than 2^31-1 pairs in one call");
+  if (P == 0) return 0;
+  hipStream_t stream = (hipStream_t)stream_;
+  CallArrays io(p, space, stream);
+  EssentialMinimalArgs a;
+  a.data = p->d_data;
+  a.block_offset = p->d_block_offset;
+  a.count = p->d_count;
+  a.algorithm = algorithm;
+  a.flags = flags;
+  io.out(a.out_q, out_q, 4 * P);
+  io.out(a.out_t, out_t, 3 * P);
+  io.out(a.out_E, out_E, 9 * P);
+  io.out(a.out_singular, out_singular, 3 * P);
+  io.out(a.out_gap, out_gap, P);
+  io.out(a.out_n_solutions, out_n_solutions, P);
+  io.out(a.out_E_all, out_E_all, 9 * PNEC_HIP_EM_MAX_SOLUTIONS * P);
+  io.out(a.out_quality, out_quality, 4 * PNEC_HIP_EM_MAX_SOLUTIONS * P);
+  io.out(a.out_choice, out_choice, P);
+  io.out(a.out_status, out_status, P);
+  if (int rc = io.commit()) return rc;
+  PNEC_HIP_TRY(launch_essential_minimal(P, a, stream));
   return io.finish();
 }
 

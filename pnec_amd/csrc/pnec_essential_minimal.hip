@@ -1,0 +1,1000 @@
+// pnec_essential_minimal.hip -- the minimal essential-matrix baselines: Nister's five-point and the seven-point solver,
+// every solution and the chosen pose of every pair in one pass.  A translation unit of its own.  include/pnec_hip.h has
+// the definitions; this file says how the wavefront is used.
+//
+// One block of one wavefront per pair.  The phases, every branch that holds a barrier wave-uniform:
+//   sums, Jacobi   the eight-point kernel's two phases, statement for statement (pnec_eight_point.hip; this unit carries
+//                  its own copy, so that kernel's instruction stream is untouched): 45 sums by the fixed butterfly, the
+//                  9x9 and its eigenvectors as an 18x9 array in LDS with rows on lanes.
+//   null space     the diagonal is ranked in registers (72 comparisons, the lowest index wins a tie); the four (two)
+//                  vectors of the smallest eigenvalues are read from LDS at the ranked columns.
+//   cubics         NISTER.  Every lane forms E E' (six quadratic polynomials) from the basis; lane r < 9 takes row r / 3
+//                  of 2 E E' - tr(E E') and column r % 3 of E by selects and multiplies out its own cubic, lane 9 holds
+//                  det E: one row of the 10 x 20 matrix per lane, all indices static.  The rows pass through LDS once
+//                  and come back transposed: lane c < 20 holds column c in ten registers.
+//   elimination    Gauss-Jordan on columns in registers: the pivot column is broadcast by v_readlane (the pivot step is
+//                  unrolled, so its lane is a constant), a row exchange is a wave-uniform select.  No LDS.
+//   p(z)           the six rows that make B(z) are broadcast (60 values); det B(z) is multiplied out by every lane.
+//                  SEVENPT has its cubic here instead and shares everything below.
+//   Sturm chain    coefficient j on lane j: a remainder step is one broadcast of the leading coefficients, one division,
+//                  one lane shift and one FMA per lane, at the polynomials' actual degrees (wave-uniform trip counts).
+//                  The chain (66 coefficients at most) goes through LDS into registers of every lane.
+//   roots          lane i bisects for the i-th real root on the count of sign changes, in the integer order of the
+//                  doubles (64 halvings reach one ulp from any bound); 66 FMAs per count, no memory.
+//   per solution   lane i: null vector of B(z), two Gauss-Newton steps on the ten cubics (one Newton step pair on det for
+//                  SEVENPT), norm and sign, rank in the lexicographic order by ten broadcasts, exchange through LDS, then
+//                  the eight-point's 3x3 decomposition.  A lane that has converged is frozen while others sweep on; the
+//                  sweep loops end by ballot.
+//   qualities      lane 4 i + j reads candidate j of solution i from LDS and sums its terms over the sample (or over all
+//                  correspondences); every lane reads the same bearing (one broadcast load per plane).
+//   choice         a butterfly minimum and a ballot: the lowest lane that holds the minimum.
+// Lane 0 stores the pair's outputs, lanes < 10 / < 40 their rows of out_E_all / out_quality, with plain vector stores.
+// No atomics; a pair's bits depend on its own rows, on `algorithm` and on `flags` only.
+#include <hip/hip_runtime.h>
+
+#include "pnec_device.hpp"
+#include "pnec_eight_point.hpp"         // the Jacobi constants and the start quality, shared with the eight-point
+#include "pnec_essential_minimal.hpp"
+#include "pnec_triangulate.hpp"         // tri_depths: the midpoint system
+
+namespace pnec_hip {
+
+namespace {
+
+constexpr int kEmDim = 9;
+constexpr int kEmRows = 2 * kEmDim;
+constexpr int kEmCand = 24;   // doubles per solution in LDS: Ra, Rb, ta, singular values
+
+// ---- the eight-point kernel's helpers (copies: see the head of this file) --------------------------------------------
+template <int P, int Q>
+__device__ __forceinline__ void em_rotate3(double (&A)[9], double (&V)[9]) {
+  constexpr int R = 3 - P - Q;
+  const double apq = A[3 * P + Q];
+  const bool nz = apq != 0.0;
+  const double theta = (A[4 * Q] - A[4 * P]) / (2.0 * (nz ? apq : 1.0));
+  double t = copysign(1.0, theta) / (fabs(theta) + sqrt(__builtin_fma(theta, theta, 1.0)));
+  t = nz ? t : 0.0;
+  const double c = 1.0 / sqrt(__builtin_fma(t, t, 1.0)), s = t * c;
+  A[4 * P] = __builtin_fma(-t, apq, A[4 * P]);
+  A[4 * Q] = __builtin_fma(t, apq, A[4 * Q]);
+  A[3 * P + Q] = A[3 * Q + P] = 0.0;
+  const double arp = A[3 * R + P], arq = A[3 * R + Q];
+  A[3 * R + P] = A[3 * P + R] = c * arp - s * arq;
+  A[3 * R + Q] = A[3 * Q + R] = s * arp + c * arq;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double vp = V[3 * k + P], vq = V[3 * k + Q];
+    V[3 * k + P] = c * vp - s * vq;
+    V[3 * k + Q] = s * vp + c * vq;
+  }
+}
+
+__device__ __forceinline__ double em_pick3(const double (&x)[9], int row, int col) {
+  const double a = x[3 * row], b = x[3 * row + 1], c = x[3 * row + 2];
+  return col == 0 ? a : (col == 1 ? b : c);
+}
+
+__device__ __forceinline__ void em_cross(const double (&a)[3], const double (&b)[3], double (&c)[3]) {
+  c[0] = a[1] * b[2] - a[2] * b[1];
+  c[1] = a[2] * b[0] - a[0] * b[2];
+  c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+__device__ __forceinline__ void em_normalise(double (&v)[3]) {
+  const double inv = 1.0 / sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+  v[0] *= inv;
+  v[1] *= inv;
+  v[2] *= inv;
+}
+
+template <int N>
+__device__ __forceinline__ double em_sign(const double (&v)[N]) {
+  double big = v[0];
+#pragma unroll
+  for (int k = 1; k < N; ++k) big = fabs(v[k]) > fabs(big) ? v[k] : big;
+  return big < 0.0 ? -1.0 : 1.0;
+}
+
+__device__ __forceinline__ double em_det3(const double (&R)[9]) {
+  return R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+}
+
+__device__ __forceinline__ double em_term(const double (&f)[6], const double (&R)[9], const double (&t)[3]) {
+  TriSystem ts;
+  tri_depths(f, R, t, ts);
+  const double px = 0.5 * __builtin_fma(ts.depth1, f[0], __builtin_fma(ts.depth2, ts.ux, t[0]));
+  const double py = 0.5 * __builtin_fma(ts.depth1, f[1], __builtin_fma(ts.depth2, ts.uy, t[1]));
+  const double pz = 0.5 * __builtin_fma(ts.depth1, f[2], __builtin_fma(ts.depth2, ts.uz, t[2]));
+  const double n1 = 1.0 / sqrt(px * px + py * py + pz * pz);
+  const double wx = px - t[0], wy = py - t[1], wz = pz - t[2];
+  const double x2 = R[0] * wx + R[3] * wy + R[6] * wz;
+  const double y2 = R[1] * wx + R[4] * wy + R[7] * wz;
+  const double z2 = R[2] * wx + R[5] * wy + R[8] * wz;
+  const double n2 = 1.0 / sqrt(x2 * x2 + y2 * y2 + z2 * z2);
+  const double e1 = 1.0 - (f[0] * px + f[1] * py + f[2] * pz) * n1;
+  const double e2 = 1.0 - (f[3] * x2 + f[4] * y2 + f[5] * z2) * n2;
+  return e1 + e2;
+}
+
+__device__ __forceinline__ void em_quat(const double (&R)[9], double (&q)[4]) {
+  const double tr = R[0] + R[4] + R[8];
+  double x, y, z, w;
+  if (tr > 0.0) {
+    w = 1.0 + tr;
+    x = R[7] - R[5];
+    y = R[2] - R[6];
+    z = R[3] - R[1];
+  } else if (R[0] >= R[4] && R[0] >= R[8]) {
+    x = 1.0 + R[0] - R[4] - R[8];
+    y = R[1] + R[3];
+    z = R[2] + R[6];
+    w = R[7] - R[5];
+  } else if (R[4] >= R[8]) {
+    x = R[1] + R[3];
+    y = 1.0 - R[0] + R[4] - R[8];
+    z = R[5] + R[7];
+    w = R[2] - R[6];
+  } else {
+    x = R[2] + R[6];
+    y = R[5] + R[7];
+    z = 1.0 - R[0] - R[4] + R[8];
+    w = R[3] - R[1];
+  }
+  const double inv = 1.0 / sqrt(x * x + y * y + z * z + w * w);
+  q[0] = x * inv;
+  q[1] = y * inv;
+  q[2] = z * inv;
+  q[3] = w * inv;
+}
+
+// ---- lanes ---------------------------------------------------------------------------------------------------------------
+// the value lane `src` holds, src wave-uniform (a constant where the caller's loop is unrolled)
+__device__ __forceinline__ double em_lane(double x, int src) {
+  const int lo = __builtin_amdgcn_readlane(__double2loint(x), src);
+  const int hi = __builtin_amdgcn_readlane(__double2hiint(x), src);
+  return make_double(hi, lo);
+}
+// the value of any lane, src per lane
+__device__ __forceinline__ double em_gather(double x, int src) {
+  const int lo = __builtin_amdgcn_ds_bpermute(src << 2, __double2loint(x));
+  const int hi = __builtin_amdgcn_ds_bpermute(src << 2, __double2hiint(x));
+  return make_double(hi, lo);
+}
+__device__ __forceinline__ double em_wave_max(double x) {
+#pragma unroll
+  for (int m = 1; m < kWave; m <<= 1) x = fmax(x, em_gather(x, (int)threadIdx.x ^ m));
+  return x;
+}
+__device__ __forceinline__ double em_wave_min(double x) {
+#pragma unroll
+  for (int m = 1; m < kWave; m <<= 1) x = fmin(x, em_gather(x, (int)threadIdx.x ^ m));
+  return x;
+}
+
+// ---- polynomials in (x, y, z) ------------------------------------------------------------------------------------------
+// linear: x y z 1.  quadratic: the products (a, b), a <= b, of the linear monomials in the order of em_q2.  cubic:
+// Nister's order  x3 y3 x2y xy2 x2z x2 y2z y2 xyz xy | xz2 xz x yz2 yz y z3 z2 z 1.
+constexpr int em_q2(int a, int b) { return a <= b ? a * 4 - a * (a - 1) / 2 + (b - a) : em_q2(b, a); }
+constexpr int em_qa(int i) { return i < 4 ? 0 : (i < 7 ? 1 : (i < 9 ? 2 : 3)); }
+constexpr int em_qb(int i) { return i < 4 ? i : (i < 7 ? i - 3 : (i < 9 ? i - 5 : 3)); }
+constexpr int em_cnt(int v, int a, int b, int c) { return (a == v) + (b == v) + (c == v); }
+constexpr int em_c3e(int ex, int ey, int ez) {
+  return ex == 3 ? 0 : ey == 3 ? 1 : (ex == 2 && ey == 1) ? 2 : (ex == 1 && ey == 2) ? 3 : (ex == 2 && ez == 1) ? 4
+       : ex == 2 ? 5 : (ey == 2 && ez == 1) ? 6 : ey == 2 ? 7 : (ex == 1 && ey == 1 && ez == 1) ? 8
+       : (ex == 1 && ey == 1) ? 9 : (ex == 1 && ez == 2) ? 10 : (ex == 1 && ez == 1) ? 11 : ex == 1 ? 12
+       : (ey == 1 && ez == 2) ? 13 : (ey == 1 && ez == 1) ? 14 : ey == 1 ? 15 : ez == 3 ? 16 : ez == 2 ? 17 : ez == 1 ? 18 : 19;
+}
+constexpr int em_c3(int q, int l) {
+  return em_c3e(em_cnt(0, em_qa(q), em_qb(q), l), em_cnt(1, em_qa(q), em_qb(q), l), em_cnt(2, em_qa(q), em_qb(q), l));
+}
+
+// q += s a b
+__device__ __forceinline__ void em_fma_ll(const double (&a)[4], const double (&b)[4], double s, double (&q)[10]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) q[em_q2(i, j)] = __builtin_fma(s * a[i], b[j], q[em_q2(i, j)]);
+}
+// c += q l
+__device__ __forceinline__ void em_fma_ql(const double (&q)[10], const double (&l)[4], double (&c)[20]) {
+#pragma unroll
+  for (int i = 0; i < 10; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) c[em_c3(i, j)] = __builtin_fma(q[i], l[j], c[em_c3(i, j)]);
+}
+// c += s a b, polynomials in z with ascending coefficients
+template <int NA, int NB>
+__device__ __forceinline__ void em_fma_zz(const double (&a)[NA], const double (&b)[NB], double s, double (&c)[NA + NB - 1]) {
+#pragma unroll
+  for (int i = 0; i < NA; ++i)
+#pragma unroll
+    for (int j = 0; j < NB; ++j) c[i + j] = __builtin_fma(s * a[i], b[j], c[i + j]);
+}
+template <int N>
+__device__ __forceinline__ double em_horner(const double (&c)[N], double z) {
+  double v = c[N - 1];
+#pragma unroll
+  for (int k = N - 2; k >= 0; --k) v = __builtin_fma(v, z, c[k]);
+  return v;
+}
+
+// the doubles in their order as integers (-0 and +0 share a key)
+__device__ __forceinline__ long long em_key(double x) {
+  const long long b = __double_as_longlong(x);
+  return b < 0 ? -(b & 0x7fffffffffffffffLL) : b;
+}
+__device__ __forceinline__ double em_unkey(long long k) {
+  return __longlong_as_double(k < 0 ? ((-k) | (long long)0x8000000000000000ULL) : k);
+}
+
+// 3x3 row-major
+__device__ __forceinline__ void em_mul33(const double (&A)[9], const double (&B)[9], double (&C)[9]) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) C[3 * i + j] = A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j] + A[3 * i + 2] * B[6 + j];
+}
+// A B'
+__device__ __forceinline__ void em_mul33_nt(const double (&A)[9], const double (&B)[9], double (&C)[9]) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) C[3 * i + j] = A[3 * i] * B[3 * j] + A[3 * i + 1] * B[3 * j + 1] + A[3 * i + 2] * B[3 * j + 2];
+}
+// A' B
+__device__ __forceinline__ void em_mul33_tn(const double (&A)[9], const double (&B)[9], double (&C)[9]) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) C[3 * i + j] = A[i] * B[j] + A[3 + i] * B[3 + j] + A[6 + i] * B[6 + j];
+}
+// the rows of E crossed: c[k] is column k of adj(E), so d det(E + s D) / ds = sum_k c[k] . row k of D
+__device__ __forceinline__ void em_cofactors(const double (&E)[9], double (&c)[9]) {
+  const double r0[3] = {E[0], E[1], E[2]}, r1[3] = {E[3], E[4], E[5]}, r2[3] = {E[6], E[7], E[8]};
+  double c0[3], c1[3], c2[3];
+  em_cross(r1, r2, c0);
+  em_cross(r2, r0, c1);
+  em_cross(r0, r1, c2);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    c[k] = c0[k];
+    c[3 + k] = c1[k];
+    c[6 + k] = c2[k];
+  }
+}
+__device__ __forceinline__ double em_dot9(const double (&a)[9], const double (&b)[9]) {
+  double s = 0.0;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) s = __builtin_fma(a[k], b[k], s);
+  return s;
+}
+
+// the ten constraints at E: r[0] = det E, r[1..9] = 2 E E'E - tr(E E') E; G = E E', H = E'E, cof, tr for the derivative
+struct EmPoint {
+  double G[9], H[9], cof[9], tr;
+};
+__device__ __forceinline__ void em_residual(const double (&E)[9], EmPoint &w, double (&r)[10]) {
+  em_mul33_nt(E, E, w.G);
+  em_mul33_tn(E, E, w.H);
+  em_cofactors(E, w.cof);
+  w.tr = w.G[0] + w.G[4] + w.G[8];
+  r[0] = E[0] * w.cof[0] + E[1] * w.cof[1] + E[2] * w.cof[2];
+  double GE[9];
+  em_mul33(w.G, E, GE);
+#pragma unroll
+  for (int k = 0; k < 9; ++k) r[1 + k] = __builtin_fma(2.0, GE[k], -w.tr * E[k]);
+}
+// the derivative of the ten along D: tr(adj(E) D) and 2 (D E'E + E D'E + E E'D) - 2 tr(E D') E - tr(E E') D
+__device__ __forceinline__ void em_derivative(const double (&E)[9], const EmPoint &w, const double (&D)[9], double (&j)[10]) {
+  j[0] = em_dot9(w.cof, D);
+  double DH[9], P[9], PE[9], GD[9];
+  em_mul33(D, w.H, DH);
+  em_mul33_nt(E, D, P);
+  em_mul33(P, E, PE);
+  em_mul33(w.G, D, GD);
+  const double ted = em_dot9(E, D);
+#pragma unroll
+  for (int k = 0; k < 9; ++k) j[1 + k] = 2.0 * (DH[k] + PE[k] + GD[k]) - 2.0 * ted * E[k] - w.tr * D[k];
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(kWave) void essential_minimal_kernel(const EssentialMinimalArgs a) {
+  __shared__ double M[kEmRows * kEmDim];          // rows 0..8: A'A, rows 9..17: its eigenvectors as columns
+  __shared__ double T[10 * 20];                   // the ten cubics, row-major
+  __shared__ double S[11 * 11];                   // the Sturm chain, polynomial k at S[11 k]
+  __shared__ double Es[kEmMaxSolutions * 9];      // the solutions in their order
+  __shared__ double C[kEmMaxSolutions * kEmCand]; // the candidates of every solution
+
+  const int64_t pair = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int n = to_sgpr(a.count[pair]);
+  const bool nister = a.algorithm == PNEC_HIP_EM_NISTER;
+  const int64_t stride = ((int64_t)n + kWave - 1) & ~(int64_t)(kWave - 1);
+  const double *base = a.data + a.block_offset[pair];
+  auto load6 = [&](int i, double (&f)[6]) {
+#pragma unroll
+    for (int c = 0; c < 6; ++c) f[c] = base[(int64_t)c * stride + i];
+  };
+
+  const double nan = __builtin_nan("");
+  int status = n < (nister ? 5 : 7) ? PNEC_HIP_EM_TOO_FEW : PNEC_HIP_EM_OK;
+  int choice = -1, n_sol = 0;
+  double gap = nan, quality = nan;
+  double e[9];                                   // lane i: solution i
+#pragma unroll
+  for (int k = 0; k < 9; ++k) e[k] = nan;
+
+  double trace = 0.0;
+  if (status == PNEC_HIP_EM_OK) {
+    // ---- the 45 sums (pnec_eight_point.hip) ------------------------------------------------------------------------------
+    double acc[45];
+#pragma unroll
+    for (int k = 0; k < 45; ++k) acc[k] = 0.0;
+#pragma unroll 1
+    for (int i0 = 0; i0 < n; i0 += kWave) {
+      const int i = i0 + lane;
+      const bool in = i < n;
+      double f[6];
+      load6(in ? i : n - 1, f);
+      double r[9];
+#pragma unroll
+      for (int k = 0; k < 9; ++k) r[k] = in ? f[k / 3] * f[3 + k % 3] : 0.0;
+      int k = 0;
+#pragma unroll
+      for (int x = 0; x < 9; ++x)
+#pragma unroll
+        for (int y = x; y < 9; ++y) {
+          acc[k] = __builtin_fma(r[x], r[y], acc[k]);
+          ++k;
+        }
+    }
+    {
+      int k = 0;
+#pragma unroll
+      for (int x = 0; x < 9; ++x)
+#pragma unroll
+        for (int y = x; y < 9; ++y) {
+          const double s = wave_allreduce_sum(acc[k]);
+          ++k;
+          if (x == y) trace += s;
+          if (lane == 0) {
+            M[x * kEmDim + y] = s;
+            M[y * kEmDim + x] = s;
+          }
+        }
+    }
+    for (int x = lane; x < kEmDim * kEmDim; x += kWave) M[kEmDim * kEmDim + x] = (x / kEmDim == x % kEmDim) ? 1.0 : 0.0;
+    trace = to_sgpr(trace);
+    if (!finite_d(trace)) status = PNEC_HIP_EM_NOT_FINITE;
+  }
+  __syncthreads();
+
+  if (status == PNEC_HIP_EM_OK) {
+    // ---- cyclic Jacobi on the 9x9 (pnec_eight_point.hip) -----------------------------------------------------------------
+    const double off_limit = (kEpOffTol * trace) * (kEpOffTol * trace), skip_limit = kEpSkipTol * trace;
+    const int row = lane < kEmRows ? lane : 0;
+    const bool upper = lane < kEmDim, active = lane < kEmRows;
+#pragma unroll 1
+    for (int sweep = 0; sweep < kEpMaxSweeps; ++sweep) {
+      double o = 0.0;
+#pragma unroll
+      for (int j = 0; j < kEmDim; ++j) {
+        const double v = M[row * kEmDim + j];
+        o = __builtin_fma((upper && j != lane) ? v : 0.0, v, o);
+      }
+      const double off2 = to_sgpr(wave_allreduce_sum(o));
+      if (!(off2 > off_limit)) break;
+#pragma unroll 1
+      for (int p = 0; p < kEmDim - 1; ++p)
+#pragma unroll 1
+        for (int q = p + 1; q < kEmDim; ++q) {
+          const double app = to_sgpr(M[p * kEmDim + p]), aqq = to_sgpr(M[q * kEmDim + q]), apq = to_sgpr(M[p * kEmDim + q]);
+          const double x = M[row * kEmDim + p], y = M[row * kEmDim + q];
+          if (!(fabs(apq) > skip_limit)) continue;
+          const double theta = 0.5 * (aqq - app) * fast_rcp(apq);
+          const double t = copysign(fast_rcp(fabs(theta) + fast_sqrt(__builtin_fma(theta, theta, 1.0))), theta);
+          const double c = fast_rsqrt(__builtin_fma(t, t, 1.0)), s = t * c;
+          const double nx = c * x - s * y, ny = s * x + c * y;
+          __syncthreads();   // every lane has read before any lane writes
+          if (active) {
+            const bool isp = upper && lane == p, isq = upper && lane == q;
+            M[row * kEmDim + p] = isp ? __builtin_fma(-t, apq, app) : (isq ? 0.0 : nx);
+            M[row * kEmDim + q] = isq ? __builtin_fma(t, apq, aqq) : (isp ? 0.0 : ny);
+            if (upper && !isp && !isq) {
+              M[p * kEmDim + row] = nx;
+              M[q * kEmDim + row] = ny;
+            }
+          }
+          __syncthreads();
+        }
+    }
+
+    // ---- the null space: the eigenvalues ranked, the lowest index first among equals --------------------------------------
+    const int nb = nister ? 4 : 2;
+    double d[kEmDim];
+#pragma unroll
+    for (int k = 0; k < kEmDim; ++k) d[k] = M[k * kEmDim + k];
+    int col[4] = {0, 0, 0, 0};
+    double lam_lo = 0.0, lam_hi = 0.0, lam8 = d[0];
+#pragma unroll
+    for (int k = 0; k < kEmDim; ++k) {
+      int rank = 0;
+#pragma unroll
+      for (int j = 0; j < kEmDim; ++j) rank += (j != k && (d[j] < d[k] || (d[j] == d[k] && j < k))) ? 1 : 0;
+#pragma unroll
+      for (int b = 0; b < 4; ++b) col[b] = rank == b ? k : col[b];
+      lam_lo = rank == nb - 1 ? d[k] : lam_lo;
+      lam_hi = rank == nb ? d[k] : lam_hi;
+      lam8 = d[k] > lam8 ? d[k] : lam8;
+    }
+    gap = (lam_hi - lam_lo) / lam8;
+    // Bv[m]: the coefficient of (x, y, z, 1)[m] in E -- NISTER X = v3, Y = v2, Z = v1, W = v0; SEVENPT X = v1, W = v0
+    double Bv[4][9];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      const int c = nister ? col[3 - m] : (m == 0 ? col[1] : col[0]);
+      const bool used = nister || m == 0 || m == 3;
+#pragma unroll
+      for (int k = 0; k < 9; ++k) Bv[m][k] = used ? M[(kEmDim + k) * kEmDim + c] : 0.0;
+    }
+
+    // ---- p(z), ascending coefficients; the rows of B(z) stay for the null vector -------------------------------------------
+    double pz[11];
+#pragma unroll
+    for (int k = 0; k < 11; ++k) pz[k] = 0.0;
+    double bx[3][4], by[3][4], b1[3][5];
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) bx[s][k] = by[s][k] = 0.0;
+#pragma unroll
+      for (int k = 0; k < 5; ++k) b1[s][k] = 0.0;
+    }
+    if (nister) {
+      // the ten cubics, one per lane
+      double row20[20];
+#pragma unroll
+      for (int k = 0; k < 20; ++k) row20[k] = 0.0;
+      {
+        double El[9][4];
+#pragma unroll
+        for (int k = 0; k < 9; ++k)
+#pragma unroll
+          for (int m = 0; m < 4; ++m) El[k][m] = Bv[m][k];
+        // lane r < 9: entry (ri, rj) of 2 E E'E - tr(E E') E = sum_k L(ri, k) E(k, rj), L = 2 E E' - tr(E E') I
+        const int r9 = lane < 9 ? lane : 0, ri = r9 / 3, rj = r9 % 3;
+        double tr[10];
+#pragma unroll
+        for (int k = 0; k < 10; ++k) tr[k] = 0.0;
+        double Lrow[3][10];
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+#pragma unroll
+          for (int m = 0; m < 10; ++m) Lrow[k][m] = 0.0;
+#pragma unroll
+        for (int x = 0; x < 3; ++x)
+#pragma unroll
+          for (int y = x; y < 3; ++y) {
+            double g[10];
+#pragma unroll
+            for (int m = 0; m < 10; ++m) g[m] = 0.0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) em_fma_ll(El[3 * x + k], El[3 * y + k], 1.0, g);
+            if (x == y) {
+#pragma unroll
+              for (int m = 0; m < 10; ++m) tr[m] += g[m];
+            }
+            // G(x, y) = G(y, x) is entry y of row x and entry x of row y
+#pragma unroll
+            for (int m = 0; m < 10; ++m) {
+              Lrow[y][m] = ri == x ? 2.0 * g[m] : Lrow[y][m];
+              if (x != y) Lrow[x][m] = ri == y ? 2.0 * g[m] : Lrow[x][m];
+            }
+          }
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+#pragma unroll
+          for (int m = 0; m < 10; ++m) Lrow[k][m] -= ri == k ? tr[m] : 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          double ecol[4];
+#pragma unroll
+          for (int m = 0; m < 4; ++m) ecol[m] = rj == 0 ? El[3 * k][m] : (rj == 1 ? El[3 * k + 1][m] : El[3 * k + 2][m]);
+          em_fma_ql(Lrow[k], ecol, row20);
+        }
+        // det E = sum_k E(0, k) (E(1, k+1) E(2, k+2) - E(1, k+2) E(2, k+1))
+        double detc[20];
+#pragma unroll
+        for (int k = 0; k < 20; ++k) detc[k] = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const int k1 = (k + 1) % 3, k2 = (k + 2) % 3;
+          double minor[10];
+#pragma unroll
+          for (int m = 0; m < 10; ++m) minor[m] = 0.0;
+          em_fma_ll(El[3 + k1], El[6 + k2], 1.0, minor);
+          em_fma_ll(El[3 + k2], El[6 + k1], -1.0, minor);
+          em_fma_ql(minor, El[k], detc);
+        }
+#pragma unroll
+        for (int k = 0; k < 20; ++k) row20[k] = lane == 9 ? detc[k] : row20[k];
+      }
+      if (lane < 10) {
+#pragma unroll
+        for (int k = 0; k < 20; ++k) T[lane * 20 + k] = row20[k];
+      }
+      __syncthreads();
+      // lane c < 20: column c.  Gauss-Jordan on the first ten columns, partial pivoting, the lowest row wins a tie
+      double cl[10];
+      {
+        const int c = lane < 20 ? lane : 19;
+#pragma unroll
+        for (int r = 0; r < 10; ++r) cl[r] = T[r * 20 + c];
+      }
+#pragma unroll
+      for (int p = 0; p < 10; ++p) {
+        double pc[10];            // column p, wave-uniform
+#pragma unroll
+        for (int r = 0; r < 10; ++r) pc[r] = em_lane(cl[r], p);
+        int piv = p;
+        double big = fabs(pc[p]);
+#pragma unroll
+        for (int r = p + 1; r < 10; ++r) {
+          const bool more = fabs(pc[r]) > big;
+          big = more ? fabs(pc[r]) : big;
+          piv = more ? r : piv;
+        }
+#pragma unroll
+        for (int r = p + 1; r < 10; ++r) {
+          const bool sw = piv == r;
+          const double mine = cl[r], theirs = cl[p];
+          cl[p] = sw ? mine : theirs;
+          cl[r] = sw ? theirs : mine;
+          const double um = pc[r], ut = pc[p];
+          pc[p] = sw ? um : ut;
+          pc[r] = sw ? ut : um;
+        }
+        cl[p] = cl[p] / pc[p];
+#pragma unroll
+        for (int r = 0; r < 10; ++r)
+          if (r != p) cl[r] = __builtin_fma(-pc[r], cl[p], cl[r]);
+      }
+      // rows 4..9 = <x2z> <x2> <y2z> <y2> <xyz> <xy>, columns 10..19 = xz2 xz x yz2 yz y z3 z2 z 1
+#pragma unroll
+      for (int s = 0; s < 3; ++s) {
+        double ra[10], rb[10];
+#pragma unroll
+        for (int c = 0; c < 10; ++c) {
+          ra[c] = em_lane(cl[4 + 2 * s], 10 + c);
+          rb[c] = em_lane(cl[5 + 2 * s], 10 + c);
+        }
+        bx[s][0] = ra[2];
+        bx[s][1] = ra[1] - rb[2];
+        bx[s][2] = ra[0] - rb[1];
+        bx[s][3] = -rb[0];
+        by[s][0] = ra[5];
+        by[s][1] = ra[4] - rb[5];
+        by[s][2] = ra[3] - rb[4];
+        by[s][3] = -rb[3];
+        b1[s][0] = ra[9];
+        b1[s][1] = ra[8] - rb[9];
+        b1[s][2] = ra[7] - rb[8];
+        b1[s][3] = ra[6] - rb[7];
+        b1[s][4] = -rb[6];
+      }
+      // det B(z) along its third column
+#pragma unroll
+      for (int s = 0; s < 3; ++s) {
+        const int s1 = (s + 1) % 3, s2 = (s + 2) % 3;
+        double minor[7];
+#pragma unroll
+        for (int k = 0; k < 7; ++k) minor[k] = 0.0;
+        em_fma_zz<4, 4>(bx[s1], by[s2], 1.0, minor);
+        em_fma_zz<4, 4>(by[s1], bx[s2], -1.0, minor);
+        em_fma_zz<5, 7>(b1[s], minor, 1.0, pz);
+      }
+    } else {
+      // det(W + aX) = det W + tr(adj(W) X) a + tr(adj(X) W) a2 + det X a3
+      double cw[9], cx[9];
+      em_cofactors(Bv[3], cw);
+      em_cofactors(Bv[0], cx);
+      pz[0] = Bv[3][0] * cw[0] + Bv[3][1] * cw[1] + Bv[3][2] * cw[2];
+      pz[1] = em_dot9(cw, Bv[0]);
+      pz[2] = em_dot9(cx, Bv[3]);
+      pz[3] = Bv[0][0] * cx[0] + Bv[0][1] * cx[1] + Bv[0][2] * cx[2];
+    }
+
+    // ---- the Sturm chain, coefficient j on lane j ----------------------------------------------------------------------------
+    // scale a polynomial by its largest coefficient and find its actual degree; not finite or all zero: the zero polynomial
+    auto settle = [&](double &c, int &deg) {
+      const bool bad = __builtin_amdgcn_ballot_w64(!finite_d(c)) != 0;
+      const double m = em_wave_max(fabs(c));
+      c = (bad || !(m > 0.0)) ? 0.0 : c / m;
+      const unsigned long long nz = __builtin_amdgcn_ballot_w64(c != 0.0);
+      deg = nz ? 63 - __builtin_clzll(nz) : -1;
+    };
+    if (lane == 0) {
+#pragma unroll
+      for (int k = 0; k < 11; ++k) S[k] = pz[k];
+    }
+    __syncthreads();
+    double chain[11];
+    int deg[11];
+    chain[0] = lane < 11 ? S[lane] : 0.0;
+    __syncthreads();
+    settle(chain[0], deg[0]);
+    {
+      const double up = em_gather(chain[0], lane < 63 ? lane + 1 : lane);   // (by every lane: an idle lane would send 0)
+      chain[1] = lane < 10 ? (double)(lane + 1) * up : 0.0;
+    }
+    settle(chain[1], deg[1]);
+#pragma unroll
+    for (int k = 1; k < 10; ++k) {
+      double r = 0.0;
+      int dr = -1;
+      const int dA = deg[k - 1], dB = deg[k];
+      if (dB >= 1) {
+        r = chain[k - 1];
+        const double lead = em_lane(chain[k], dB);
+#pragma unroll 1
+        for (int i = dA; i >= dB; --i) {
+          const double f = em_lane(r, i) / lead;
+          const int sh = i - dB;
+          const double b = em_gather(chain[k], lane >= sh ? lane - sh : lane);
+          r = __builtin_fma(-f, lane >= sh ? b : 0.0, r);
+          r = lane >= i ? 0.0 : r;
+        }
+        r = -r;
+        settle(r, dr);
+      }
+      chain[k + 1] = r;
+      deg[k + 1] = dr;
+    }
+    if (lane < 11) {
+#pragma unroll
+      for (int k = 0; k < 11; ++k) S[11 * k + lane] = chain[k];
+    }
+    __syncthreads();
+    double sc[66];   // polynomial k: 11 - k coefficients at sc[k (23 - k) / 2]
+#pragma unroll
+    for (int k = 0; k < 11; ++k)
+#pragma unroll
+      for (int j = 0; j < 11 - k; ++j) sc[k * (23 - k) / 2 + j] = S[11 * k + j];
+    auto variations = [&](double z) {
+      int v = 0, last = 0;
+#pragma unroll
+      for (int k = 0; k < 11; ++k) {
+        double val = sc[k * (23 - k) / 2 + 10 - k];
+#pragma unroll
+        for (int j = 9 - k; j >= 0; --j) val = __builtin_fma(val, z, sc[k * (23 - k) / 2 + j]);
+        const int s = val > 0.0 ? 1 : (val < 0.0 ? -1 : 0);
+        v += (s != 0 && last != 0 && s != last) ? 1 : 0;
+        last = s != 0 ? s : last;
+      }
+      return v;
+    };
+
+    // ---- the real roots: all of them lie within Cauchy's bound; lane i bisects for the i-th ----------------------------------
+    double root = 0.0;
+    {
+      const int d0 = deg[0];
+      double bound = 0.0;
+      if (d0 >= 1) {
+        const double lead = em_lane(chain[0], d0);
+        bound = 1.0 + em_wave_max(lane < d0 ? fabs(chain[0] / lead) : 0.0);
+      }
+      bound = to_sgpr(bound);
+      int v_lo = 0;
+      if (d0 >= 1 && finite_d(bound)) {
+        v_lo = to_sgpr(variations(-bound));
+        n_sol = v_lo - to_sgpr(variations(bound));
+        n_sol = n_sol < 0 ? 0 : (n_sol > d0 ? d0 : n_sol);
+      }
+      long long lo = em_key(-bound), hi = em_key(bound);
+      if (n_sol > 0) {
+#pragma unroll 1
+        for (int it = 0; it < kEmBisections; ++it) {
+          const long long mid = lo + (long long)(((unsigned long long)hi - (unsigned long long)lo) >> 1);
+          const bool below = v_lo - variations(em_unkey(mid)) >= lane + 1;   // at least lane + 1 roots in (-bound, mid]
+          hi = below ? mid : hi;
+          lo = below ? lo : mid;
+        }
+      }
+      root = em_unkey(hi);
+    }
+    const bool valid = lane < n_sol;
+
+    // ---- per solution: the point, the polish, norm and sign --------------------------------------------------------------------
+    if (n_sol > 0) {
+      double E[9];
+      if (nister) {
+        double Bz[3][3];
+#pragma unroll
+        for (int s = 0; s < 3; ++s) {
+          Bz[s][0] = em_horner(bx[s], root);
+          Bz[s][1] = em_horner(by[s], root);
+          Bz[s][2] = em_horner(b1[s], root);
+        }
+        // (x, y, 1) spans the null space of B(z): the cross product of two rows, the pair whose product is longest
+        double c01[3], c02[3], c12[3];
+        em_cross(Bz[0], Bz[1], c01);
+        em_cross(Bz[0], Bz[2], c02);
+        em_cross(Bz[1], Bz[2], c12);
+        const double n01 = c01[0] * c01[0] + c01[1] * c01[1] + c01[2] * c01[2];
+        const double n02 = c02[0] * c02[0] + c02[1] * c02[1] + c02[2] * c02[2];
+        const double n12 = c12[0] * c12[0] + c12[1] * c12[1] + c12[2] * c12[2];
+        const bool t01 = n01 >= n02 && n01 >= n12, t02 = !t01 && n02 >= n12;
+        double cv[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) cv[k] = t01 ? c01[k] : (t02 ? c02[k] : c12[k]);
+        double xyz[3] = {cv[0] / cv[2], cv[1] / cv[2], root};
+#pragma unroll 1
+        for (int step = 0; step < kEmPolishSteps; ++step) {
+#pragma unroll
+          for (int k = 0; k < 9; ++k)
+            E[k] = __builtin_fma(xyz[0], Bv[0][k], __builtin_fma(xyz[1], Bv[1][k], __builtin_fma(xyz[2], Bv[2][k], Bv[3][k])));
+          EmPoint w;
+          double r[10], J[3][10];
+          em_residual(E, w, r);
+#pragma unroll
+          for (int m = 0; m < 3; ++m) em_derivative(E, w, Bv[m], J[m]);
+          // the normal equations, 3x3, by the adjugate
+          double A[9], g[3];
+#pragma unroll
+          for (int x = 0; x < 3; ++x) {
+            double s = 0.0;
+#pragma unroll
+            for (int k = 0; k < 10; ++k) s = __builtin_fma(J[x][k], r[k], s);
+            g[x] = s;
+#pragma unroll
+            for (int y = x; y < 3; ++y) {
+              double t = 0.0;
+#pragma unroll
+              for (int k = 0; k < 10; ++k) t = __builtin_fma(J[x][k], J[y][k], t);
+              A[3 * x + y] = A[3 * y + x] = t;
+            }
+          }
+          double cof[9];
+          em_cofactors(A, cof);   // A symmetric: its adjugate is the cofactor matrix
+          const double det = A[0] * cof[0] + A[1] * cof[1] + A[2] * cof[2];
+          const double inv = 1.0 / det;
+#pragma unroll
+          for (int x = 0; x < 3; ++x)
+            xyz[x] -= (cof[x] * g[0] + cof[3 + x] * g[1] + cof[6 + x] * g[2]) * inv;
+        }
+#pragma unroll
+        for (int k = 0; k < 9; ++k)
+          E[k] = __builtin_fma(xyz[0], Bv[0][k], __builtin_fma(xyz[1], Bv[1][k], __builtin_fma(xyz[2], Bv[2][k], Bv[3][k])));
+      } else {
+        double al = root;
+#pragma unroll 1
+        for (int step = 0; step < kEmPolishSteps; ++step) {
+#pragma unroll
+          for (int k = 0; k < 9; ++k) E[k] = __builtin_fma(al, Bv[0][k], Bv[3][k]);
+          double cof[9];
+          em_cofactors(E, cof);
+          al -= (E[0] * cof[0] + E[1] * cof[1] + E[2] * cof[2]) / em_dot9(cof, Bv[0]);
+        }
+#pragma unroll
+        for (int k = 0; k < 9; ++k) E[k] = __builtin_fma(al, Bv[0][k], Bv[3][k]);
+      }
+      {
+        double nn = 0.0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) nn = __builtin_fma(E[k], E[k], nn);
+        const double scl = em_sign(E) / sqrt(nn);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) E[k] = valid ? E[k] * scl : nan;
+      }
+
+      // ---- the order: ascending e[0], then e[1], ...; equal vectors keep the order of their roots ---------------------------
+      int rank = 0;
+#pragma unroll
+      for (int j = 0; j < kEmMaxSolutions; ++j) {
+        if (j < n_sol) {
+          bool less = false, decided = false;
+#pragma unroll
+          for (int k = 0; k < 9; ++k) {
+            const double o = em_lane(E[k], j);
+            less = (!decided && o < E[k]) ? true : less;
+            decided = decided || o != E[k];
+          }
+          rank += (less || (!decided && j < lane)) ? 1 : 0;
+        }
+      }
+      if (valid) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) Es[rank * 9 + k] = E[k];
+      }
+      __syncthreads();
+#pragma unroll
+      for (int k = 0; k < 9; ++k) e[k] = valid ? Es[lane * 9 + k] : nan;
+
+      // ---- SVD of every E through E'E (pnec_eight_point.hip, one lane per solution) -------------------------------------------
+      double B[9], V[9];
+#pragma unroll
+      for (int x = 0; x < 3; ++x)
+#pragma unroll
+        for (int y = x; y < 3; ++y) B[3 * x + y] = B[3 * y + x] = e[x] * e[y] + e[3 + x] * e[3 + y] + e[6 + x] * e[6 + y];
+#pragma unroll
+      for (int k = 0; k < 9; ++k) V[k] = (k % 4 == 0) ? 1.0 : 0.0;
+      {
+        const double tr3 = B[0] + B[4] + B[8];
+        const double lim3 = (kEpOffTol * tr3) * (kEpOffTol * tr3);
+#pragma unroll 1
+        for (int sweep = 0; sweep < kEpMaxSweeps; ++sweep) {
+          const double off2 = 2.0 * (B[1] * B[1] + B[2] * B[2] + B[5] * B[5]);
+          const bool more = off2 > lim3;
+          if (__builtin_amdgcn_ballot_w64(more) == 0) break;
+          double Bn[9], Vn[9];
+#pragma unroll
+          for (int k = 0; k < 9; ++k) {
+            Bn[k] = B[k];
+            Vn[k] = V[k];
+          }
+          em_rotate3<0, 1>(Bn, Vn);
+          em_rotate3<0, 2>(Bn, Vn);
+          em_rotate3<1, 2>(Bn, Vn);
+#pragma unroll
+          for (int k = 0; k < 9; ++k) {   // a lane that has converged keeps what it has
+            B[k] = more ? Bn[k] : B[k];
+            V[k] = more ? Vn[k] : V[k];
+          }
+        }
+      }
+      const double w0 = B[0], w1 = B[4], w2 = B[8];
+      const int i0 = (w0 >= w1 && w0 >= w2) ? 0 : (w1 >= w2 ? 1 : 2);
+      const int ja = i0 == 0 ? 1 : 0, jb = i0 == 2 ? 1 : 2;
+      const double wa = ja == 0 ? w0 : w1, wb = jb == 1 ? w1 : w2;
+      const int i2 = wb <= wa ? jb : ja, i1 = 3 - i0 - i2;
+      const double lam[3] = {i0 == 0 ? w0 : (i0 == 1 ? w1 : w2), i1 == 0 ? w0 : (i1 == 1 ? w1 : w2),
+                             i2 == 0 ? w0 : (i2 == 1 ? w1 : w2)};
+      double sing[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) sing[k] = sqrt(lam[k] > 0.0 ? lam[k] : 0.0);
+      double v0[3], v1[3], v2[3], u0[3], u1[3], u2[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        v0[k] = em_pick3(V, k, i0);
+        v1[k] = em_pick3(V, k, i1);
+        v2[k] = em_pick3(V, k, i2);
+      }
+      {
+        const double sg = em_sign(v2);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) v2[k] *= sg;
+        double cr[3];
+        em_cross(v1, v2, cr);
+        const double det = v0[0] * cr[0] + v0[1] * cr[1] + v0[2] * cr[2];
+        const double s1 = det < 0.0 ? -1.0 : 1.0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) v1[k] *= s1;
+      }
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        u0[k] = e[3 * k] * v0[0] + e[3 * k + 1] * v0[1] + e[3 * k + 2] * v0[2];
+        u1[k] = e[3 * k] * v1[0] + e[3 * k + 1] * v1[1] + e[3 * k + 2] * v1[2];
+      }
+      em_normalise(u0);
+      em_normalise(u1);
+      em_cross(u0, u1, u2);
+      em_normalise(u2);
+      if (lane < kEmMaxSolutions) {
+#pragma unroll
+        for (int x = 0; x < 3; ++x)
+#pragma unroll
+          for (int y = 0; y < 3; ++y) {
+            const double m = u1[x] * v0[y] - u0[x] * v1[y], z = u2[x] * v2[y];
+            C[lane * kEmCand + 3 * x + y] = z + m;        // Ra before its sign
+            C[lane * kEmCand + 9 + 3 * x + y] = z - m;    // Rb
+          }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          C[lane * kEmCand + 18 + k] = u2[k];
+          C[lane * kEmCand + 21 + k] = sing[k];
+        }
+      }
+      __syncthreads();
+
+      // ---- the forty qualities: lane 4 i + j, candidate j of solution i ----------------------------------------------------------
+      const int ci = lane < 4 * kEmMaxSolutions ? lane >> 2 : 0, cj = lane & 3;
+      const bool cand = lane < 4 * n_sol;
+      double R[9], t[3];
+#pragma unroll
+      for (int k = 0; k < 9; ++k) R[k] = C[ci * kEmCand + ((cj & 1) ? 9 : 0) + k];
+      {
+        const double sd = em_det3(R) < 0.0 ? -1.0 : 1.0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R[k] *= sd;
+      }
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const double u = C[ci * kEmCand + 18 + k];
+        t[k] = (cj & 2) ? -u : u;
+      }
+      {
+        const int sample = nister ? kEmSampleNister : kEmSampleSevenpt;
+        const int K = (a.flags & PNEC_HIP_EM_QUALITY_ALL) ? n : (n < sample ? n : sample);
+        double qs = 0.0;
+#pragma unroll 1
+        for (int k = 0; k < K; ++k) {
+          double f[6];
+          load6(k, f);
+          qs += em_term(f, R, t);
+        }
+        qs = finite_d(qs) ? qs : __builtin_inf();
+        quality = cand ? qs : nan;
+        const double mine = cand ? qs : __builtin_inf();
+        const double best = em_wave_min(mine);
+        if (best < kEpStartQuality) {
+          const unsigned long long at = __builtin_amdgcn_ballot_w64(cand && mine == best);
+          choice = at ? (int)__builtin_ctzll(at) : -1;
+        }
+      }
+      if (choice < 0) status = PNEC_HIP_EM_NO_CANDIDATE;
+    } else {
+      status = PNEC_HIP_EM_NO_SOLUTION;
+    }
+  }
+
+  // ---- the outputs ----------------------------------------------------------------------------------------------------------------
+  if (a.out_E_all && lane < kEmMaxSolutions) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) a.out_E_all[(pair * kEmMaxSolutions + lane) * 9 + k] = e[k];
+  }
+  if (a.out_quality && lane < 4 * kEmMaxSolutions) a.out_quality[pair * 4 * kEmMaxSolutions + lane] = quality;
+  if (lane == 0) {
+    double Rc[9], tc[3], Ec[9], sing[3];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Rc[k] = Ec[k] = nan;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) tc[k] = sing[k] = nan;
+    if (status == PNEC_HIP_EM_OK) {
+      const int ci = choice >> 2;
+#pragma unroll
+      for (int k = 0; k < 9; ++k) {
+        Rc[k] = C[ci * kEmCand + ((choice & 1) ? 9 : 0) + k];
+        Ec[k] = Es[ci * 9 + k];
+      }
+      const double sd = em_det3(Rc) < 0.0 ? -1.0 : 1.0;
+#pragma unroll
+      for (int k = 0; k < 9; ++k) Rc[k] *= sd;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const double u = C[ci * kEmCand + 18 + k];
+        tc[k] = (choice & 2) ? -u : u;
+        sing[k] = C[ci * kEmCand + 21 + k];
+      }
+    }
+    if (a.out_q) {
+      double q[4] = {nan, nan, nan, nan};
+      if (status == PNEC_HIP_EM_OK) em_quat(Rc, q);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) a.out_q[4 * pair + k] = q[k];
+    }
+    if (a.out_t) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) a.out_t[3 * pair + k] = tc[k];
+    }
+    if (a.out_E) {
+#pragma unroll
+      for (int k = 0; k < 9; ++k) a.out_E[9 * pair + k] = Ec[k];
+    }
+    if (a.out_singular) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) a.out_singular[3 * pair + k] = sing[k];
+    }
+    if (a.out_gap) a.out_gap[pair] = gap;
+    if (a.out_n_solutions) a.out_n_solutions[pair] = n_sol;
+    if (a.out_choice) a.out_choice[pair] = choice;
+    if (a.out_status) a.out_status[pair] = status;
+  }
+}
+
+hipError_t launch_essential_minimal(int64_t n_pairs, const EssentialMinimalArgs &a, hipStream_t stream) {
+  hipLaunchKernelGGL(essential_minimal_kernel, dim3((unsigned)n_pairs), dim3(kWave), 0, stream, a);
+  return hipGetLastError();
+}
+
+}  // namespace pnec_hip

@@ -13,7 +13,12 @@ run_simulation.cc:88-131) one more column follows the six:
 
     8pt            EMPoseEstimation(..., EIGHTPT, ransac = false)      essential_matrix_methods.cc:45-126
 
-(the start pose where the pair gives no pose, as the reference returns it).  All experiments of the
+(the start pose where the pair gives no pose, as the reference returns it), and with --em-minimal two more after those:
+
+    7pt            MinimalEMPoseEstimation(..., SEVENPT): opengv's sevenpt, ransac = false
+    Nister5pt      MinimalEMPoseEstimation(..., NISTER): opengv's fivept_nister, ransac = false
+
+(the reference's names and order, run_simulation.cc:88-131).  All experiments of the
 folder go through each stage in ONE device launch.  Input side as `ReadExperiments`
 (src/simulation/sim_common.cc:109-236): relative pose = pose_1^-1 pose_2, bearings = normalised
 points, frame-2 covariances through the unscented transform (K^-1 = I, kappa = 1), start pose = ground
@@ -21,7 +26,7 @@ truth perturbed by <= 0.01 rad / 0.01 (own RNG with a recorded seed: the C++ std
 uniform_real_distribution stream is not reproduced).
 
     python -m pnec_amd.run_simulation <experiment_folder> [--camera pinhole|omni] [--out DIR]
-                                      [--init-scaling 1.0] [--seed 1] [--em-methods]
+                                      [--init-scaling 1.0] [--seed 1] [--em-methods] [--em-minimal]
 """
 from __future__ import annotations
 
@@ -38,7 +43,8 @@ from .frontend import CAMERA_OMNIDIRECTIONAL, CAMERA_PINHOLE, unscented_transfor
 from .io_formats import read_experiments, relative_poses, write_result_tables
 
 METHODS = ("NEC", "NEC-LS", "NEC PNEC-LS", "PNEC only LS", "PNEC w/o LS", "PNEC")
-EM_METHODS = ("8pt",)   # the essential-matrix baselines that are built (7pt, Nister, Stewenius and the RANSAC forms are not)
+EM_MINIMAL_METHODS = ("7pt", "Nister5pt")   # --em-minimal: pnec_hip_essential_minimal, the reference's names and order
+EM_METHODS = ("8pt",)   # --em-methods: the eight-point baseline (Stewenius and the RANSAC forms are not built)
 
 
 def _quat_to_matrix(q):
@@ -93,7 +99,8 @@ def perturbed_start(R_gt, t_gt, rng, init_scaling=1.0):
     return R0, t0 / np.linalg.norm(t0, axis=1, keepdims=True)
 
 
-def run(folder: str, camera: str = "pinhole", init_scaling: float = 1.0, seed: int = 1, em_methods: bool = False):
+def run(folder: str, camera: str = "pinhole", init_scaling: float = 1.0, seed: int = 1, em_methods: bool = False,
+        em_minimal: bool = False):
     ex = read_experiments(folder)
     E = len(ex["points_1"])
     counts = np.array([len(p) for p in ex["points_1"]], dtype=np.int64)
@@ -130,6 +137,12 @@ def run(folder: str, camera: str = "pinhole", init_scaling: float = 1.0, seed: i
             ok = (ep.status == capi.EP_OK)[:, None]
             sols["8pt"] = (np.where(ok, ep.q, q0), np.where(ok, ep.t, t0))
             methods = METHODS + EM_METHODS
+        if em_minimal:
+            for name, solve in (("7pt", nb.seven_point), ("Nister5pt", nb.five_point)):
+                mp = solve(on_device=False)
+                ok = (mp.status == capi.EM_OK)[:, None]
+                sols[name] = (np.where(ok, mp.q, q0), np.where(ok, mp.t, t0))
+            methods = methods + EM_MINIMAL_METHODS
         results = {}
         for m in methods:
             q, t = sols[m]
@@ -148,12 +161,14 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--em-methods", action="store_true",
                     help="add the essential-matrix baselines that are built (8pt) after the six columns")
+    ap.add_argument("--em-minimal", action="store_true",
+                    help="add the minimal baselines (7pt, Nister5pt) after the columns that --em-methods gives")
     return ap
 
 
 def main(argv=None):
     args = parser().parse_args(argv)
-    res = run(args.folder, args.camera, args.init_scaling, args.seed, args.em_methods)
+    res = run(args.folder, args.camera, args.init_scaling, args.seed, args.em_methods, args.em_minimal)
     write_result_tables(args.out or args.folder, res)
     print(json.dumps({m: {"median_r_error_deg": float(np.median(res[m]["r_error"])),
                           "median_t_error_deg": float(np.median(res[m]["t_error"]))} for m in res}))

@@ -180,6 +180,19 @@ void batch_lists(int64_t P, int64_t n_hyp, int64_t n) {
       l.out(l.opt(), P, 4);        // status
     }, 24 * P, 2 * P);
 
+    run(tag("essential_minimal", {P}), [&](List &l) {
+      l.out(l.opt(), 4 * P, 8);    // q
+      l.out(l.opt(), 3 * P, 8);    // t
+      l.out(l.opt(), 9 * P, 8);    // E
+      l.out(l.opt(), 3 * P, 8);    // singular
+      l.out(l.opt(), P, 8);        // gap
+      l.out(l.opt(), P, 4);        // n_solutions
+      l.out(l.opt(), 90 * P, 8);   // E_all
+      l.out(l.opt(), 40 * P, 8);   // quality
+      l.out(l.opt(), P, 4);        // choice
+      l.out(l.opt(), P, 4);        // status
+    }, 150 * P, 3 * P);
+
     // pairs of the previous batch: one more than of this one, so that the two counts cannot be mixed up unnoticed
     const int64_t Pp = P + 1;
     run(tag("relative_scale", {P, Pp, C}), [&](List &l) {
