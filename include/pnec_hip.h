@@ -707,7 +707,7 @@ int pnec_hip_eight_point(pnec_hip_problem *p, int32_t flags, double *out_q, doub
  *    zero is taken at its actual degree): the roots lie within Cauchy's bound 1 + max |p_i / p_n|, their count is the
  *    difference of the sign changes at the two ends, root i is isolated by bisection on the count, 64 halvings in the
  *    integer order of the doubles.  x and y are the null vector of B(z): the cross product of two rows, the pair whose
- *    product is longest.  Polish: two Gauss-Newton steps on the ten cubics in (x, y, z), evaluated from E directly -- the
+ *    product is longest.  Polish: five Gauss-Newton steps on the ten cubics in (x, y, z), evaluated from E directly -- the
  *    derivative of det E along X is tr(adj(E) X), that of the nine entries 2 (X E'E + E X'E + E E'X) - 2 tr(E X') E -
  *    tr(E E') X; the 3 x 3 normal equations are solved by the adjugate.
  *  2b SEVENPT.  E(a) = W + aX, det E(a) = det W + tr(adj(W) X) a + tr(adj(X) W) a2 + det X a3; the real roots of the

@@ -21,7 +21,7 @@
 //                  The chain (66 coefficients at most) goes through LDS into registers of every lane.
 //   roots          lane i bisects for the i-th real root on the count of sign changes, in the integer order of the
 //                  doubles (64 halvings reach one ulp from any bound); 66 FMAs per count, no memory.
-//   per solution   lane i: null vector of B(z), two Gauss-Newton steps on the ten cubics (one Newton step pair on det for
+//   per solution   lane i: null vector of B(z), five Gauss-Newton steps on the ten cubics (one Newton step pair on det for
 //                  SEVENPT), norm and sign, rank in the lexicographic order by ten broadcasts, exchange through LDS, then
 //                  the eight-point's 3x3 decomposition.  A lane that has converged is frozen while others sweep on; the
 //                  sweep loops end by ballot.
@@ -730,7 +730,7 @@ __global__ __launch_bounds__(kWave) void essential_minimal_kernel(const Essentia
         for (int k = 0; k < 3; ++k) cv[k] = t01 ? c01[k] : (t02 ? c02[k] : c12[k]);
         double xyz[3] = {cv[0] / cv[2], cv[1] / cv[2], root};
 #pragma unroll 1
-        for (int step = 0; step < kEmPolishSteps; ++step) {
+        for (int step = 0; step < kEmPolishNister; ++step) {
 #pragma unroll
           for (int k = 0; k < 9; ++k)
             E[k] = __builtin_fma(xyz[0], Bv[0][k], __builtin_fma(xyz[1], Bv[1][k], __builtin_fma(xyz[2], Bv[2][k], Bv[3][k])));
@@ -769,7 +769,7 @@ __global__ __launch_bounds__(kWave) void essential_minimal_kernel(const Essentia
       } else {
         double al = root;
 #pragma unroll 1
-        for (int step = 0; step < kEmPolishSteps; ++step) {
+        for (int step = 0; step < kEmPolishSevenpt; ++step) {
 #pragma unroll
           for (int k = 0; k < 9; ++k) E[k] = __builtin_fma(al, Bv[0][k], Bv[3][k]);
           double cof[9];
