@@ -27,13 +27,7 @@ struct EightPointArgs {
 // one block of one wavefront per pair
 hipError_t launch_eight_point(int64_t n_pairs, const EightPointArgs &a, hipStream_t stream);
 
-// the cyclic Jacobi iteration on A'A: it stops when the Frobenius norm of the off-diagonal part is at or below
-// kEpOffTol * trace, after kEpMaxSweeps sweeps at the latest; a rotation whose pivot is at or below kEpSkipTol * trace
-// is left out (it would change nothing that the stop looks at)
-constexpr int kEpMaxSweeps = 16;
-constexpr double kEpOffTol = 0x1p-58;
-constexpr double kEpSkipTol = 0x1p-90;
-constexpr double kEpStartQuality = 1e6;   // the reference's bestQuality (src/common/common.cc:273)
+// (the Jacobi iteration's constants and the start quality: pnec_essential_shared.hpp)
 constexpr int kEpSample = 9;              // the reference's sampleSize for EIGHTPT: 8 + 1 (common.cc:378)
 
 }  // namespace pnec_hip

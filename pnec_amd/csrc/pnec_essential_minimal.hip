@@ -3,9 +3,8 @@
 // the definitions; this file says how the wavefront is used.
 //
 // One block of one wavefront per pair.  The phases, every branch that holds a barrier wave-uniform:
-//   sums, Jacobi   the eight-point kernel's two phases, statement for statement (pnec_eight_point.hip; this unit carries
-//                  its own copy, so that kernel's instruction stream is untouched): 45 sums by the fixed butterfly, the
-//                  9x9 and its eigenvectors as an 18x9 array in LDS with rows on lanes.
+//   sums, Jacobi   es_sums and es_jacobi of pnec_essential_shared.hpp, the eight-point kernel's two phases: 45 sums by the
+//                  fixed butterfly, the 9x9 and its eigenvectors as an 18x9 array in LDS with rows on lanes.
 //   null space     the diagonal is ranked in registers (72 comparisons, the lowest index wins a tie); the four (two)
 //                  vectors of the smallest eigenvalues are read from LDS at the ranked columns.
 //   cubics         NISTER.  Every lane forms E E' (six quadratic polynomials) from the basis; lane r < 9 takes row r / 3
@@ -23,129 +22,26 @@
 //                  doubles (64 halvings reach one ulp from any bound); 66 FMAs per count, no memory.
 //   per solution   lane i: null vector of B(z), five Gauss-Newton steps on the ten cubics (one Newton step pair on det for
 //                  SEVENPT), norm and sign, rank in the lexicographic order by ten broadcasts, exchange through LDS, then
-//                  the eight-point's 3x3 decomposition.  A lane that has converged is frozen while others sweep on; the
-//                  sweep loops end by ballot.
+//                  the 3x3 decomposition with one solution per lane: its own sweep loop (a lane that has converged is
+//                  frozen while others sweep on, the loop ends by ballot), then es_decompose's pieces -- es_order3,
+//                  es_right_vectors, es_left_vectors, es_rotations.
 //   qualities      lane 4 i + j reads candidate j of solution i from LDS and sums its terms over the sample (or over all
 //                  correspondences); every lane reads the same bearing (one broadcast load per plane).
 //   choice         a butterfly minimum and a ballot: the lowest lane that holds the minimum.
-// Lane 0 stores the pair's outputs, lanes < 10 / < 40 their rows of out_E_all / out_quality, with plain vector stores.
-// No atomics; a pair's bits depend on its own rows, on `algorithm` and on `flags` only.
+// Lane 0 stores the pair's outputs (the number of solutions, then es_store_pose), lanes < 10 / < 40 their rows of
+// out_E_all / out_quality, with plain vector stores.  No atomics; a pair's bits depend on its own rows, on `algorithm`
+// and on `flags` only.
 #include <hip/hip_runtime.h>
 
 #include "pnec_device.hpp"
-#include "pnec_eight_point.hpp"         // the Jacobi constants and the start quality, shared with the eight-point
 #include "pnec_essential_minimal.hpp"
-#include "pnec_triangulate.hpp"         // tri_depths: the midpoint system
+#include "pnec_essential_shared.hpp"
 
 namespace pnec_hip {
 
 namespace {
 
-constexpr int kEmDim = 9;
-constexpr int kEmRows = 2 * kEmDim;
 constexpr int kEmCand = 24;   // doubles per solution in LDS: Ra, Rb, ta, singular values
-
-// ---- the eight-point kernel's helpers (copies: see the head of this file) --------------------------------------------
-template <int P, int Q>
-__device__ __forceinline__ void em_rotate3(double (&A)[9], double (&V)[9]) {
-  constexpr int R = 3 - P - Q;
-  const double apq = A[3 * P + Q];
-  const bool nz = apq != 0.0;
-  const double theta = (A[4 * Q] - A[4 * P]) / (2.0 * (nz ? apq : 1.0));
-  double t = copysign(1.0, theta) / (fabs(theta) + sqrt(__builtin_fma(theta, theta, 1.0)));
-  t = nz ? t : 0.0;
-  const double c = 1.0 / sqrt(__builtin_fma(t, t, 1.0)), s = t * c;
-  A[4 * P] = __builtin_fma(-t, apq, A[4 * P]);
-  A[4 * Q] = __builtin_fma(t, apq, A[4 * Q]);
-  A[3 * P + Q] = A[3 * Q + P] = 0.0;
-  const double arp = A[3 * R + P], arq = A[3 * R + Q];
-  A[3 * R + P] = A[3 * P + R] = c * arp - s * arq;
-  A[3 * R + Q] = A[3 * Q + R] = s * arp + c * arq;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double vp = V[3 * k + P], vq = V[3 * k + Q];
-    V[3 * k + P] = c * vp - s * vq;
-    V[3 * k + Q] = s * vp + c * vq;
-  }
-}
-
-__device__ __forceinline__ double em_pick3(const double (&x)[9], int row, int col) {
-  const double a = x[3 * row], b = x[3 * row + 1], c = x[3 * row + 2];
-  return col == 0 ? a : (col == 1 ? b : c);
-}
-
-__device__ __forceinline__ void em_cross(const double (&a)[3], const double (&b)[3], double (&c)[3]) {
-  c[0] = a[1] * b[2] - a[2] * b[1];
-  c[1] = a[2] * b[0] - a[0] * b[2];
-  c[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-__device__ __forceinline__ void em_normalise(double (&v)[3]) {
-  const double inv = 1.0 / sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-  v[0] *= inv;
-  v[1] *= inv;
-  v[2] *= inv;
-}
-
-template <int N>
-__device__ __forceinline__ double em_sign(const double (&v)[N]) {
-  double big = v[0];
-#pragma unroll
-  for (int k = 1; k < N; ++k) big = fabs(v[k]) > fabs(big) ? v[k] : big;
-  return big < 0.0 ? -1.0 : 1.0;
-}
-
-__device__ __forceinline__ double em_det3(const double (&R)[9]) {
-  return R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
-}
-
-__device__ __forceinline__ double em_term(const double (&f)[6], const double (&R)[9], const double (&t)[3]) {
-  TriSystem ts;
-  tri_depths(f, R, t, ts);
-  const double px = 0.5 * __builtin_fma(ts.depth1, f[0], __builtin_fma(ts.depth2, ts.ux, t[0]));
-  const double py = 0.5 * __builtin_fma(ts.depth1, f[1], __builtin_fma(ts.depth2, ts.uy, t[1]));
-  const double pz = 0.5 * __builtin_fma(ts.depth1, f[2], __builtin_fma(ts.depth2, ts.uz, t[2]));
-  const double n1 = 1.0 / sqrt(px * px + py * py + pz * pz);
-  const double wx = px - t[0], wy = py - t[1], wz = pz - t[2];
-  const double x2 = R[0] * wx + R[3] * wy + R[6] * wz;
-  const double y2 = R[1] * wx + R[4] * wy + R[7] * wz;
-  const double z2 = R[2] * wx + R[5] * wy + R[8] * wz;
-  const double n2 = 1.0 / sqrt(x2 * x2 + y2 * y2 + z2 * z2);
-  const double e1 = 1.0 - (f[0] * px + f[1] * py + f[2] * pz) * n1;
-  const double e2 = 1.0 - (f[3] * x2 + f[4] * y2 + f[5] * z2) * n2;
-  return e1 + e2;
-}
-
-__device__ __forceinline__ void em_quat(const double (&R)[9], double (&q)[4]) {
-  const double tr = R[0] + R[4] + R[8];
-  double x, y, z, w;
-  if (tr > 0.0) {
-    w = 1.0 + tr;
-    x = R[7] - R[5];
-    y = R[2] - R[6];
-    z = R[3] - R[1];
-  } else if (R[0] >= R[4] && R[0] >= R[8]) {
-    x = 1.0 + R[0] - R[4] - R[8];
-    y = R[1] + R[3];
-    z = R[2] + R[6];
-    w = R[7] - R[5];
-  } else if (R[4] >= R[8]) {
-    x = R[1] + R[3];
-    y = 1.0 - R[0] + R[4] - R[8];
-    z = R[5] + R[7];
-    w = R[2] - R[6];
-  } else {
-    x = R[2] + R[6];
-    y = R[5] + R[7];
-    z = 1.0 - R[0] - R[4] + R[8];
-    w = R[3] - R[1];
-  }
-  const double inv = 1.0 / sqrt(x * x + y * y + z * z + w * w);
-  q[0] = x * inv;
-  q[1] = y * inv;
-  q[2] = z * inv;
-  q[3] = w * inv;
-}
 
 // ---- lanes ---------------------------------------------------------------------------------------------------------------
 // the value lane `src` holds, src wave-uniform (a constant where the caller's loop is unrolled)
@@ -252,9 +148,9 @@ __device__ __forceinline__ void em_mul33_tn(const double (&A)[9], const double (
 __device__ __forceinline__ void em_cofactors(const double (&E)[9], double (&c)[9]) {
   const double r0[3] = {E[0], E[1], E[2]}, r1[3] = {E[3], E[4], E[5]}, r2[3] = {E[6], E[7], E[8]};
   double c0[3], c1[3], c2[3];
-  em_cross(r1, r2, c0);
-  em_cross(r2, r0, c1);
-  em_cross(r0, r1, c2);
+  es_cross(r1, r2, c0);
+  es_cross(r2, r0, c1);
+  es_cross(r0, r1, c2);
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     c[k] = c0[k];
@@ -300,7 +196,7 @@ __device__ __forceinline__ void em_derivative(const double (&E)[9], const EmPoin
 }  // namespace
 
 __global__ __launch_bounds__(kWave) void essential_minimal_kernel(const EssentialMinimalArgs a) {
-  __shared__ double M[kEmRows * kEmDim];          // rows 0..8: A'A, rows 9..17: its eigenvectors as columns
+  __shared__ double M[kEsRows * kEsDim];          // rows 0..8: A'A, rows 9..17: its eigenvectors as columns
   __shared__ double T[10 * 20];                   // the ten cubics, row-major
   __shared__ double S[11 * 11];                   // the Sturm chain, polynomial k at S[11 k]
   __shared__ double Es[kEmMaxSolutions * 9];      // the solutions in their order
@@ -310,12 +206,7 @@ __global__ __launch_bounds__(kWave) void essential_minimal_kernel(const Essentia
   const int lane = threadIdx.x;
   const int n = to_sgpr(a.count[pair]);
   const bool nister = a.algorithm == PNEC_HIP_EM_NISTER;
-  const int64_t stride = ((int64_t)n + kWave - 1) & ~(int64_t)(kWave - 1);
-  const double *base = a.data + a.block_offset[pair];
-  auto load6 = [&](int i, double (&f)[6]) {
-#pragma unroll
-    for (int c = 0; c < 6; ++c) f[c] = base[(int64_t)c * stride + i];
-  };
+  const EsPair pr = {a.data + a.block_offset[pair], ((int64_t)n + kWave - 1) & ~(int64_t)(kWave - 1)};
 
   const double nan = __builtin_nan("");
   int status = n < (nister ? 5 : 7) ? PNEC_HIP_EM_TOO_FEW : PNEC_HIP_EM_OK;
@@ -327,101 +218,26 @@ __global__ __launch_bounds__(kWave) void essential_minimal_kernel(const Essentia
 
   double trace = 0.0;
   if (status == PNEC_HIP_EM_OK) {
-    // ---- the 45 sums (pnec_eight_point.hip) ------------------------------------------------------------------------------
-    double acc[45];
-#pragma unroll
-    for (int k = 0; k < 45; ++k) acc[k] = 0.0;
-#pragma unroll 1
-    for (int i0 = 0; i0 < n; i0 += kWave) {
-      const int i = i0 + lane;
-      const bool in = i < n;
-      double f[6];
-      load6(in ? i : n - 1, f);
-      double r[9];
-#pragma unroll
-      for (int k = 0; k < 9; ++k) r[k] = in ? f[k / 3] * f[3 + k % 3] : 0.0;
-      int k = 0;
-#pragma unroll
-      for (int x = 0; x < 9; ++x)
-#pragma unroll
-        for (int y = x; y < 9; ++y) {
-          acc[k] = __builtin_fma(r[x], r[y], acc[k]);
-          ++k;
-        }
-    }
-    {
-      int k = 0;
-#pragma unroll
-      for (int x = 0; x < 9; ++x)
-#pragma unroll
-        for (int y = x; y < 9; ++y) {
-          const double s = wave_allreduce_sum(acc[k]);
-          ++k;
-          if (x == y) trace += s;
-          if (lane == 0) {
-            M[x * kEmDim + y] = s;
-            M[y * kEmDim + x] = s;
-          }
-        }
-    }
-    for (int x = lane; x < kEmDim * kEmDim; x += kWave) M[kEmDim * kEmDim + x] = (x / kEmDim == x % kEmDim) ? 1.0 : 0.0;
-    trace = to_sgpr(trace);
+    trace = es_sums(pr, n, lane, M);
     if (!finite_d(trace)) status = PNEC_HIP_EM_NOT_FINITE;
   }
   __syncthreads();
 
   if (status == PNEC_HIP_EM_OK) {
-    // ---- cyclic Jacobi on the 9x9 (pnec_eight_point.hip) -----------------------------------------------------------------
-    const double off_limit = (kEpOffTol * trace) * (kEpOffTol * trace), skip_limit = kEpSkipTol * trace;
-    const int row = lane < kEmRows ? lane : 0;
-    const bool upper = lane < kEmDim, active = lane < kEmRows;
-#pragma unroll 1
-    for (int sweep = 0; sweep < kEpMaxSweeps; ++sweep) {
-      double o = 0.0;
-#pragma unroll
-      for (int j = 0; j < kEmDim; ++j) {
-        const double v = M[row * kEmDim + j];
-        o = __builtin_fma((upper && j != lane) ? v : 0.0, v, o);
-      }
-      const double off2 = to_sgpr(wave_allreduce_sum(o));
-      if (!(off2 > off_limit)) break;
-#pragma unroll 1
-      for (int p = 0; p < kEmDim - 1; ++p)
-#pragma unroll 1
-        for (int q = p + 1; q < kEmDim; ++q) {
-          const double app = to_sgpr(M[p * kEmDim + p]), aqq = to_sgpr(M[q * kEmDim + q]), apq = to_sgpr(M[p * kEmDim + q]);
-          const double x = M[row * kEmDim + p], y = M[row * kEmDim + q];
-          if (!(fabs(apq) > skip_limit)) continue;
-          const double theta = 0.5 * (aqq - app) * fast_rcp(apq);
-          const double t = copysign(fast_rcp(fabs(theta) + fast_sqrt(__builtin_fma(theta, theta, 1.0))), theta);
-          const double c = fast_rsqrt(__builtin_fma(t, t, 1.0)), s = t * c;
-          const double nx = c * x - s * y, ny = s * x + c * y;
-          __syncthreads();   // every lane has read before any lane writes
-          if (active) {
-            const bool isp = upper && lane == p, isq = upper && lane == q;
-            M[row * kEmDim + p] = isp ? __builtin_fma(-t, apq, app) : (isq ? 0.0 : nx);
-            M[row * kEmDim + q] = isq ? __builtin_fma(t, apq, aqq) : (isp ? 0.0 : ny);
-            if (upper && !isp && !isq) {
-              M[p * kEmDim + row] = nx;
-              M[q * kEmDim + row] = ny;
-            }
-          }
-          __syncthreads();
-        }
-    }
+    es_jacobi(M, trace, lane);
 
     // ---- the null space: the eigenvalues ranked, the lowest index first among equals --------------------------------------
     const int nb = nister ? 4 : 2;
-    double d[kEmDim];
+    double d[kEsDim];
 #pragma unroll
-    for (int k = 0; k < kEmDim; ++k) d[k] = M[k * kEmDim + k];
+    for (int k = 0; k < kEsDim; ++k) d[k] = M[k * kEsDim + k];
     int col[4] = {0, 0, 0, 0};
     double lam_lo = 0.0, lam_hi = 0.0, lam8 = d[0];
 #pragma unroll
-    for (int k = 0; k < kEmDim; ++k) {
+    for (int k = 0; k < kEsDim; ++k) {
       int rank = 0;
 #pragma unroll
-      for (int j = 0; j < kEmDim; ++j) rank += (j != k && (d[j] < d[k] || (d[j] == d[k] && j < k))) ? 1 : 0;
+      for (int j = 0; j < kEsDim; ++j) rank += (j != k && (d[j] < d[k] || (d[j] == d[k] && j < k))) ? 1 : 0;
 #pragma unroll
       for (int b = 0; b < 4; ++b) col[b] = rank == b ? k : col[b];
       lam_lo = rank == nb - 1 ? d[k] : lam_lo;
@@ -436,7 +252,7 @@ __global__ __launch_bounds__(kWave) void essential_minimal_kernel(const Essentia
       const int c = nister ? col[3 - m] : (m == 0 ? col[1] : col[0]);
       const bool used = nister || m == 0 || m == 3;
 #pragma unroll
-      for (int k = 0; k < 9; ++k) Bv[m][k] = used ? M[(kEmDim + k) * kEmDim + c] : 0.0;
+      for (int k = 0; k < 9; ++k) Bv[m][k] = used ? M[(kEsDim + k) * kEsDim + c] : 0.0;
     }
 
     // ---- p(z), ascending coefficients; the rows of B(z) stay for the null vector -------------------------------------------
@@ -718,9 +534,9 @@ __global__ __launch_bounds__(kWave) void essential_minimal_kernel(const Essentia
         }
         // (x, y, 1) spans the null space of B(z): the cross product of two rows, the pair whose product is longest
         double c01[3], c02[3], c12[3];
-        em_cross(Bz[0], Bz[1], c01);
-        em_cross(Bz[0], Bz[2], c02);
-        em_cross(Bz[1], Bz[2], c12);
+        es_cross(Bz[0], Bz[1], c01);
+        es_cross(Bz[0], Bz[2], c02);
+        es_cross(Bz[1], Bz[2], c12);
         const double n01 = c01[0] * c01[0] + c01[1] * c01[1] + c01[2] * c01[2];
         const double n02 = c02[0] * c02[0] + c02[1] * c02[1] + c02[2] * c02[2];
         const double n12 = c12[0] * c12[0] + c12[1] * c12[1] + c12[2] * c12[2];
@@ -783,7 +599,7 @@ __global__ __launch_bounds__(kWave) void essential_minimal_kernel(const Essentia
         double nn = 0.0;
 #pragma unroll
         for (int k = 0; k < 9; ++k) nn = __builtin_fma(E[k], E[k], nn);
-        const double scl = em_sign(E) / sqrt(nn);
+        const double scl = es_sign(E) / sqrt(nn);
 #pragma unroll
         for (int k = 0; k < 9; ++k) E[k] = valid ? E[k] * scl : nan;
       }
@@ -811,7 +627,7 @@ __global__ __launch_bounds__(kWave) void essential_minimal_kernel(const Essentia
 #pragma unroll
       for (int k = 0; k < 9; ++k) e[k] = valid ? Es[lane * 9 + k] : nan;
 
-      // ---- SVD of every E through E'E (pnec_eight_point.hip, one lane per solution) -------------------------------------------
+      // ---- SVD of every E through E'E, one E per lane: the sweeps end by ballot, the rest is es_decompose's pieces ------------
       double B[9], V[9];
 #pragma unroll
       for (int x = 0; x < 3; ++x)
@@ -821,9 +637,9 @@ __global__ __launch_bounds__(kWave) void essential_minimal_kernel(const Essentia
       for (int k = 0; k < 9; ++k) V[k] = (k % 4 == 0) ? 1.0 : 0.0;
       {
         const double tr3 = B[0] + B[4] + B[8];
-        const double lim3 = (kEpOffTol * tr3) * (kEpOffTol * tr3);
+        const double lim3 = (kEsOffTol * tr3) * (kEsOffTol * tr3);
 #pragma unroll 1
-        for (int sweep = 0; sweep < kEpMaxSweeps; ++sweep) {
+        for (int sweep = 0; sweep < kEsMaxSweeps; ++sweep) {
           const double off2 = 2.0 * (B[1] * B[1] + B[2] * B[2] + B[5] * B[5]);
           const bool more = off2 > lim3;
           if (__builtin_amdgcn_ballot_w64(more) == 0) break;
@@ -833,9 +649,9 @@ __global__ __launch_bounds__(kWave) void essential_minimal_kernel(const Essentia
             Bn[k] = B[k];
             Vn[k] = V[k];
           }
-          em_rotate3<0, 1>(Bn, Vn);
-          em_rotate3<0, 2>(Bn, Vn);
-          em_rotate3<1, 2>(Bn, Vn);
+          es_rotate3<0, 1>(Bn, Vn);
+          es_rotate3<0, 2>(Bn, Vn);
+          es_rotate3<1, 2>(Bn, Vn);
 #pragma unroll
           for (int k = 0; k < 9; ++k) {   // a lane that has converged keeps what it has
             B[k] = more ? Bn[k] : B[k];
@@ -844,51 +660,24 @@ __global__ __launch_bounds__(kWave) void essential_minimal_kernel(const Essentia
         }
       }
       const double w0 = B[0], w1 = B[4], w2 = B[8];
-      const int i0 = (w0 >= w1 && w0 >= w2) ? 0 : (w1 >= w2 ? 1 : 2);
-      const int ja = i0 == 0 ? 1 : 0, jb = i0 == 2 ? 1 : 2;
-      const double wa = ja == 0 ? w0 : w1, wb = jb == 1 ? w1 : w2;
-      const int i2 = wb <= wa ? jb : ja, i1 = 3 - i0 - i2;
+      int i0, i1, i2;
+      es_order3(w0, w1, w2, i0, i1, i2);
       const double lam[3] = {i0 == 0 ? w0 : (i0 == 1 ? w1 : w2), i1 == 0 ? w0 : (i1 == 1 ? w1 : w2),
                              i2 == 0 ? w0 : (i2 == 1 ? w1 : w2)};
       double sing[3];
 #pragma unroll
       for (int k = 0; k < 3; ++k) sing[k] = sqrt(lam[k] > 0.0 ? lam[k] : 0.0);
       double v0[3], v1[3], v2[3], u0[3], u1[3], u2[3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        v0[k] = em_pick3(V, k, i0);
-        v1[k] = em_pick3(V, k, i1);
-        v2[k] = em_pick3(V, k, i2);
-      }
-      {
-        const double sg = em_sign(v2);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) v2[k] *= sg;
-        double cr[3];
-        em_cross(v1, v2, cr);
-        const double det = v0[0] * cr[0] + v0[1] * cr[1] + v0[2] * cr[2];
-        const double s1 = det < 0.0 ? -1.0 : 1.0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) v1[k] *= s1;
-      }
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        u0[k] = e[3 * k] * v0[0] + e[3 * k + 1] * v0[1] + e[3 * k + 2] * v0[2];
-        u1[k] = e[3 * k] * v1[0] + e[3 * k + 1] * v1[1] + e[3 * k + 2] * v1[2];
-      }
-      em_normalise(u0);
-      em_normalise(u1);
-      em_cross(u0, u1, u2);
-      em_normalise(u2);
+      es_right_vectors(V, i0, i1, i2, v0, v1, v2);
+      es_left_vectors(e, v0, v1, u0, u1, u2);
       if (lane < kEmMaxSolutions) {
+        double Ra[9], Rb[9];   // before their sign
+        es_rotations(u0, u1, u2, v0, v1, v2, Ra, Rb);
 #pragma unroll
-        for (int x = 0; x < 3; ++x)
-#pragma unroll
-          for (int y = 0; y < 3; ++y) {
-            const double m = u1[x] * v0[y] - u0[x] * v1[y], z = u2[x] * v2[y];
-            C[lane * kEmCand + 3 * x + y] = z + m;        // Ra before its sign
-            C[lane * kEmCand + 9 + 3 * x + y] = z - m;    // Rb
-          }
+        for (int k = 0; k < 9; ++k) {
+          C[lane * kEmCand + k] = Ra[k];
+          C[lane * kEmCand + 9 + k] = Rb[k];
+        }
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
           C[lane * kEmCand + 18 + k] = u2[k];
@@ -903,11 +692,7 @@ __global__ __launch_bounds__(kWave) void essential_minimal_kernel(const Essentia
       double R[9], t[3];
 #pragma unroll
       for (int k = 0; k < 9; ++k) R[k] = C[ci * kEmCand + ((cj & 1) ? 9 : 0) + k];
-      {
-        const double sd = em_det3(R) < 0.0 ? -1.0 : 1.0;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) R[k] *= sd;
-      }
+      es_signed_rotation(R);
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
         const double u = C[ci * kEmCand + 18 + k];
@@ -920,14 +705,14 @@ __global__ __launch_bounds__(kWave) void essential_minimal_kernel(const Essentia
 #pragma unroll 1
         for (int k = 0; k < K; ++k) {
           double f[6];
-          load6(k, f);
-          qs += em_term(f, R, t);
+          pr.load6(k, f);
+          qs += es_term(f, R, t);
         }
         qs = finite_d(qs) ? qs : __builtin_inf();
         quality = cand ? qs : nan;
         const double mine = cand ? qs : __builtin_inf();
         const double best = em_wave_min(mine);
-        if (best < kEpStartQuality) {
+        if (best < kEsStartQuality) {
           const unsigned long long at = __builtin_amdgcn_ballot_w64(cand && mine == best);
           choice = at ? (int)__builtin_ctzll(at) : -1;
         }
@@ -957,9 +742,7 @@ __global__ __launch_bounds__(kWave) void essential_minimal_kernel(const Essentia
         Rc[k] = C[ci * kEmCand + ((choice & 1) ? 9 : 0) + k];
         Ec[k] = Es[ci * 9 + k];
       }
-      const double sd = em_det3(Rc) < 0.0 ? -1.0 : 1.0;
-#pragma unroll
-      for (int k = 0; k < 9; ++k) Rc[k] *= sd;
+      es_signed_rotation(Rc);
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
         const double u = C[ci * kEmCand + 18 + k];
@@ -967,28 +750,9 @@ __global__ __launch_bounds__(kWave) void essential_minimal_kernel(const Essentia
         sing[k] = C[ci * kEmCand + 21 + k];
       }
     }
-    if (a.out_q) {
-      double q[4] = {nan, nan, nan, nan};
-      if (status == PNEC_HIP_EM_OK) em_quat(Rc, q);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) a.out_q[4 * pair + k] = q[k];
-    }
-    if (a.out_t) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) a.out_t[3 * pair + k] = tc[k];
-    }
-    if (a.out_E) {
-#pragma unroll
-      for (int k = 0; k < 9; ++k) a.out_E[9 * pair + k] = Ec[k];
-    }
-    if (a.out_singular) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) a.out_singular[3 * pair + k] = sing[k];
-    }
-    if (a.out_gap) a.out_gap[pair] = gap;
+    // (the number of solutions first: stored after `status`, a launch of pairs that are all TOO_FEW took 2 % longer)
     if (a.out_n_solutions) a.out_n_solutions[pair] = n_sol;
-    if (a.out_choice) a.out_choice[pair] = choice;
-    if (a.out_status) a.out_status[pair] = status;
+    es_store_pose(a, pair, status == PNEC_HIP_EM_OK, Rc, tc, Ec, sing, gap, choice, status);
   }
 }
 
