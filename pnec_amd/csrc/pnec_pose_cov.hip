@@ -1,6 +1,7 @@
 // pnec_pose_cov.hip -- pose covariance: the Gauss-Newton information J'J of a pair at a pose the caller passes in, and
 // its inverse lifted to a 6x6 covariance of (rotation vector, translation direction).  One pass over the pair's
-// resident SoA planes, a translation unit of its own (the solve / stream objects do not see it).
+// resident SoA planes, a translation unit of its own (the solve / stream objects do not see it).  Blocks, wavefronts, the
+// pose and the exchange of the wavefronts' sums: pnec_pose_pass.hpp.
 //
 // The residuals of the probabilistic families are whitened by the propagated variance, so J'J at the solution is the
 // inverse of the posterior covariance (Laplace approximation; what ceres::Covariance returns for the reference's
@@ -82,47 +83,35 @@ __device__ __forceinline__ bool spd_inverse5(const double (&H)[15], double (&S)[
   return ok && (z == 0.0);
 }
 
+// one wavefront's 21 sums
+struct CovSums {
+  double v[kNumAcc];
+  __device__ __forceinline__ void add(const CovSums &o) {
+#pragma unroll
+    for (int j = 0; j < kNumAcc; ++j) v[j] += o.v[j];
+  }
+};
+
 }  // namespace
 
 template <int MODE>
 __global__ __launch_bounds__(kCovMaxWaves *kWave) void pose_covariance_kernel(const PoseCovArgs a) {
   constexpr int NC = num_components(MODE);
-  __shared__ double part[kCovMaxWaves][kNumAcc];
+  __shared__ CovSums part[kCovMaxWaves];
   __shared__ double outbuf[kOutDoubles];
   __shared__ int32_t out_st;
 
-  const int64_t s = blockIdx.x;
-  const int64_t p = s / a.n_hyp;
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wave = to_sgpr((int)(threadIdx.x >> 6));
-  const int n = a.count[p];
-  const int stride = (n + kWave - 1) & ~(kWave - 1);
-  const double *base = a.data + a.block_offset[p];
-  // (the block is sized for the batch's largest pair, so the bound below never binds; it keeps a wrong size harmless)
-  const int W = min(cov_waves(n), (int)(blockDim.x >> 6));
+  const PoseSlot g = pose_slot(a.count, a.n_hyp);
+  const int64_t s = g.s;
+  const int lane = g.lane, wave = g.wave, n = g.n, stride = g.stride, W = g.W;
+  const double *base = a.data + a.block_offset[g.p];
 
-  // pose: q normalised as pnec_hip_cost_function does; (theta, phi) of t by AnglesFromVec (common.cc:103-116) -- as
-  // sines and cosines straight from the components, which keeps sin(theta)'s relative accuracy at the pole where
-  // acos loses it:  theta < 1e-10 (and t = 0) -> phi = 0.
-  double q[4] = {a.q[4 * s], a.q[4 * s + 1], a.q[4 * s + 2], a.q[4 * s + 3]};
-  const double qn = 1.0 / sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) q[k] *= qn;
-  const double tx = a.t[3 * s], ty = a.t[3 * s + 1], tz = a.t[3 * s + 2];
-  const double nrm = sqrt(tx * tx + ty * ty + tz * tz), rho = sqrt(tx * tx + ty * ty);
-  double st = rho / nrm, ct = tz / nrm, cp = tx / rho, sp = ty / rho;
-  if (nrm == 0.0) {
-    st = 0.0;
-    ct = 1.0;
-  }
-  if (rho == 0.0 || (st < 1e-10 && ct > 0.0)) {
-    cp = 1.0;
-    sp = 0.0;
-  }
+  // the pose goes to scalar registers: every lane holds the same bits, and eval_corr reads it in every term
+  double st, ct, cp, sp;
   PassUniforms U;
   {
     double R[9];
-    rot_from_quat(q, R);
+    pose_setup(a.q + 4 * s, a.t + 3 * s, R, st, ct, cp, sp);
 #pragma unroll
     for (int i = 0; i < 9; ++i) U.R[i] = to_sgpr(R[i]);
   }
@@ -145,21 +134,12 @@ __global__ __launch_bounds__(kCovMaxWaves *kWave) void pose_covariance_kernel(co
       accumulate(r, J, acc);
     }
   }
-  double sum[kNumAcc];
-  wave_reduce21(acc, sum);
-  if (blockDim.x > kWave) {   // (uniform: the launch's block size)
-    if (lane == 0 && wave > 0 && wave < W) {
-#pragma unroll
-      for (int j = 0; j < kNumAcc; ++j) part[wave][j] = sum[j];
-    }
-    __syncthreads();
-  }
+  CovSums total;
+  wave_reduce21(acc, total.v);
+  combine_waves(g, part, total);
 
   if (threadIdx.x == 0) {
-    for (int w = 1; w < W; ++w) {
-#pragma unroll
-      for (int j = 0; j < kNumAcc; ++j) sum[j] += part[w][j];
-    }
+    const double (&sum)[kNumAcc] = total.v;
     double z = 0.0;
 #pragma unroll
     for (int j = 0; j < kNumAcc; ++j) z = __builtin_fma(sum[j], 0.0, z);
@@ -225,25 +205,13 @@ __global__ __launch_bounds__(kCovMaxWaves *kWave) void pose_covariance_kernel(co
   }
 }
 
+template <int MODE>
+struct PoseCovKernel {
+  static constexpr auto run = &pose_covariance_kernel<MODE>;
+};
+
 hipError_t launch_pose_covariance(int mode, int64_t n_slots, int waves, const PoseCovArgs &a, hipStream_t stream) {
-  const dim3 grid((unsigned)n_slots), block((unsigned)(waves * kWave));
-  switch (mode) {
-    case PNEC_HIP_MODE_NEC:
-      hipLaunchKernelGGL(pose_covariance_kernel<PNEC_HIP_MODE_NEC>, grid, block, 0, stream, a);
-      break;
-    case PNEC_HIP_MODE_TARGET:
-      hipLaunchKernelGGL(pose_covariance_kernel<PNEC_HIP_MODE_TARGET>, grid, block, 0, stream, a);
-      break;
-    case PNEC_HIP_MODE_HOST:
-      hipLaunchKernelGGL(pose_covariance_kernel<PNEC_HIP_MODE_HOST>, grid, block, 0, stream, a);
-      break;
-    case PNEC_HIP_MODE_SYM:
-      hipLaunchKernelGGL(pose_covariance_kernel<PNEC_HIP_MODE_SYM>, grid, block, 0, stream, a);
-      break;
-    default:
-      return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return launch_by_mode<PoseCovKernel>(mode, n_slots, waves, a, stream);
 }
 
 }  // namespace pnec_hip

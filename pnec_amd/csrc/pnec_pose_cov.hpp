@@ -4,18 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-namespace pnec_hip {
+#include "pnec_pose_pass.hpp"   // cov_waves: the wavefronts of a pair follow from its own count
 
-// How many wavefronts sum one pair: one per 512 correspondences (eight per lane, the one-wavefront solve's share),
-// at most eight.  A function of the PAIR's own count, not of the launch: the block is sized for the batch's largest
-// pair and the wavefronts a smaller pair does not need only meet the barrier, so a pair's sums are added in the same
-// order -- have the same bits -- whatever batch it sits in.
-constexpr int kCovCorrPerWave = 512;
-constexpr int kCovMaxWaves = 8;
-__host__ __device__ constexpr int cov_waves(int n) {
-  const int w = (n + kCovCorrPerWave - 1) / kCovCorrPerWave;
-  return w < 1 ? 1 : (w > kCovMaxWaves ? kCovMaxWaves : w);
-}
+namespace pnec_hip {
 
 struct PoseCovArgs {
   const double *data;

@@ -2,10 +2,9 @@
 // and three exact order statistics of the ratios (lower quartile, lower median, upper quartile).  A translation unit of
 // its own; pnec_relative_scale.hpp has the definitions.
 //
-// Geometry: triangulate_kernel's.  One block per pair of the current batch, cov_waves(n_max) wavefronts of which the pair
-// uses W = cov_waves(n); correspondence i goes to wavefront (i / 64) mod W.  The current pair's six bearing planes are
-// read coalesced; the six bearing values of the linked correspondence are gathered from the previous pair's planes (one
-// 8-byte load per plane and lane, not coalesced: the link is a permutation).
+// Blocks, wavefronts, the poses and the plane loads: pnec_pose_pass.hpp, with one slot per pair of the current batch.  The
+// current pair's six bearing planes are read coalesced; the six bearing values of the linked correspondence are gathered
+// from the previous pair's planes (one 8-byte load per plane and lane, not coalesced: the link is a permutation).
 //
 // Pass 1 stores every ratio (NaN for a link that is not used) to a.ratio -- the caller's out_ratio or the handle's
 // workspace -- and counts.  A pair may be of any size, so the selection reads the ratios back from there; a thread reads
@@ -43,19 +42,13 @@ __global__ __launch_bounds__(kCovMaxWaves *kWave) void relative_scale_kernel(con
   __shared__ int32_t hist[3][kRsBins];
   __shared__ int32_t cnt[kCovMaxWaves][2];   // linked | used
 
-  const int64_t p = blockIdx.x;
+  const PoseSlot slot = pose_slot(a.count, a.offsets, 1);
+  const int64_t p = slot.p, e0 = slot.ob;
   const int tid = threadIdx.x;
-  const int lane = tid & (kWave - 1);
-  const int wave = to_sgpr((int)(tid >> 6));
-  const int n = a.count[p];
-  const int stride = (n + kWave - 1) & ~(kWave - 1);
-  // one scalar base and a 32-bit byte offset per load, as triangulate_kernel (the ABI layer refuses a batch whose
-  // largest pair has 4 GiB of planes or more, on either side)
+  const int lane = slot.lane, wave = slot.wave, n = slot.n, stride = slot.stride, W = slot.W;
+  // (the ABI layer refuses a batch whose largest pair has 4 GiB of planes or more, on either side)
   const char *base = reinterpret_cast<const char *>(a.data + a.block_offset[p]);
   const unsigned plane_bytes = (unsigned)stride * 8u;
-  // (the block is sized for the batch's largest pair, so the bound below never binds; it keeps a wrong size harmless)
-  const int W = min(cov_waves(n), (int)(blockDim.x >> 6));
-  const int64_t e0 = a.offsets[p] - a.offsets[0];
 
   const int64_t pp = a.prev_pair[p];
   const bool has_prev = pp >= 0 && pp < a.n_prev_pairs;   // uniform over the block
@@ -63,10 +56,16 @@ __global__ __launch_bounds__(kCovMaxWaves *kWave) void relative_scale_kernel(con
   const char *pbase = reinterpret_cast<const char *>(a.prev_data + (has_prev ? a.prev_block_offset[pp] : 0));
   const unsigned pplane_bytes = (unsigned)((n_prev + kWave - 1) & ~(kWave - 1)) * 8u;
 
-  double R[9], t[3], Rp[9], tp[3];
-  rs_pose(a.q + 4 * p, a.t + 3 * p, R, t);
+  double R[9], t[3], Rp[9], tp[3], st, ct, cp, sp;
+  pose_setup(a.q + 4 * p, a.t + 3 * p, R, st, ct, cp, sp);
+  t[0] = st * cp;
+  t[1] = st * sp;
+  t[2] = ct;
   if (has_prev) {
-    rs_pose(a.q_prev + 4 * pp, a.t_prev + 3 * pp, Rp, tp);
+    pose_setup(a.q_prev + 4 * pp, a.t_prev + 3 * pp, Rp, st, ct, cp, sp);
+    tp[0] = st * cp;
+    tp[1] = st * sp;
+    tp[2] = ct;
   } else {   // (nothing is linked: any pose will do)
 #pragma unroll
     for (int c = 0; c < 9; ++c) Rp[c] = (c % 4 == 0) ? 1.0 : 0.0;
@@ -88,13 +87,13 @@ __global__ __launch_bounds__(kCovMaxWaves *kWave) void relative_scale_kernel(con
       double f[6], g[6];
 #pragma unroll
       for (int c = 0; c < 6; ++c)
-        f[c] = *reinterpret_cast<const double *>(base + ((unsigned)c * plane_bytes + (unsigned)i * 8u));
+        f[c] = load_plane(base, plane_bytes, c, i);
 #pragma unroll
       for (int c = 0; c < 6; ++c) g[c] = 0.0;
       if (linked) {
 #pragma unroll
         for (int c = 0; c < 6; ++c)
-          g[c] = *reinterpret_cast<const double *>(pbase + ((unsigned)c * pplane_bytes + (unsigned)j * 8u));
+          g[c] = load_plane(pbase, pplane_bytes, c, j);
       }
       TriSystem cs, rs;
       tri_depths(f, R, t, cs);

@@ -20,7 +20,7 @@
 #include <stdint.h>
 
 #include "pnec_device.hpp"
-#include "pnec_triangulate.hpp"   // tri_depths / TriSystem, cov_waves
+#include "pnec_triangulate.hpp"   // tri_depths / TriSystem; through it pnec_pose_pass.hpp
 
 namespace pnec_hip {
 
@@ -50,30 +50,6 @@ struct RelativeScaleArgs {
 
 // one block of `waves` wavefronts per pair of the current batch
 hipError_t launch_relative_scale(int64_t n_pairs, int waves, const RelativeScaleArgs &a, hipStream_t stream);
-
-// the pose of a pair exactly as triangulate_kernel sets it up: q normalised, t as a direction through the sines and
-// cosines of its angles, t = 0 read as (0, 0, 1)
-__device__ __forceinline__ void rs_pose(const double *qp, const double *tp, double (&R)[9], double (&t)[3]) {
-  double q[4] = {qp[0], qp[1], qp[2], qp[3]};
-  const double qn = 1.0 / sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) q[k] *= qn;
-  const double tx = tp[0], ty = tp[1], tz = tp[2];
-  const double nrm = sqrt(tx * tx + ty * ty + tz * tz), rho = sqrt(tx * tx + ty * ty);
-  double st = rho / nrm, ct = tz / nrm, cp = tx / rho, sp = ty / rho;
-  if (nrm == 0.0) {
-    st = 0.0;
-    ct = 1.0;
-  }
-  if (rho == 0.0 || (st < 1e-10 && ct > 0.0)) {
-    cp = 1.0;
-    sp = 0.0;
-  }
-  rot_from_quat(q, R);
-  t[0] = st * cp;
-  t[1] = st * sp;
-  t[2] = ct;
-}
 
 // the parallax gate of one system (see the head of this file)
 __device__ __forceinline__ bool rs_parallax_ok(const TriSystem &s, double sin2_min, bool gate_a10) {

@@ -7,10 +7,10 @@
 // `gate` sigmas of the pose".  The pass writes r_i, den_i and that verdict per correspondence, and per slot sum r^2, the
 // same sum and the count over the gated set, and max |r|.  It classifies AT the pose it is given; it estimates nothing.
 //
-// r_i is eval_residual (pnec_residuals.hpp): eval_cost's operations in eval_cost's order.  The slot sums go lane by lane
-// through the stride of the pose-covariance pass (correspondence i in wavefront (i / 64) mod W, W = cov_waves(n)), the
-// tree of wave_reduce21 for accumulator 0 and the wavefronts' partials in wave order: no atomics, and a slot's bits
-// depend on its own pair and pose only.
+// r_i is eval_residual (pnec_residuals.hpp): eval_cost's operations in eval_cost's order.  Blocks, wavefronts, the pose
+// and the output offset: pnec_pose_pass.hpp.  The slot sums go lane by lane through that header's stride, the tree of
+// wave_reduce21 for accumulator 0 and the wavefronts' partials in wave order: no atomics, and a slot's bits depend on its
+// own pair and pose only.
 #include <hip/hip_runtime.h>
 
 #include "pnec_device.hpp"
@@ -18,46 +18,35 @@
 
 namespace pnec_hip {
 
+// what one wavefront found
+struct ResidualSums {
+  double chi2, gated, max_abs;
+  int32_t count, nan_seen;   // gated count | a NaN residual seen
+  __device__ __forceinline__ void add(const ResidualSums &o) {
+    chi2 += o.chi2;
+    gated += o.gated;
+    max_abs = fmax(max_abs, o.max_abs);
+    count += o.count;
+    nan_seen |= o.nan_seen;
+  }
+};
+
 template <int MODE>
 __global__ __launch_bounds__(kCovMaxWaves *kWave) void residuals_kernel(const ResidualArgs a) {
   constexpr int NC = num_components(MODE);
-  __shared__ double part[kCovMaxWaves][3];   // chi2 | gated chi2 | max |r|
-  __shared__ int32_t parti[kCovMaxWaves][2]; // gated count | a NaN residual seen
+  __shared__ ResidualSums part[kCovMaxWaves];
 
-  const int64_t s = blockIdx.x;
-  const int64_t p = s / a.n_hyp;
-  const int64_t h = s - p * a.n_hyp;
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wave = to_sgpr((int)(threadIdx.x >> 6));
-  const int n = a.count[p];
-  const int stride = (n + kWave - 1) & ~(kWave - 1);
-  const double *base = a.data + a.block_offset[p];
-  // (the block is sized for the batch's largest pair, so the bound below never binds; it keeps a wrong size harmless)
-  const int W = min(cov_waves(n), (int)(blockDim.x >> 6));
-  // where this slot's correspondences go: n_hyp * offsets[p] + h * N_p  (offsets relative to the batch's first pair)
-  const int64_t ob = (int64_t)a.n_hyp * (a.offsets[p] - a.offsets[0]) + h * (int64_t)n;
+  const PoseSlot g = pose_slot(a.count, a.offsets, a.n_hyp);
+  const int64_t s = g.s, ob = g.ob;
+  const int lane = g.lane, wave = g.wave, n = g.n, stride = g.stride, W = g.W;
+  const double *base = a.data + a.block_offset[g.p];
 
-  // pose: exactly pose_covariance_kernel's (q normalised; the sines and cosines of AnglesFromVec's angles straight
-  // from the components of t).  eval_residual reads R and t only.
-  double q[4] = {a.q[4 * s], a.q[4 * s + 1], a.q[4 * s + 2], a.q[4 * s + 3]};
-  const double qn = 1.0 / sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) q[k] *= qn;
-  const double tx = a.t[3 * s], ty = a.t[3 * s + 1], tz = a.t[3 * s + 2];
-  const double nrm = sqrt(tx * tx + ty * ty + tz * tz), rho = sqrt(tx * tx + ty * ty);
-  double st = rho / nrm, ct = tz / nrm, cp = tx / rho, sp = ty / rho;
-  if (nrm == 0.0) {
-    st = 0.0;
-    ct = 1.0;
-  }
-  if (rho == 0.0 || (st < 1e-10 && ct > 0.0)) {
-    cp = 1.0;
-    sp = 0.0;
-  }
+  // the pose goes to scalar registers, as in the covariance pass.  eval_residual reads R and t only.
+  double st, ct, cp, sp;
   PassUniforms U;
   {
     double R[9];
-    rot_from_quat(q, R);
+    pose_setup(a.q + 4 * s, a.t + 3 * s, R, st, ct, cp, sp);
 #pragma unroll
     for (int i = 0; i < 9; ++i) U.R[i] = to_sgpr(R[i]);
   }
@@ -95,52 +84,23 @@ __global__ __launch_bounds__(kCovMaxWaves *kWave) void residuals_kernel(const Re
   // chi2 through accumulator 0's tree, the gated sum through accumulator 11's (the other half of the same swaps):
   // after the two swap levels row 0 holds chi2's columns and row 2 the gated sum's
   const double c0 = row_allreduce_sum(swap_add16(swap_add32(chi2, gchi2), 0.0));
-  double sum_chi2 = read_lane<0>(c0), sum_g = read_lane<32>(c0);
-  double mxw = read_lane<0>(wave_allreduce_max(mx));
-  if (blockDim.x > kWave) {   // (uniform: the launch's block size)
-    if (lane == 0 && wave > 0 && wave < W) {
-      part[wave][0] = sum_chi2;
-      part[wave][1] = sum_g;
-      part[wave][2] = mxw;
-      parti[wave][0] = cnt;
-      parti[wave][1] = nan_seen;
-    }
-    __syncthreads();
-  }
+  ResidualSums total = {read_lane<0>(c0), read_lane<32>(c0), read_lane<0>(wave_allreduce_max(mx)), cnt, nan_seen};
+  combine_waves(g, part, total);
   if (threadIdx.x == 0) {
-    for (int w = 1; w < W; ++w) {
-      sum_chi2 += part[w][0];
-      sum_g += part[w][1];
-      mxw = fmax(mxw, part[w][2]);
-      cnt += parti[w][0];
-      nan_seen |= parti[w][1];
-    }
-    if (a.out_chi2) a.out_chi2[s] = sum_chi2;
-    if (a.out_gated_chi2) a.out_gated_chi2[s] = sum_g;
-    if (a.out_gated_count) a.out_gated_count[s] = cnt;
-    if (a.out_max_abs) a.out_max_abs[s] = nan_seen ? __builtin_nan("") : mxw;
+    if (a.out_chi2) a.out_chi2[s] = total.chi2;
+    if (a.out_gated_chi2) a.out_gated_chi2[s] = total.gated;
+    if (a.out_gated_count) a.out_gated_count[s] = total.count;
+    if (a.out_max_abs) a.out_max_abs[s] = total.nan_seen ? __builtin_nan("") : total.max_abs;
   }
 }
 
+template <int MODE>
+struct ResidualsKernel {
+  static constexpr auto run = &residuals_kernel<MODE>;
+};
+
 hipError_t launch_residuals(int mode, int64_t n_slots, int waves, const ResidualArgs &a, hipStream_t stream) {
-  const dim3 grid((unsigned)n_slots), block((unsigned)(waves * kWave));
-  switch (mode) {
-    case PNEC_HIP_MODE_NEC:
-      hipLaunchKernelGGL(residuals_kernel<PNEC_HIP_MODE_NEC>, grid, block, 0, stream, a);
-      break;
-    case PNEC_HIP_MODE_TARGET:
-      hipLaunchKernelGGL(residuals_kernel<PNEC_HIP_MODE_TARGET>, grid, block, 0, stream, a);
-      break;
-    case PNEC_HIP_MODE_HOST:
-      hipLaunchKernelGGL(residuals_kernel<PNEC_HIP_MODE_HOST>, grid, block, 0, stream, a);
-      break;
-    case PNEC_HIP_MODE_SYM:
-      hipLaunchKernelGGL(residuals_kernel<PNEC_HIP_MODE_SYM>, grid, block, 0, stream, a);
-      break;
-    default:
-      return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return launch_by_mode<ResidualsKernel>(mode, n_slots, waves, a, stream);
 }
 
 }  // namespace pnec_hip

@@ -6,7 +6,7 @@
 #include <stdint.h>
 
 #include "pnec_device.hpp"
-#include "pnec_pose_cov.hpp"   // cov_waves: the wavefronts of a pair follow from its own count
+#include "pnec_pose_pass.hpp"   // cov_waves: the wavefronts of a pair follow from its own count
 
 namespace pnec_hip {
 

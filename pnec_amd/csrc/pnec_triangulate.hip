@@ -2,9 +2,9 @@
 // that fixes the sign of t.  One pass over the pair's resident SoA planes, a translation unit of its own (the solve /
 // stream / front-stage objects do not see it).  pnec_triangulate.hpp has the definitions.
 //
-// Geometry: residuals_kernel's.  One block per slot (pair * n_hyp + h), cov_waves(n_max) wavefronts of which the pair
-// uses W = cov_waves(n); correspondence i goes to wavefront (i / 64) mod W.  The six bearing planes are always read, the
-// covariance planes only when the depth variance is wanted (wave-uniform).  Counts are popcounts of ballots; the
+// Blocks, wavefronts, the pose, the plane loads and the output offset: pnec_pose_pass.hpp.  The six bearing planes are
+// always read, the covariance planes only when the depth variance is wanted (wave-uniform).  Counts are popcounts of
+// ballots; the
 // parallax sum goes lane by lane, then through the tree of wave_reduce21 for accumulator 0 and the wavefronts' partials
 // in wave order: no atomics, a slot's bits depend on its own pair and pose only.
 //
@@ -26,46 +26,18 @@ __global__ __launch_bounds__(kCovMaxWaves *kWave) void triangulate_kernel(const 
   __shared__ double part[kCovMaxWaves];        // sweep 2: parallax sum
   __shared__ int32_t parti[kCovMaxWaves][3];   // sweep 2: front | back | left out of the parallax mean
 
-  const int64_t s = blockIdx.x;
-  const int64_t p = s / a.n_hyp;
-  const int64_t h = s - p * a.n_hyp;
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wave = to_sgpr((int)(threadIdx.x >> 6));
-  const int n = a.count[p];
-  const int stride = (n + kWave - 1) & ~(kWave - 1);
-  // one scalar base and a 32-bit byte offset per load (as the solve kernels' plane loads): a 64-bit index per plane
-  // costs scalar registers that the output pointers and the constants of the arctangent need.  The ABI layer refuses
-  // a batch whose largest pair has 4 GiB of planes or more.
-  const char *base = reinterpret_cast<const char *>(a.data + a.block_offset[p]);
+  const PoseSlot g = pose_slot(a.count, a.offsets, a.n_hyp);
+  const int64_t s = g.s, ob = g.ob;
+  const int lane = g.lane, wave = g.wave, n = g.n, stride = g.stride, W = g.W;
+  // load_plane's 32-bit offsets: a 64-bit index per plane costs scalar registers that the output pointers and the
+  // constants of the arctangent need
+  const char *base = reinterpret_cast<const char *>(a.data + a.block_offset[g.p]);
   const unsigned plane_bytes = (unsigned)stride * 8u;
-  auto plane = [&](int c, int i) {
-    return *reinterpret_cast<const double *>(base + ((unsigned)c * plane_bytes + (unsigned)i * 8u));
-  };
-  // (the block is sized for the batch's largest pair, so the bound below never binds; it keeps a wrong size harmless)
-  const int W = min(cov_waves(n), (int)(blockDim.x >> 6));
-  // where this slot's correspondences go: n_hyp * offsets[p] + h * N_p  (offsets relative to the batch's first pair)
-  const int64_t ob = (int64_t)a.n_hyp * (a.offsets[p] - a.offsets[0]) + h * (int64_t)n;
 
-  // pose: exactly residuals_kernel's (q normalised; t as a direction through the sines and cosines of its angles)
-  double q[4] = {a.q[4 * s], a.q[4 * s + 1], a.q[4 * s + 2], a.q[4 * s + 3]};
-  const double qn = 1.0 / sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) q[k] *= qn;
-  const double tx = a.t[3 * s], ty = a.t[3 * s + 1], tz = a.t[3 * s + 2];
-  const double nrm = sqrt(tx * tx + ty * ty + tz * tz), rho = sqrt(tx * tx + ty * ty);
-  double st = rho / nrm, ct = tz / nrm, cp = tx / rho, sp = ty / rho;
-  if (nrm == 0.0) {
-    st = 0.0;
-    ct = 1.0;
-  }
-  if (rho == 0.0 || (st < 1e-10 && ct > 0.0)) {
-    cp = 1.0;
-    sp = 0.0;
-  }
   // R stays in vector registers (every lane holds the same bits): the scalar file is full with the output pointers,
   // t and the constants of the arctangent, and nine more pairs there are spilled
-  double R[9], t[3];
-  rot_from_quat(q, R);
+  double R[9], t[3], st, ct, cp, sp;
+  pose_setup(a.q + 4 * s, a.t + 3 * s, R, st, ct, cp, sp);
   st = to_sgpr(st);
   t[0] = to_sgpr(st * cp);   t[1] = to_sgpr(st * sp);   t[2] = to_sgpr(ct);
 
@@ -82,7 +54,7 @@ __global__ __launch_bounds__(kCovMaxWaves *kWave) void triangulate_kernel(const 
       for (int i = wave * kWave + lane; i < stride; i += W * kWave) {
         double f[6];
 #pragma unroll
-        for (int c = 0; c < 6; ++c) f[c] = plane(c, i);
+        for (int c = 0; c < 6; ++c) f[c] = load_plane(base, plane_bytes, c, i);
         TriSystem ts;
         tri_depths(f, R, t, ts);
         // (a padding slot is all zeros: D = 0, neither front nor back)
@@ -120,12 +92,12 @@ __global__ __launch_bounds__(kCovMaxWaves *kWave) void triangulate_kernel(const 
     for (int i = wave * kWave + lane; i < stride; i += W * kWave) {
       double d[NC];
 #pragma unroll
-      for (int c = 0; c < 6; ++c) d[c] = plane(c, i);
+      for (int c = 0; c < 6; ++c) d[c] = load_plane(base, plane_bytes, c, i);
 #pragma unroll
       for (int c = 6; c < NC; ++c) d[c] = 0.0;
       if (want_var) {
 #pragma unroll
-        for (int c = 6; c < NC; ++c) d[c] = plane(c, i);
+        for (int c = 6; c < NC; ++c) d[c] = load_plane(base, plane_bytes, c, i);
       }
       TriCorr o;
       triangulate_corr<MODE>(d, R, t, want_var, o);
@@ -151,6 +123,8 @@ __global__ __launch_bounds__(kCovMaxWaves *kWave) void triangulate_kernel(const 
     }
   }
   double sum_psi = read_lane<0>(wave_reduce_acc0_row0(psum));
+  // combine_waves' exchange written out: one double and three counts as one parked struct pad to 24 bytes a wavefront,
+  // 32 bytes of LDS more than the two arrays
   if (many) {
     if (lane == 0 && wave > 0 && wave < W) {
       part[wave] = sum_psi;
@@ -195,25 +169,13 @@ __global__ __launch_bounds__(kCovMaxWaves *kWave) void triangulate_kernel(const 
   }
 }
 
+template <int MODE>
+struct TriangulateKernel {
+  static constexpr auto run = &triangulate_kernel<MODE>;
+};
+
 hipError_t launch_triangulate(int mode, int64_t n_slots, int waves, const TriangulateArgs &a, hipStream_t stream) {
-  const dim3 grid((unsigned)n_slots), block((unsigned)(waves * kWave));
-  switch (mode) {
-    case PNEC_HIP_MODE_NEC:
-      hipLaunchKernelGGL(triangulate_kernel<PNEC_HIP_MODE_NEC>, grid, block, 0, stream, a);
-      break;
-    case PNEC_HIP_MODE_TARGET:
-      hipLaunchKernelGGL(triangulate_kernel<PNEC_HIP_MODE_TARGET>, grid, block, 0, stream, a);
-      break;
-    case PNEC_HIP_MODE_HOST:
-      hipLaunchKernelGGL(triangulate_kernel<PNEC_HIP_MODE_HOST>, grid, block, 0, stream, a);
-      break;
-    case PNEC_HIP_MODE_SYM:
-      hipLaunchKernelGGL(triangulate_kernel<PNEC_HIP_MODE_SYM>, grid, block, 0, stream, a);
-      break;
-    default:
-      return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return launch_by_mode<TriangulateKernel>(mode, n_slots, waves, a, stream);
 }
 
 }  // namespace pnec_hip

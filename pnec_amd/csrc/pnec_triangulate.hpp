@@ -2,8 +2,8 @@
 // with the ABI layer, and the device function that triangulates one correspondence.
 //
 // Pose.  R maps frame-2 vectors into frame 1 and x1 = R x2 + t: camera 1 sits at the origin, camera 2 at t.  The pose
-// is set up exactly as residuals_kernel does: q is normalised inside, t is used as a DIRECTION (so the baseline is 1
-// and every length below is in baselines), and t = 0 is read as (0, 0, 1).
+// is pose_setup's (pnec_pose_pass.hpp): q is normalised inside, t is used as a DIRECTION (so the baseline is 1 and
+// every length below is in baselines), and t = 0 is read as (0, 0, 1).
 //
 // Midpoint triangulation (the system of reprojection_score in pnec_frontend.hip, bearings not assumed unit).  With
 // u = R f2:
@@ -43,7 +43,7 @@
 #include <stdint.h>
 
 #include "pnec_device.hpp"
-#include "pnec_pose_cov.hpp"   // cov_waves: the wavefronts of a pair follow from its own count
+#include "pnec_pose_pass.hpp"   // cov_waves: the wavefronts of a pair follow from its own count; pose_setup
 
 namespace pnec_hip {
 

@@ -25,9 +25,11 @@ using namespace pnec_hip;
 extern "C" void rs_link_host(int64_t n, const double *fc, const double *qc, const double *tc, const double *fp,
                              const double *qp, const double *tp, double sin2_min, int gate_a10, double *ratio,
                              uint8_t *used) {
-  double R[9], t[3], Rp[9], t2[3];
-  rs_pose(qc, tc, R, t);
-  rs_pose(qp, tp, Rp, t2);
+  double R[9], Rp[9], st, ct, cp, sp;
+  pose_setup(qc, tc, R, st, ct, cp, sp);
+  const double t[3] = {st * cp, st * sp, ct};
+  pose_setup(qp, tp, Rp, st, ct, cp, sp);
+  const double t2[3] = {st * cp, st * sp, ct};
   for (int64_t i = 0; i < n; ++i) {
     double f[6], g[6];
     for (int c = 0; c < 6; ++c) {
