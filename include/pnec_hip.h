@@ -751,6 +751,61 @@ int pnec_hip_essential_minimal(pnec_hip_problem *p, int32_t algorithm, int32_t f
                                double *out_E_all, double *out_quality, int32_t *out_choice, int32_t *out_status,
                                int space, void *stream);
 
+/* The RANSAC forms of the three closed-form baselines: a pose and an inlier mask per pair from its correspondences
+ * alone, no start rotation (added within ABI 8: a pure addition, PNEC_HIP_ABI_VERSION is unchanged).  This is the
+ * `ransac = true` branch of the reference's EMPoseEstimation (src/rel_pose_estimation/essential_matrix_methods.cc:56-75)
+ * for NISTER, SEVENPT and EIGHTPT.  opengv's CentralRelativePoseSacProblem and sac::Ransac::computeModel are restated
+ * from memory ([EXT]), with the constants of pnec_hip_ransac_eigensolver; rand() is that call's counter-based hash.
+ * Per pair p with N correspondences, (m, S) = (5, 8) NISTER, (7, 9) SEVENPT, (8, 9) EIGHTPT (the reference's sample
+ * sizes 5 + 3, 7 + 2, 8 + 1, common.cc:352-380):
+ *  1 Sample of attempt a = 0, 1, 2, ...: the first S distinct indices min(floor(u N), N - 1) with
+ *    u = rng_uniform(seed, first_pair_id + p, a, draw), draw = 0, 1, 2, ... -- the hash and the draw-until-distinct loop
+ *    of pnec_hip_ransac_eigensolver; all 64 bits of `seed` enter.
+ *  2 Model of an attempt.  Steps 1-3 of pnec_hip_essential_minimal (of pnec_hip_eight_point for EIGHTPT) on the sample's
+ *    rows 0..m-1; step 4, the choice over the four candidates of every solution, sums the quality over all S rows of the
+ *    sample in sample order.  The model is the chosen (R, unit t), R taking frame-2 vectors into frame 1.  An attempt has
+ *    no model if its sums are not finite (a sample row holds a NaN or an infinity), if there is no real solution, or if
+ *    no candidate's quality is below 1e6.
+ *  3 Score.  A correspondence's score at a model is the quality term (1 - f1.r1) + (1 - f2.r2) of the midpoint
+ *    triangulation (step 4 of pnec_hip_eight_point; opengv's reprojection error of CentralRelativePoseSacProblem [EXT]).
+ *    Inlier iff score < threshold; a score that is not finite is no inlier.
+ *  4 The sequential rule [EXT].  it = 0, a = 0, skipped = 0, k = 1, best = -1.  While it < k and
+ *    skipped < 10 max_iterations: take attempt a, ++a; no model: ++skipped and go on (not an iteration -- unlike
+ *    pnec_hip_ransac_eigensolver, where a capped hypothesis scores zero: here the first attempt may fail while k is 1);
+ *    otherwise count its inliers c over all N rows; c > best: the attempt becomes the best, best = c, w = c / N,
+ *    p_no = min(max(1 - w^S, 2^-52), 1 - 2^-52) (w^S by squaring), k = log(1 - 0.99) / log(p_no); ++it; it >
+ *    max_iterations: stop.  No refit follows (essential_matrix_methods.cc:72-75 returns model_coefficients_ as it is).
+ *  5 Status, pnec_hip_er_status.  TOO_FEW: N < S.  NO_MODEL: the rule ended with best = -1.  Both write NaN to the
+ *    doubles, -1 to out_best_attempt and zeros to the mask and the count; TOO_FEW also 0 to out_iterations and
+ *    out_attempts, NO_MODEL what the rule counted.
+ *
+ * Outputs for P pairs; every pointer may be NULL (not wanted), not all of them.
+ *   out_q [P,4] xyzw, out_t [P,3] unit: the best attempt's model   out_E [P,9]: its chosen solution
+ *   out_singular [P,3]: that solution's singular values
+ *   out_inlier_mask uint8 [sum N], in the caller's correspondence order as pnec_hip_ransac_eigensolver writes it
+ *   out_inlier_count int32 [P]: the mask's sum   out_iterations int32 [P]: it   out_attempts int32 [P]: a
+ *   out_best_attempt int32 [P]: the index a of the winning attempt   out_status int32 [P]
+ * A pair's bits depend on its own rows, `algorithm`, `seed`, first_pair_id + p, `max_iterations` and `threshold` only:
+ * not on the batch around it and not on the memory space (no atomics, fixed reduction order).
+ *
+ * All four problem modes (only the six bearing planes are read); batches made by pnec_hip_problem_select(_view) and
+ * reshaped capacity batches included.  DEVICE space: nothing waits, nothing is allocated, the call is asynchronous on
+ * `stream`.  HOST space: the outputs are staged on the device and the call blocks.
+ * NULL problem, an `algorithm` other than the three, max_iterations < 0, a threshold that is not finite and positive,
+ * first_pair_id < 0, all outputs NULL or a bad `space`: PNEC_HIP_ERR_INVALID_ARGUMENT before the handle is read or any
+ * device is touched. */
+#define PNEC_HIP_EM_EIGHTPT 3 /* beside PNEC_HIP_EM_NISTER 1, PNEC_HIP_EM_SEVENPT 2: the values of algorithm_t */
+typedef enum pnec_hip_er_status {
+  PNEC_HIP_ER_OK = 0,
+  PNEC_HIP_ER_TOO_FEW = 1,
+  PNEC_HIP_ER_NO_MODEL = 2
+} pnec_hip_er_status;
+int pnec_hip_essential_ransac(pnec_hip_problem *p, int32_t algorithm, uint64_t seed, int64_t first_pair_id,
+                              int32_t max_iterations, double threshold, double *out_q, double *out_t, double *out_E,
+                              double *out_singular, uint8_t *out_inlier_mask, int32_t *out_inlier_count,
+                              int32_t *out_iterations, int32_t *out_attempts, int32_t *out_best_attempt,
+                              int32_t *out_status, int space, void *stream);
+
 /* Relative scale between consecutive pairs from linked tracks (added within ABI 8: a pure addition,
  * PNEC_HIP_ABI_VERSION is unchanged).  Every pose carries t as a direction, so each pair is reconstructed with a
  * baseline of 1; a track seen in three consecutive frames has a depth from the shared middle camera in both

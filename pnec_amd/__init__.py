@@ -16,7 +16,7 @@ Layout:
   distributed.py   one-process-per-GPU sharding of independent pair batches + one RCCL gather
 """
 from . import capi  # noqa: F401
-from .batch import (Batch, EightPoint, MinimalPose, PoseCovariance, RelativeScale, ResidualReport, SolveResult, Triangulation, gate_sigma,  # noqa: F401
+from .batch import (Batch, EightPoint, EssentialRansac, MinimalPose, PoseCovariance, RelativeScale, ResidualReport, SolveResult, Triangulation, gate_sigma,  # noqa: F401
                     select_best)
 from .keyframes import KeyframePairs, KeyframeState, KeyframeTracker, keyframe_pairs  # noqa: F401
 from .odometry import Odometry, OdometryResult  # noqa: F401
@@ -29,5 +29,5 @@ from .undistort import Undistorted, camera_array, undistort_keypoints  # noqa: F
 from .trajectory import (Trajectory, TrajectoryMetrics, compose_trajectory, matched, stack_steps,  # noqa: F401
                          trajectory_metrics)
 
-__all__ = ["capi", "Batch", "EightPoint", "KeyframePairs", "KeyframeState", "KeyframeTracker", "Keypoints", "MinimalPose", "Odometry", "OdometryResult", "PATTERN52", "PatchCovariance", "PatchStore", "PatchTrack", "PoseCovariance", "RelativeScale", "ResidualReport", "SolveResult",
+__all__ = ["capi", "Batch", "EightPoint", "EssentialRansac", "KeyframePairs", "KeyframeState", "KeyframeTracker", "Keypoints", "MinimalPose", "Odometry", "OdometryResult", "PATTERN52", "PatchCovariance", "PatchStore", "PatchTrack", "PoseCovariance", "RelativeScale", "ResidualReport", "SolveResult",
            "TrackSet", "Tracker", "Trajectory", "TrajectoryMetrics", "Triangulation", "Undistorted", "add_patches", "append_tracks", "camera_array", "chain_scales", "compose_trajectory", "detect_keypoints", "gate_sigma", "image_pyramid", "keyframe_pairs", "matched", "new_patch_store", "patch_covariance", "patch_track", "patch_track_stored", "retain_tracks", "select_best", "stack_steps", "trajectory_metrics", "undistort_keypoints"]

@@ -219,6 +219,26 @@ class MinimalPose:
 
 
 @dataclass
+class EssentialRansac:
+    """pnec_hip_essential_ransac's outputs (include/pnec_hip.h has the definitions): the pose of the best five-, seven- or
+    eight-point model among random samples and its inliers, from correspondences alone.  Per pair [P]; where `status` is
+    not capi.ER_OK, q, t, E and singular are NaN, best_attempt is -1 and the pair's part of the mask is zero."""
+    q: object             # [P,4] xyzw; R takes frame-2 vectors into frame 1
+    t: object             # [P,3] unit direction in frame 1
+    E: object             # [P,9] the best attempt's chosen solution, row-major, unit norm
+    singular: object      # [P,3] its singular values, descending
+    mask: object          # [sum N] uint8 in the batch's correspondence order: what Batch.select takes
+    count: object         # [P] int32, the mask's sum per pair
+    iterations: object    # [P] int32, attempts that had a model (the rule's `it`)
+    attempts: object      # [P] int32, samples drawn
+    best_attempt: object  # [P] int32, the index of the winning sample
+    status: object        # [P] int32, capi.ER_OK / ER_TOO_FEW / ER_NO_MODEL
+
+
+_ER_ALGORITHMS = {"nister": capi.EM_NISTER, "sevenpt": capi.EM_SEVENPT, "eightpt": capi.EM_EIGHTPT}
+
+
+@dataclass
 class RelativeScale:
     """pnec_hip_relative_scale's outputs (include/pnec_hip.h has the definitions): the ratio of each pair's baseline to
     its previous pair's, from the tracks the two pairs share.  Per pair [P]: `scale` (the lower median of the used
@@ -957,6 +977,37 @@ class Batch:
         det(W + aX) = 0 and the pose chosen among their decompositions; the sample is min(9, N).  Otherwise as
         five_point."""
         return self._essential_minimal(capi.EM_SEVENPT, quality, on_device)
+
+    def essential_ransac(self, algorithm, seed: int = 1, max_iterations: int = 5000, threshold: float = 1e-6,
+                         first_pair_id: int = 0, on_device: bool | None = None) -> EssentialRansac:
+        """RANSAC around the five-point, seven-point or eight-point solver (pnec_hip_essential_ransac): a pose and an
+        inlier mask per pair from its correspondences alone, no start rotation.  `algorithm` is "nister", "sevenpt" or
+        "eightpt" (or capi.EM_NISTER / EM_SEVENPT / EM_EIGHTPT).  Pair p draws its samples from
+        (seed, first_pair_id + p), so a pair taken alone with first_pair_id set to its index has the bits it had in the
+        batch.  Spaces as eight_point (`on_device` overrides); the mask's length is the batch's number of
+        correspondences, which a batch made by select() waits for."""
+        alg = _ER_ALGORITHMS.get(algorithm.lower(), None) if isinstance(algorithm, str) else int(algorithm)
+        if alg not in _ER_ALGORITHMS.values():
+            raise ValueError('algorithm must be "nister", "sevenpt" or "eightpt"')
+        if on_device is None:
+            on_device = bool(getattr(self, "_on_device", False))
+        P, M = self.n_pairs, self.num_correspondences
+        shapes = ((P, 4), (P, 3), (P, 9), (P, 3), (max(M, 1),), (P,), (P,), (P,), (P,), (P,))
+        if on_device:
+            import torch
+            kinds = (torch.float64,) * 4 + (torch.uint8,) + (torch.int32,) * 5
+            out = [torch.empty(sh, dtype=k, device=f"cuda:{self.device}") for sh, k in zip(shapes, kinds)]
+            ptrs = [o.data_ptr() for o in out]
+            space, stream = capi.MEM_DEVICE, torch.cuda.current_stream(self.device).cuda_stream
+        else:
+            kinds = (np.float64,) * 4 + (np.uint8,) + (np.int32,) * 5
+            out = [np.zeros(sh, dtype=k) for sh, k in zip(shapes, kinds)]
+            ptrs = [o.ctypes.data for o in out]
+            space, stream = capi.MEM_HOST, None
+        capi.check(self._lib.pnec_hip_essential_ransac(self._h, alg, int(seed), int(first_pair_id), int(max_iterations),
+                                                       float(threshold), *ptrs, space, stream))
+        out[4] = out[4][:M]
+        return EssentialRansac(*out)
 
     def relative_scale(self, prev, prev_pair, link, q, t, q_prev, t_prev, min_parallax: float = 0.0,
                        per_link: bool = True) -> RelativeScale:

@@ -32,6 +32,10 @@ EM_MAX_SOLUTIONS = 10
 EM_OK, EM_TOO_FEW, EM_NOT_FINITE, EM_NO_CANDIDATE, EM_NO_SOLUTION = 0, 1, 2, 3, 4
 EM_NAMES = {EM_OK: "ok", EM_TOO_FEW: "too_few", EM_NOT_FINITE: "not_finite", EM_NO_CANDIDATE: "no_candidate",
             EM_NO_SOLUTION: "no_solution"}
+# pnec_hip_essential_ransac: the third algorithm and pnec_hip_er_status
+EM_EIGHTPT = 3
+ER_OK, ER_TOO_FEW, ER_NO_MODEL = 0, 1, 2
+ER_NAMES = {ER_OK: "ok", ER_TOO_FEW: "too_few", ER_NO_MODEL: "no_model"}
 # pnec_hip_eigensolver_scheme: which iteration stands in for opengv's eigenvalue minimisation (include/pnec_hip.h)
 ES_NEWTON, ES_DESCENT, ES_LM = 0, 1, 2
 # PNEC_HIP_RANSAC_* bits (pnec_hip_pipeline_options.ransac_flags, pnec_hip_problem_set_ransac_flags)
@@ -88,6 +92,7 @@ SYMBOLS = [
     "pnec_hip_triangulate",
     "pnec_hip_eight_point",
     "pnec_hip_essential_minimal",
+    "pnec_hip_essential_ransac",
     "pnec_hip_relative_scale",
     "pnec_hip_patch_covariance",
     "pnec_hip_image_pyramid_level",
@@ -253,6 +258,8 @@ def lib() -> C.CDLL:
     L.pnec_hip_triangulate.argtypes = [_vp, _vp, _vp, C.c_int32, C.c_int32] + [_vp] * 11 + [C.c_int, _vp]
     L.pnec_hip_eight_point.argtypes = [_vp, C.c_int32] + [_vp] * 8 + [C.c_int, _vp]
     L.pnec_hip_essential_minimal.argtypes = [_vp, C.c_int32, C.c_int32] + [_vp] * 10 + [C.c_int, _vp]
+    L.pnec_hip_essential_ransac.argtypes = [_vp, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.c_double] + [_vp] * 10 + \
+        [C.c_int, _vp]
     L.pnec_hip_undistort_keypoints.argtypes = [C.c_int, C.c_int64] + [_vp] * 5 + [C.c_int32, C.c_int32, C.c_uint32] + \
         [_vp] * 6 + [C.c_int, _vp]
     L.pnec_hip_trajectory_compose.argtypes = [C.c_int, C.c_int64, _vp, C.c_int64] + [_vp] * 8 + [C.c_int, _vp]

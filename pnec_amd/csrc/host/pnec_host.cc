@@ -1289,6 +1289,31 @@ SE3d MinimalEMPoseEstimation(const bearingVectors_t &bvs1, const bearingVectors_
   return SE3d(Quaterniond(q[3], q[0], q[1], q[2]).toRotationMatrix(), Vector3d(t[0], t[1], t[2]) * singular[0]);
 }
 
+SE3d RansacEMPoseEstimation(const bearingVectors_t &bvs1, const bearingVectors_t &bvs2, const SE3d &initial_pose,
+                            algorithm_t algorithm, std::vector<int> *inliers, int max_iterations, double threshold,
+                            uint64_t seed) {
+  if (algorithm == STEWENIUS)
+    throw std::invalid_argument("RansacEMPoseEstimation: STEWENIUS is not built (NISTER, SEVENPT and EIGHTPT are)");
+  if (algorithm != NISTER && algorithm != SEVENPT && algorithm != EIGHTPT)
+    throw std::invalid_argument("RansacEMPoseEstimation: unknown algorithm");
+  if (bvs1.size() != bvs2.size()) throw std::invalid_argument("bvs1 and bvs2 differ in size");
+  if (inliers) inliers->clear();
+  if (bvs1.empty()) return initial_pose;
+  Problem batch(optimization::SolverOptions().device, PNEC_HIP_MODE_NEC, {0, (int64_t)bvs1.size()});
+  Check(pnec_hip_problem_fill(batch.p, 0, 1, bvs1[0].data(), bvs2[0].data(), nullptr, nullptr, PNEC_HIP_MEM_HOST, nullptr));
+  double q[4], t[3], singular[3];
+  int32_t status = PNEC_HIP_ER_OK;
+  std::vector<uint8_t> mask(bvs1.size());
+  // (algorithm_t's values are the ABI's: NISTER 1, SEVENPT 2, EIGHTPT 3)
+  Check(pnec_hip_essential_ransac(batch.p, (int32_t)algorithm, seed, 0, max_iterations, threshold, q, t, nullptr, singular,
+                                  mask.data(), nullptr, nullptr, nullptr, nullptr, &status, PNEC_HIP_MEM_HOST, nullptr));
+  if (status != PNEC_HIP_ER_OK) return initial_pose;
+  if (inliers)
+    for (size_t i = 0; i < mask.size(); ++i)
+      if (mask[i]) inliers->push_back((int)i);
+  return SE3d(Quaterniond(q[3], q[0], q[1], q[2]).toRotationMatrix(), Vector3d(t[0], t[1], t[2]) * singular[0]);
+}
+
 }  // namespace rel_pose_estimation
 
 namespace odometry {

@@ -498,6 +498,16 @@ SE3d EMPoseEstimation(const bearingVectors_t &bvs1, const bearingVectors_t &bvs2
 // initial_pose where the call finds no pose as EMPoseEstimation; any other algorithm throws std::invalid_argument.
 SE3d MinimalEMPoseEstimation(const bearingVectors_t &bvs1, const bearingVectors_t &bvs2, const SE3d &initial_pose,
                              algorithm_t algorithm);
+// The RANSAC forms, again under a name of their own (EMPoseEstimation(..., ransac = true) keeps throwing): the
+// ransac == true branch of essential_matrix_methods.cc:56-75 for NISTER, SEVENPT and EIGHTPT on the device --
+// pnec_hip_essential_ransac, opengv's CentralRelativePoseSacProblem and Ransac restated, its rand() a hash of `seed`.
+// max_iterations and threshold default to the reference's.  `inliers`, when given, receives the indices of the best
+// model's inliers in ascending order.  Rotation and translation (of length s0 of the chosen solution) as above;
+// initial_pose (and no inliers) where the call finds no model or has fewer correspondences than a sample.  STEWENIUS
+// throws std::invalid_argument saying that it is not built.
+SE3d RansacEMPoseEstimation(const bearingVectors_t &bvs1, const bearingVectors_t &bvs2, const SE3d &initial_pose,
+                            algorithm_t algorithm, std::vector<int> *inliers = nullptr, int max_iterations = 5000,
+                            double threshold = 1e-6, uint64_t seed = 1);
 
 }  // namespace rel_pose_estimation
 

@@ -403,6 +403,28 @@ arr minimal_pose(arr bvs1, arr bvs2, pnec::rel_pose_estimation::algorithm_t algo
 arr five_point(arr bvs1, arr bvs2) { return minimal_pose(bvs1, bvs2, pnec::rel_pose_estimation::NISTER); }
 arr seven_point(arr bvs1, arr bvs2) { return minimal_pose(bvs1, bvs2, pnec::rel_pose_estimation::SEVENPT); }
 
+// RansacEMPoseEstimation(bvs1, bvs2, identity, algorithm, ...): (4x4, inlier indices)
+py::tuple essential_ransac(arr bvs1, arr bvs2, const std::string &algorithm, int max_iterations, double threshold,
+                           uint64_t seed) {
+  namespace rp = pnec::rel_pose_estimation;
+  rp::algorithm_t alg;
+  if (algorithm == "nister") alg = rp::NISTER;
+  else if (algorithm == "sevenpt") alg = rp::SEVENPT;
+  else if (algorithm == "eightpt") alg = rp::EIGHTPT;
+  else throw std::invalid_argument("algorithm must be \"nister\", \"sevenpt\" or \"eightpt\"");
+  const auto b1 = ToBearings(bvs1, "bvs_1"), b2 = ToBearings(bvs2, "bvs_2");
+  pnec::SE3d result;
+  std::vector<int> inliers;
+  {
+    py::gil_scoped_release release;
+    result = rp::RansacEMPoseEstimation(b1, b2, pnec::SE3d(), alg, &inliers, max_iterations, threshold, seed);
+  }
+  py::array_t<int> idx((py::ssize_t)inliers.size());
+  auto w = idx.mutable_unchecked<1>();
+  for (py::ssize_t i = 0; i < (py::ssize_t)inliers.size(); ++i) w(i) = inliers[(size_t)i];
+  return py::make_tuple(FromPose(result), idx);
+}
+
 // (scale, q25, q75, n_used, ratio [N]) of one frame against the previous one
 py::tuple relative_scale(arr bvs_prev1, arr bvs_prev2, arr pose_prev, arr bvs1, arr bvs2, arr pose,
                          const std::vector<int> &link, double min_parallax) {
@@ -763,6 +785,12 @@ PYBIND11_MODULE(pypnec, m) {
   m.def("seven_point", &seven_point, py::arg("bvs1"), py::arg("bvs2"),
         "pnec::rel_pose_estimation::MinimalEMPoseEstimation(bvs1, bvs2, identity, SEVENPT) (device): the same of the "
         "seven-point solver");
+  m.def("essential_ransac", &essential_ransac, py::arg("bvs1"), py::arg("bvs2"), py::arg("algorithm"),
+        py::arg("max_iterations") = 5000, py::arg("threshold") = 1e-6, py::arg("seed") = 1,
+        "pnec::rel_pose_estimation::RansacEMPoseEstimation(bvs1, bvs2, identity, algorithm, ...) (device): RANSAC around "
+        "the \"nister\", \"sevenpt\" or \"eightpt\" solver; returns (the 4x4 pose, translation of length s0, and the indices "
+        "of its inliers); the identity and no inliers when the pair gives no model -- include/pnec_hip.h "
+        "pnec_hip_essential_ransac");
   m.def("relative_scale", &relative_scale, py::arg("bvs_prev1"), py::arg("bvs_prev2"), py::arg("pose_prev"),
         py::arg("bvs1"), py::arg("bvs2"), py::arg("pose"), py::arg("link"), py::arg("min_parallax") = 0.0,
         "pnec::common::RelativeScale (addition; device): (scale, q25, q75, n_used, ratio [N]) -- the baseline of `pose` in "

@@ -25,6 +25,7 @@
 #include "pnec_residuals.hpp"
 #include "pnec_eight_point.hpp"
 #include "pnec_essential_minimal.hpp"
+#include "pnec_essential_ransac.hpp"
 #include "pnec_undistort.hpp"
 #include "pnec_trajectory.hpp"
 #include "pnec_relative_scale.hpp"
@@ -1478,6 +1479,58 @@ int pnec_hip_essential_minimal(pnec_hip_problem *p, int32_t algorithm, int32_t f
   io.out(a.out_status, out_status, P);
   if (int rc = io.commit()) return rc;
   PNEC_HIP_TRY(launch_essential_minimal(P, a, stream));
+  return io.finish();
+}
+
+// the RANSAC forms of the five-, seven- and eight-point baselines, pose and inlier mask of every pair:
+// pnec_essential_ransac.hip
+int pnec_hip_essential_ransac(pnec_hip_problem *p, int32_t algorithm, uint64_t seed, int64_t first_pair_id,
+                              int32_t max_iterations, double threshold, double *out_q, double *out_t, double *out_E,
+                              double *out_singular, uint8_t *out_inlier_mask, int32_t *out_inlier_count,
+                              int32_t *out_iterations, int32_t *out_attempts, int32_t *out_best_attempt,
+                              int32_t *out_status, int space, void *stream_) {
+  if (!p) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "essential_ransac: problem is NULL");
+  if (algorithm != PNEC_HIP_EM_NISTER && algorithm != PNEC_HIP_EM_SEVENPT && algorithm != PNEC_HIP_EM_EIGHTPT)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "essential_ransac: algorithm is none of NISTER, SEVENPT, EIGHTPT");
+  if (max_iterations < 0) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "essential_ransac: max_iterations < 0");
+  if (!std::isfinite(threshold) || !(threshold > 0.0))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "essential_ransac: threshold is not finite and positive");
+  if (first_pair_id < 0) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "essential_ransac: first_pair_id < 0");
+  if (!out_q && !out_t && !out_E && !out_singular && !out_inlier_mask && !out_inlier_count && !out_iterations &&
+      !out_attempts && !out_best_attempt && !out_status)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "essential_ransac: every output is NULL");
+  if (int rc = check_space("essential_ransac: ", space)) return rc;
+  const int64_t P = p->n_pairs;
+  if (P > 0x7fffffffLL) return fail(PNEC_HIP_ERR_UNSUPPORTED, "more than 2^31-1 pairs in one call");
+  if (P == 0) return 0;
+  hipStream_t stream = (hipStream_t)stream_;
+  CallArrays io(p, space, stream);
+  // HOST space: the mask's length is the batch's own total, so a batch made by select waits for its sizes here.
+  // (DEVICE space needs no host-side number: the kernel reads the batch's offsets.)
+  if (io.host() && out_inlier_mask)
+    if (int rc = materialize(p)) return rc;
+  EssentialRansacArgs a;
+  a.data = p->d_data;
+  a.block_offset = p->d_block_offset;
+  a.offsets = p->d_offsets;
+  a.count = p->d_count;
+  a.algorithm = algorithm;
+  a.max_iterations = max_iterations;
+  a.seed = seed;
+  a.first_pair_id = (uint64_t)first_pair_id;
+  a.threshold = threshold;
+  io.out(a.out_q, out_q, 4 * P);
+  io.out(a.out_t, out_t, 3 * P);
+  io.out(a.out_E, out_E, 9 * P);
+  io.out(a.out_singular, out_singular, 3 * P);
+  io.out(a.out_inlier_mask, out_inlier_mask, p->n_corr);
+  io.out(a.out_inlier_count, out_inlier_count, P);
+  io.out(a.out_iterations, out_iterations, P);
+  io.out(a.out_attempts, out_attempts, P);
+  io.out(a.out_best_attempt, out_best_attempt, P);
+  io.out(a.out_status, out_status, P);
+  if (int rc = io.commit()) return rc;
+  PNEC_HIP_TRY(launch_essential_ransac(P, a, stream));
   return io.finish();
 }
 

@@ -3,7 +3,8 @@
 // include/pnec_hip.h has the definitions; this file says how the wavefront is used.
 //
 // One block of one wavefront per pair, as the front stages' sums kernel.  Four phases, every branch wave-uniform; the
-// first three are the functions of pnec_essential_shared.hpp, which the minimal solvers' kernel calls too:
+// first is es_sums of pnec_essential_shared.hpp, the other three are ep_model of pnec_essential_model.hpp, which the
+// RANSAC kernel calls once per attempt:
 //   sums    es_sums: lane l takes correspondences l, l + 64, ...: nine products f1_a f2_b and 45 FMAs into 45
 //           accumulators; each accumulator then goes through wave_allreduce_sum (the DPP / permlane butterfly of
 //           pnec_device.hpp), always the same tree.  This phase is all of the memory traffic: the six bearing planes,
@@ -21,6 +22,7 @@
 
 #include "pnec_device.hpp"
 #include "pnec_eight_point.hpp"
+#include "pnec_essential_model.hpp"
 #include "pnec_essential_shared.hpp"
 
 namespace pnec_hip {
@@ -53,95 +55,12 @@ __global__ __launch_bounds__(kWave) void eight_point_kernel(const EightPointArgs
   __syncthreads();
 
   if (status == PNEC_HIP_EP_OK) {
-    es_jacobi(M, trace, lane);
-
-    // ---- the null vector and the gap -----------------------------------------------------------------------------------
-    double d[kEsDim];
-#pragma unroll
-    for (int k = 0; k < kEsDim; ++k) d[k] = M[k * kEsDim + k];
-    int imin = 0;
-    double lam0 = d[0], lam8 = d[0];
-#pragma unroll
-    for (int k = 1; k < kEsDim; ++k) {
-      if (d[k] < lam0) {
-        lam0 = d[k];
-        imin = k;
-      }
-      lam8 = d[k] > lam8 ? d[k] : lam8;
-    }
-    double lam1 = __builtin_inf();
-#pragma unroll
-    for (int k = 0; k < kEsDim; ++k) lam1 = (k != imin && d[k] < lam1) ? d[k] : lam1;
-    gap = (lam1 - lam0) / lam8;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) E[k] = M[(kEsDim + k) * kEsDim + imin];
-    {
-      double nn = 0.0;
-#pragma unroll
-      for (int k = 0; k < 9; ++k) nn = __builtin_fma(E[k], E[k], nn);
-      const double sc = es_sign(E) / sqrt(nn);
-#pragma unroll
-      for (int k = 0; k < 9; ++k) E[k] *= sc;
-    }
-
-    // ---- SVD of E through E'E, the two rotations ----------------------------------------------------------------------
-    double u2[3], Ra[9], Rb[9];
-    es_decompose(E, sing, u2, Ra, Rb);
-    es_signed_rotation(Ra);
-    es_signed_rotation(Rb);
-
-    // ---- the choice among (Ra, ta), (Rb, ta), (Ra, -ta), (Rb, -ta) -----------------------------------------------------
-    const double tn[3] = {-u2[0], -u2[1], -u2[2]};
-    if (a.flags & PNEC_HIP_EP_QUALITY_ALL) {
-      double qa[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll 1
-      for (int i0_ = 0; i0_ < n; i0_ += kWave) {
-        const int i = i0_ + lane;
-        const bool in = i < n;
-        double f[6];
-        pr.load6(in ? i : n - 1, f);
-        const double e0 = es_term(f, Ra, u2), e1 = es_term(f, Rb, u2), e2 = es_term(f, Ra, tn), e3 = es_term(f, Rb, tn);
-        qa[0] += in ? e0 : 0.0;
-        qa[1] += in ? e1 : 0.0;
-        qa[2] += in ? e2 : 0.0;
-        qa[3] += in ? e3 : 0.0;
-      }
-#pragma unroll
-      for (int c = 0; c < 4; ++c) quality[c] = to_sgpr(wave_allreduce_sum(qa[c]));
-    } else {
-      const int cand = lane >> 4, k = lane & 15;
-      const bool in = k < (n < kEpSample ? n : kEpSample);
-      double f[6], R[9], t[3];
-      pr.load6(in ? k : 0, f);
-#pragma unroll
-      for (int j = 0; j < 9; ++j) R[j] = (cand & 1) ? Rb[j] : Ra[j];
-#pragma unroll
-      for (int j = 0; j < 3; ++j) t[j] = (cand & 2) ? tn[j] : u2[j];
-      const double e = es_term(f, R, t);
-      const double rs = row_allreduce_sum(in ? e : 0.0);
-      quality[0] = read_lane<0>(rs);
-      quality[1] = read_lane<16>(rs);
-      quality[2] = read_lane<32>(rs);
-      quality[3] = read_lane<48>(rs);
-    }
-    double best = kEsStartQuality;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      quality[c] = finite_d(quality[c]) ? quality[c] : __builtin_inf();
-      if (quality[c] < best) {
-        best = quality[c];
-        choice = c;
-      }
-    }
-    if (choice < 0) {
-      status = PNEC_HIP_EP_NO_CANDIDATE;
+    const bool all = a.flags & PNEC_HIP_EP_QUALITY_ALL;
+    const int K = all ? n : (n < kEpSample ? n : kEpSample);
+    status = model::ep_model(pr, K, all, lane, M, trace, gap, choice, quality, E, sing, Rc, tc);
+    if (status != PNEC_HIP_EP_OK) {
 #pragma unroll
       for (int k = 0; k < 9; ++k) E[k] = nan;
-    } else {
-#pragma unroll
-      for (int k = 0; k < 9; ++k) Rc[k] = (choice & 1) ? Rb[k] : Ra[k];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) tc[k] = (choice & 2) ? tn[k] : u2[k];
     }
   }
 

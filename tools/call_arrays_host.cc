@@ -193,6 +193,19 @@ void batch_lists(int64_t P, int64_t n_hyp, int64_t n) {
       l.out(l.opt(), P, 4);        // status
     }, 150 * P, 3 * P);
 
+    run(tag("essential_ransac", {P, C}), [&](List &l) {
+      l.out(l.opt(), 4 * P, 8);    // q
+      l.out(l.opt(), 3 * P, 8);    // t
+      l.out(l.opt(), 9 * P, 8);    // E
+      l.out(l.opt(), 3 * P, 8);    // singular
+      l.out(l.opt(), C, 1);        // inlier mask
+      l.out(l.opt(), P, 4);        // inlier count
+      l.out(l.opt(), P, 4);        // iterations
+      l.out(l.opt(), P, 4);        // attempts
+      l.out(l.opt(), P, 4);        // best attempt
+      l.out(l.opt(), P, 4);        // status
+    }, 19 * P + d8(C), 5 * P);
+
     // pairs of the previous batch: one more than of this one, so that the two counts cannot be mixed up unnoticed
     const int64_t Pp = P + 1;
     run(tag("relative_scale", {P, Pp, C}), [&](List &l) {
