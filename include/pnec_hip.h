@@ -398,6 +398,48 @@ int pnec_hip_trajectory_metrics(int device, int64_t n_seq, const int64_t *offset
                                 double *out_err_q, double *out_rmse_d, double *out_l1_d, double *out_angle1,
                                 double *out_rt1, int space, void *stream);
 
+/* pnec_hip_trajectory_advance: one frame's step of the running scale and pose of n_seq sequences in lockstep -- the
+ * online form of pnec_hip_relative_scale's chain and of pnec_hip_trajectory_compose (added within ABI 8: a pure
+ * addition, PNEC_HIP_ABI_VERSION is unchanged).  The state is per sequence and the caller's: s [n_seq] the baseline of
+ * the last pair in units of the first one, q [n_seq,4] xyzw and p [n_seq,3] the pose of the last frame.  A fresh state is
+ * s = NaN, q = (0, 0, 0, 1), p = 0.  The call reads (s, q, p) and writes (next_s, next_q, next_p): other arrays, the
+ * state is double-buffered.
+ *   rel_q [n_seq,4], rel_t [n_seq,3]   the pair's relative pose; rel_t as given (a direction: pass the oriented one,
+ *                                      out_t_oriented of pnec_hip_triangulate)
+ *   count int32 [n_seq] | NULL, min_count >= 0    the pair's correspondences and the least that make a pose
+ *   scale3 [n_seq,3] | NULL            pnec_hip_relative_scale's out_scale as it stands; entry 1, the lower median, is read
+ *   n_used int32 [n_seq] | NULL, min_used >= 1    that call's out_n_used and the least that make a ratio; needs scale3
+ *   out_status int32 [n_seq] | NULL    PNEC_HIP_TRAJ_*
+ *  1 The pair is PRESENT iff every word of rel_q and rel_t is finite, |rel_q|^2 = x x + y y + z z + w w, as computed, is
+ *    finite and > 0, and count is NULL or count >= min_count: rule 1 of pnec_hip_trajectory_compose and the count.
+ *  2 The state scale is VALID iff s is finite and > 0.
+ *  3 Not present: next = state, bit for bit; PNEC_HIP_TRAJ_ABSENT.
+ *  4 Present, state scale not valid: next_s = 1; PNEC_HIP_TRAJ_STARTED.
+ *  5 Present, state scale valid: r = scale3[1] is MEASURED iff scale3 is given, r is finite and > 0, n_used is NULL or
+ *    n_used >= min_used, and s * r is finite and > 0.  Measured: next_s = s * r, PNEC_HIP_TRAJ_MEASURED; otherwise
+ *    next_s = s (the last baseline is kept), PNEC_HIP_TRAJ_HELD.
+ *  6 The pose of a present pair: next_q = normalise(q (rel_q / |rel_q|)), next_p = p + R(q) (next_s rel_t), the product
+ *    and the rotation of pnec_hip_trajectory_compose step 3, every operation rounded on its own.  The state is
+ *    normalised once a step, where it is written; q is read as it stands (R(q) is a rotation for a unit q: a state this
+ *    call wrote, or a fresh one).  A product next_s rel_t that overflows gives a position that is not finite.
+ *  7 Against exact arithmetic on the same inputs over L steps, u = 2^-53: |dq| <= 12 (L + 2) u up to sign and
+ *    |dp| <= 26 (L + 2) u x (path length), the path being the sum of |next_s rel_t| over the present steps:
+ *    pnec_hip_trajectory_compose's 8 u a step and 4 u for the normalisation; twice that as the angle by which a step of
+ *    the path is turned, and 2 u a step for the rounding of the scale and of the sum (DESIGN.md 9r has the derivation).
+ * One lane per sequence: a sequence's outputs depend on its own inputs alone, not on n_seq, its position or `space`.
+ * DEVICE space: asynchronous on `stream`, nothing allocated, nothing read back.  HOST space: staged on `device`, the call
+ * blocks.  Refused with PNEC_HIP_ERR_INVALID_ARGUMENT before any device is touched: n_seq < 1 or > 2^31-1, a NULL rel_q,
+ * rel_t, s, q, p, next_s, next_q or next_p, min_count < 0, min_used < 1, n_used without scale3, an output that is an input
+ * or another output, a bad `space`. */
+#define PNEC_HIP_TRAJ_MEASURED 0
+#define PNEC_HIP_TRAJ_HELD 1
+#define PNEC_HIP_TRAJ_STARTED 2
+#define PNEC_HIP_TRAJ_ABSENT 3
+int pnec_hip_trajectory_advance(int device, int64_t n_seq, const double *rel_q, const double *rel_t, const int32_t *count,
+                                int32_t min_count, const double *scale3, const int32_t *n_used, int32_t min_used,
+                                const double *s, const double *q, const double *p, double *next_s, double *next_q,
+                                double *next_p, int32_t *out_status, int space, void *stream);
+
 /* The batch's SoA planes as stored in HBM (pair blocks of round_up(N_p, 64)-double planes; the layout in
  * pnec_internal.hpp / DESIGN.md): size in doubles, and a copy out (tests, debugging). */
 int64_t pnec_hip_problem_payload_doubles(const pnec_hip_problem *p);
@@ -1475,6 +1517,32 @@ int pnec_hip_tracks_keyframe(int64_t n_images, const int64_t *offsets, int64_t n
                              double *out_key_cov, int64_t *out_row, uint8_t *out_accepted, double *out_mean,
                              int32_t *out_n_matches, double *next_key_pts, double *next_key_cov, int32_t *next_span,
                              int space, int device, void *stream);
+
+/* pnec_hip_tracks_link: the join of two track sets on their ids (added within ABI 8: a pure addition,
+ * PNEC_HIP_ABI_VERSION is unchanged) -- for every row of the current set the row of the same track in the previous set,
+ * WITHIN its image's range there: the `link` pnec_hip_relative_scale takes when both sets filled a batch each.
+ *   cur_offsets int64 [n_images + 1], cur_id int64 [n_cur]      the current set's ranges and ids
+ *   prev_offsets int64 [n_images + 1], prev_id int64 [n_prev]   the previous set's
+ *   out_link int32 [n_cur]; out_n_linked int32 [n_images] | NULL
+ * Both sets' ranges are cut as in every track call: lo = clamp(offsets[f], 0, rows), hi = clamp(offsets[f + 1], lo, rows);
+ * Lp is the previous range's length, plo its first row.  For row k of image f with id = cur_id[k]: id < 0 gives -1;
+ * otherwise the lower bound by the bisection a = 0, b = Lp; while a < b: m = a + (b - a) / 2, if prev_id[plo + m] < id then
+ * a = m + 1 else b = m; and out_link[k] = a if a < Lp and prev_id[plo + a] == id, else -1.  For previous ids that ascend
+ * strictly within an image -- what pnec_hip_tracks_retain and pnec_hip_tracks_append produce: they keep the order of ids
+ * and new ids are larger -- that is the row holding the id, or -1 where there is none; for other input the result is
+ * the bisection's, and every access stays inside the arrays.  All compares are 64-bit.  Rows at and beyond the cut
+ * cur_offsets[n_images] (padding) get -1, up to n_cur.  out_n_linked[f] is the number of rows of image f with a link >= 0.
+ * DEVICE space: asynchronous on `stream`, two launches sized by n_cur and n_images alone, nothing allocated, nothing
+ * waited for, no atomic on global memory, the offsets are not read back (rows that unchecked offsets leave in no image
+ * get -1); an image's outputs depend on its own rows and its previous range alone, not on its neighbours or on `space`.
+ * HOST space: staged on `device`, both offset arrays are checked (from 0, non-decreasing, within their rows), the call
+ * blocks.  n_cur == 0 writes zeros to out_n_linked and returns 0.
+ * PNEC_HIP_ERR_INVALID_ARGUMENT, before a device is touched: n_images < 1 or > 2^31-1, n_cur or n_prev negative or
+ * > 2^31-1, NULL cur_offsets, prev_offsets or out_link, cur_id NULL with n_cur > 0, prev_id NULL with n_prev > 0, an
+ * output that is an input or the other output, a bad `space`. */
+int pnec_hip_tracks_link(int64_t n_images, const int64_t *cur_offsets, int64_t n_cur, const int64_t *cur_id,
+                         const int64_t *prev_offsets, int64_t n_prev, const int64_t *prev_id, int32_t *out_link,
+                         int32_t *out_n_linked, int space, int device, void *stream);
 
 /* Stored patches: a track keeps its templates for as long as it lives (added within ABI 8: pure additions,
  * PNEC_HIP_ABI_VERSION is unchanged).  The reference (klt_patch_optical_flow.h:344-385) builds an OpticalFlowPatch per

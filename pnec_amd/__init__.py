@@ -12,6 +12,7 @@ Layout:
   trajectory.py    trajectory evaluation: relative poses composed per sequence, RPE_1 / RPE_n / L1RPE_1 / L1RPE_n / r_t
   evaluate.py      python -m pnec_amd.evaluate: a pose file against KITTI ground truth, the reference's metrics row
   odometry.py      images in, poses out: the tracker, a batch shaped from its device offsets, and the chain
+  scaled_odometry.py  images in, a trajectory out: tracks linked on their ids, a running scale and pose per sequence
   simulation.py    synthetic inputs following the reference simulator's distributions (harness)
   distributed.py   one-process-per-GPU sharding of independent pair batches + one RCCL gather
 """
@@ -22,6 +23,8 @@ from .keyframes import KeyframePairs, KeyframeState, KeyframeTracker, keyframe_p
 from .odometry import Odometry, OdometryResult  # noqa: F401
 from .patches import (PATTERN52, Keypoints, PatchCovariance, PatchTrack, detect_keypoints, image_pyramid,  # noqa: F401
                       patch_covariance, patch_track)
+from .scaled_odometry import (ScaledOdometry, ScaledOdometryResult, TrajectoryState, advance_trajectory, link_tracks,  # noqa: F401
+                              new_trajectory_state)
 from .tracker import Tracker, TrackSet, append_tracks, retain_tracks  # noqa: F401
 from .patch_store import PatchStore, add_patches, new_patch_store, patch_track_stored  # noqa: F401
 from .tracks import chain_scales  # noqa: F401
@@ -29,5 +32,5 @@ from .undistort import Undistorted, camera_array, undistort_keypoints  # noqa: F
 from .trajectory import (Trajectory, TrajectoryMetrics, compose_trajectory, matched, stack_steps,  # noqa: F401
                          trajectory_metrics)
 
-__all__ = ["capi", "Batch", "EightPoint", "EssentialRansac", "KeyframePairs", "KeyframeState", "KeyframeTracker", "Keypoints", "MinimalPose", "Odometry", "OdometryResult", "PATTERN52", "PatchCovariance", "PatchStore", "PatchTrack", "PoseCovariance", "RelativeScale", "ResidualReport", "SolveResult",
-           "TrackSet", "Tracker", "Trajectory", "TrajectoryMetrics", "Triangulation", "Undistorted", "add_patches", "append_tracks", "camera_array", "chain_scales", "compose_trajectory", "detect_keypoints", "gate_sigma", "image_pyramid", "keyframe_pairs", "matched", "new_patch_store", "patch_covariance", "patch_track", "patch_track_stored", "retain_tracks", "select_best", "stack_steps", "trajectory_metrics", "undistort_keypoints"]
+__all__ = ["capi", "Batch", "EightPoint", "EssentialRansac", "KeyframePairs", "KeyframeState", "KeyframeTracker", "Keypoints", "MinimalPose", "Odometry", "OdometryResult", "PATTERN52", "PatchCovariance", "PatchStore", "PatchTrack", "PoseCovariance", "RelativeScale", "ResidualReport", "ScaledOdometry", "ScaledOdometryResult", "SolveResult",
+           "TrackSet", "Tracker", "Trajectory", "TrajectoryMetrics", "TrajectoryState", "Triangulation", "Undistorted", "add_patches", "advance_trajectory", "append_tracks", "camera_array", "chain_scales", "compose_trajectory", "detect_keypoints", "gate_sigma", "image_pyramid", "keyframe_pairs", "link_tracks", "matched", "new_patch_store", "new_trajectory_state", "patch_covariance", "patch_track", "patch_track_stored", "retain_tracks", "select_best", "stack_steps", "trajectory_metrics", "undistort_keypoints"]

@@ -36,6 +36,9 @@ EM_NAMES = {EM_OK: "ok", EM_TOO_FEW: "too_few", EM_NOT_FINITE: "not_finite", EM_
 EM_EIGHTPT = 3
 ER_OK, ER_TOO_FEW, ER_NO_MODEL = 0, 1, 2
 ER_NAMES = {ER_OK: "ok", ER_TOO_FEW: "too_few", ER_NO_MODEL: "no_model"}
+# pnec_hip_trajectory_advance's out_status (PNEC_HIP_TRAJ_*)
+TRAJ_MEASURED, TRAJ_HELD, TRAJ_STARTED, TRAJ_ABSENT = 0, 1, 2, 3
+TRAJ_NAMES = {TRAJ_MEASURED: "measured", TRAJ_HELD: "held", TRAJ_STARTED: "started", TRAJ_ABSENT: "absent"}
 # pnec_hip_eigensolver_scheme: which iteration stands in for opengv's eigenvalue minimisation (include/pnec_hip.h)
 ES_NEWTON, ES_DESCENT, ES_LM = 0, 1, 2
 # PNEC_HIP_RANSAC_* bits (pnec_hip_pipeline_options.ransac_flags, pnec_hip_problem_set_ransac_flags)
@@ -71,6 +74,7 @@ SYMBOLS = [
     "pnec_hip_undistort_keypoints",
     "pnec_hip_trajectory_compose",
     "pnec_hip_trajectory_metrics",
+    "pnec_hip_trajectory_advance",
     "pnec_hip_problem_payload_doubles",
     "pnec_hip_problem_export_payload",
     "pnec_hip_problem_num_pairs",
@@ -101,6 +105,7 @@ SYMBOLS = [
     "pnec_hip_tracks_retain",
     "pnec_hip_tracks_append",
     "pnec_hip_tracks_keyframe",
+    "pnec_hip_tracks_link",
     "pnec_hip_patch_track_indexed",
     "pnec_hip_patch_store_slot_bytes",
     "pnec_hip_patch_store_add",
@@ -264,6 +269,8 @@ def lib() -> C.CDLL:
         [_vp] * 6 + [C.c_int, _vp]
     L.pnec_hip_trajectory_compose.argtypes = [C.c_int, C.c_int64, _vp, C.c_int64] + [_vp] * 8 + [C.c_int, _vp]
     L.pnec_hip_trajectory_metrics.argtypes = [C.c_int, C.c_int64, _vp, C.c_int64] + [_vp] * 10 + [C.c_int, _vp]
+    L.pnec_hip_trajectory_advance.argtypes = [C.c_int, C.c_int64, _vp, _vp, _vp, C.c_int32, _vp, _vp, C.c_int32] + [_vp] * 7 + \
+        [C.c_int, _vp]
     L.pnec_hip_relative_scale.argtypes = [_vp] * 8 + [C.c_double] + [_vp] * 5 + [C.c_int, _vp]
     L.pnec_hip_patch_covariance.argtypes = [_vp, C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_int64, _vp, C.c_int64, _vp, _vp,
                                             C.c_int32, C.c_double] + [_vp] * 6 + [C.c_int, C.c_int, _vp]
@@ -281,6 +288,7 @@ def lib() -> C.CDLL:
         [C.c_int, C.c_int, _vp]
     L.pnec_hip_tracks_keyframe.argtypes = [C.c_int64, _vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp, _vp,
                                            C.c_double, C.c_int32] + [_vp] * 12 + [C.c_int, C.c_int, _vp]
+    L.pnec_hip_tracks_link.argtypes = [C.c_int64, _vp, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_int, C.c_int, _vp]
     L.pnec_hip_patch_track_indexed.argtypes = [_vp, _vp, C.c_int64] + [_vp] * 4 + [
         C.c_int32, C.c_int, C.c_int64, C.c_int32, C.c_int32, _vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp,
         C.c_int32, C.c_int32, C.c_double, C.c_uint32, C.c_double] + [_vp] * 6 + [C.c_int, C.c_int, _vp]

@@ -731,6 +731,16 @@ PatchTracks TrackPatches(const std::vector<const Pyramid *> &stack, const std::v
   return out;
 }
 
+std::vector<int32_t> LinkTracks(const std::vector<int64_t> &prev_ids, const std::vector<int64_t> &cur_ids) {
+  std::vector<int32_t> link(cur_ids.size(), -1);
+  if (cur_ids.empty()) return link;
+  const int64_t cur_offsets[2] = {0, (int64_t)cur_ids.size()}, prev_offsets[2] = {0, (int64_t)prev_ids.size()};
+  Check(pnec_hip_tracks_link(1, cur_offsets, (int64_t)cur_ids.size(), cur_ids.data(), prev_offsets, (int64_t)prev_ids.size(),
+                             prev_ids.empty() ? nullptr : prev_ids.data(), link.data(), nullptr, PNEC_HIP_MEM_HOST,
+                             optimization::SolverOptions().device, nullptr));
+  return link;
+}
+
 }  // namespace features
 
 // -------------------------------------------------------------------------------- optimization
@@ -1376,6 +1386,33 @@ TrajectoryScore TrajectoryMetrics(const std::vector<SE3d> &estimated, const std:
   s.L1RPE_n = m[3];
   s.r_t = m[4];
   return s;
+}
+
+TrajectoryState::TrajectoryState(size_t n)
+    : s(n, std::numeric_limits<double>::quiet_NaN()), q(4 * n, 0.0), p(3 * n, 0.0) {
+  for (size_t i = 0; i < n; ++i) q[4 * i + 3] = 1.0;
+}
+
+std::vector<int32_t> AdvanceTrajectory(const TrajectoryState &state, const std::vector<double> &rel_q,
+                                       const std::vector<double> &rel_t, TrajectoryState *next,
+                                       const std::vector<int32_t> *count, int min_count, const std::vector<double> *scale3,
+                                       const std::vector<int32_t> *n_used, int min_used) {
+  const size_t n = state.s.size();
+  if (!next || next == &state) throw std::invalid_argument("AdvanceTrajectory: next must be another object than state");
+  if (state.q.size() != 4 * n || state.p.size() != 3 * n || rel_q.size() != 4 * n || rel_t.size() != 3 * n ||
+      (count && count->size() != n) || (scale3 && scale3->size() != 3 * n) || (n_used && n_used->size() != n))
+    throw std::invalid_argument("AdvanceTrajectory: every array holds one row per sequence of the state");
+  next->s.resize(n);
+  next->q.resize(4 * n);
+  next->p.resize(3 * n);
+  std::vector<int32_t> status(n);
+  if (n == 0) return status;
+  Check(pnec_hip_trajectory_advance(optimization::SolverOptions().device, (int64_t)n, rel_q.data(), rel_t.data(),
+                                    count ? count->data() : nullptr, min_count, scale3 ? scale3->data() : nullptr,
+                                    n_used ? n_used->data() : nullptr, min_used, state.s.data(), state.q.data(),
+                                    state.p.data(), next->s.data(), next->q.data(), next->p.data(), status.data(),
+                                    PNEC_HIP_MEM_HOST, nullptr));
+  return status;
 }
 
 }  // namespace odometry

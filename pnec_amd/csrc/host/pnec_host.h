@@ -281,6 +281,10 @@ PatchTracks TrackPatches(const std::vector<const Pyramid *> &tmpl_stack, const s
                          const std::vector<std::array<double, 2>> *init_points = nullptr,
                          const std::vector<double> *init_angles = nullptr,
                          const std::vector<std::array<double, 2>> *pattern = nullptr);
+// Addition: the join of two track sets of one image on their ids (pnec_hip_tracks_link): for every id of `cur_ids` the
+// row of the same id in `prev_ids`, -1 where there is none or the id is negative -- the `link` a relative scale between
+// the two pairs takes.  prev_ids must ascend strictly, as the ids RetainTracks / AppendTracks produce do.
+std::vector<int32_t> LinkTracks(const std::vector<int64_t> &prev_ids, const std::vector<int64_t> &cur_ids);
 }  // namespace features
 
 namespace optimization {
@@ -529,6 +533,23 @@ struct TrajectoryScore {
   std::vector<double> angle1, rt1;    // [k]: rotation / translation error of the step k-1 -> k; [0] is 0
 };
 TrajectoryScore TrajectoryMetrics(const std::vector<SE3d> &estimated, const std::vector<SE3d> &ground_truth);
+
+// Addition: the online form (pnec_hip_trajectory_advance): a running scale and pose per sequence, one frame's step a call.
+// s [n]: the last pair's baseline in units of the first pair's (NaN: no pair yet); q [n,4] xyzw and p [n,3]: the pose
+// of the last frame.
+struct TrajectoryState {
+  std::vector<double> s, q, p;
+  explicit TrajectoryState(size_t n = 0);   // fresh: s = NaN, q = (0, 0, 0, 1), p = 0
+};
+// One step for the n sequences of `state`: rel_q [n,4] xyzw, rel_t [n,3] (the oriented direction); count / min_count: the
+// pair's correspondences and the least that make a pose; scale3 [n,3] / n_used [n] / min_used: the three quantiles of the
+// baseline ratios (the median, entry 1, is read), the links behind them and the least that make a measurement.  nullptr:
+// not given.  Writes *next (another object than `state`) and returns the statuses, PNEC_HIP_TRAJ_* [n].
+std::vector<int32_t> AdvanceTrajectory(const TrajectoryState &state, const std::vector<double> &rel_q,
+                                       const std::vector<double> &rel_t, TrajectoryState *next,
+                                       const std::vector<int32_t> *count = nullptr, int min_count = 0,
+                                       const std::vector<double> *scale3 = nullptr,
+                                       const std::vector<int32_t> *n_used = nullptr, int min_used = 1);
 
 }  // namespace odometry
 

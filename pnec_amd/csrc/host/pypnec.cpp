@@ -390,6 +390,62 @@ py::dict trajectory_metrics(arr estimated, arr ground_truth) {
   return d;
 }
 
+using iarr64 = py::array_t<int64_t, py::array::c_style | py::array::forcecast>;
+using iarr32 = py::array_t<int32_t, py::array::c_style | py::array::forcecast>;
+
+// pnec::features::LinkTracks: int32 [len(cur_ids)]
+iarr32 link_tracks(iarr64 prev_ids, iarr64 cur_ids) {
+  if (prev_ids.ndim() != 1 || cur_ids.ndim() != 1) throw std::invalid_argument("prev_ids and cur_ids must be one-dimensional");
+  const std::vector<int64_t> prev(prev_ids.data(), prev_ids.data() + prev_ids.size()),
+      cur(cur_ids.data(), cur_ids.data() + cur_ids.size());
+  std::vector<int32_t> link;
+  {
+    py::gil_scoped_release release;
+    link = pnec::features::LinkTracks(prev, cur);
+  }
+  iarr32 out((py::ssize_t)link.size());
+  if (!link.empty()) std::memcpy(out.mutable_data(), link.data(), link.size() * sizeof(int32_t));
+  return out;
+}
+
+// pnec::odometry::AdvanceTrajectory: (s [n], q [n,4], p [n,3], status int32 [n])
+py::tuple advance_trajectory(arr s, arr q, arr p, arr rel_q, arr rel_t, py::object count, int min_count, py::object scale3,
+                             py::object n_used, int min_used) {
+  const size_t n = (size_t)s.size();
+  if (s.ndim() != 1 || q.ndim() != 2 || q.shape(0) != (py::ssize_t)n || q.shape(1) != 4 || p.ndim() != 2 ||
+      p.shape(0) != (py::ssize_t)n || p.shape(1) != 3)
+    throw std::invalid_argument("the state is s [n], q [n,4], p [n,3]");
+  if (rel_q.ndim() != 2 || rel_q.shape(0) != (py::ssize_t)n || rel_q.shape(1) != 4 || rel_t.ndim() != 2 ||
+      rel_t.shape(0) != (py::ssize_t)n || rel_t.shape(1) != 3)
+    throw std::invalid_argument("rel_q must be [n,4] (xyzw), rel_t [n,3]");
+  auto doubles = [](const arr &a) { return std::vector<double>(a.data(), a.data() + a.size()); };
+  auto ints = [](const iarr32 &a) { return std::vector<int32_t>(a.data(), a.data() + a.size()); };
+  pnec::odometry::TrajectoryState state(n), next(n);
+  state.s = doubles(s);
+  state.q = doubles(q);
+  state.p = doubles(p);
+  const std::vector<double> rq = doubles(rel_q), rt = doubles(rel_t);
+  std::vector<int32_t> cnt, used;
+  std::vector<double> sc;
+  if (!count.is_none()) cnt = ints(count.cast<iarr32>());
+  if (!n_used.is_none()) used = ints(n_used.cast<iarr32>());
+  if (!scale3.is_none()) sc = doubles(scale3.cast<arr>());
+  std::vector<int32_t> status;
+  {
+    py::gil_scoped_release release;
+    status = pnec::odometry::AdvanceTrajectory(state, rq, rt, &next, count.is_none() ? nullptr : &cnt, min_count,
+                                               scale3.is_none() ? nullptr : &sc, n_used.is_none() ? nullptr : &used, min_used);
+  }
+  arr out_q({(py::ssize_t)n, (py::ssize_t)4}), out_p({(py::ssize_t)n, (py::ssize_t)3});
+  iarr32 out_status((py::ssize_t)n);
+  if (n) {
+    std::memcpy(out_q.mutable_data(), next.q.data(), 4 * n * sizeof(double));
+    std::memcpy(out_p.mutable_data(), next.p.data(), 3 * n * sizeof(double));
+    std::memcpy(out_status.mutable_data(), status.data(), n * sizeof(int32_t));
+  }
+  return py::make_tuple(FromDoubles(next.s), out_q, out_p, out_status);
+}
+
 // MinimalEMPoseEstimation(bvs1, bvs2, identity, NISTER | SEVENPT): 4x4, the translation of length s0
 arr minimal_pose(arr bvs1, arr bvs2, pnec::rel_pose_estimation::algorithm_t algorithm) {
   const auto b1 = ToBearings(bvs1, "bvs_1"), b2 = ToBearings(bvs2, "bvs_2");
@@ -778,6 +834,15 @@ PYBIND11_MODULE(pypnec, m) {
         "pnec::odometry::TrajectoryMetrics (device): RPE_1, RPE_n, L1RPE_1, L1RPE_n, r_t in radians of the matched absolute "
         "poses estimated / ground_truth [N,4,4], with rmse_d, l1_d, angle1, rt1 [N], as a dict; an exact estimate scores 0 "
         "where the reference gives NaN -- include/pnec_hip.h pnec_hip_trajectory_metrics");
+  m.def("link_tracks", &link_tracks, py::arg("prev_ids"), py::arg("cur_ids"),
+        "pnec::features::LinkTracks (device): for every track id of cur_ids the row of the same id in prev_ids (strictly "
+        "ascending), -1 where there is none; int32 [len(cur_ids)] -- include/pnec_hip.h pnec_hip_tracks_link");
+  m.def("advance_trajectory", &advance_trajectory, py::arg("s"), py::arg("q"), py::arg("p"), py::arg("rel_q"),
+        py::arg("rel_t"), py::arg("count") = py::none(), py::arg("min_count") = 0, py::arg("scale3") = py::none(),
+        py::arg("n_used") = py::none(), py::arg("min_used") = 1,
+        "pnec::odometry::AdvanceTrajectory (device): one frame's step of the running scale s [n] and pose q [n,4] xyzw, "
+        "p [n,3] by the relative pose rel_q, rel_t and the baseline ratio's median scale3[:, 1]; returns (s, q, p, status "
+        "int32 [n]: 0 measured, 1 held, 2 started, 3 absent) -- include/pnec_hip.h pnec_hip_trajectory_advance");
   m.def("five_point", &five_point, py::arg("bvs1"), py::arg("bvs2"),
         "pnec::rel_pose_estimation::MinimalEMPoseEstimation(bvs1, bvs2, identity, NISTER) (device): the 4x4 pose of "
         "Nister's five-point solver, translation of length s0; the identity when the pair gives no pose -- "

@@ -30,6 +30,7 @@
 #include "pnec_trajectory.hpp"
 #include "pnec_relative_scale.hpp"
 #include "pnec_tracks.hpp"
+#include "pnec_tracks_link.hpp"
 #include "pnec_triangulate.hpp"
 #include "pnec_solve_kernel.hpp"
 #include "pnec_solve_group_kernel.hpp"
@@ -1028,6 +1029,43 @@ int pnec_hip_trajectory_metrics(int device, int64_t n_seq, const int64_t *offset
   io.out(a.out_rt1, out_rt1, n_rows, kPreload);
   if (int rc = io.commit()) return rc;
   PNEC_HIP_TRY(launch_trajectory_metrics(a, stream));
+  return io.finish();
+}
+
+int pnec_hip_trajectory_advance(int device, int64_t n_seq, const double *rel_q, const double *rel_t, const int32_t *count,
+                                int32_t min_count, const double *scale3, const int32_t *n_used, int32_t min_used,
+                                const double *s, const double *q, const double *p, double *next_s, double *next_q,
+                                double *next_p, int32_t *out_status, int space, void *stream_) {
+  const std::string pre = "trajectory_advance: ";
+  if (n_seq < 1 || n_seq > 0x7fffffffLL) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "n_seq must be 1 .. 2^31-1");
+  if (!rel_q || !rel_t) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "rel_q or rel_t is NULL");
+  if (!s || !q || !p || !next_s || !next_q || !next_p)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "a state array (s, q, p, next_s, next_q, next_p) is NULL");
+  if (min_count < 0 || min_used < 1) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "min_count must be >= 0, min_used >= 1");
+  if (n_used && !scale3) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "n_used needs scale3");
+  if (trajectory_alias({next_s, next_q, next_p, out_status}, {rel_q, rel_t, count, scale3, n_used, s, q, p}))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "an output is also an input or another output (the state is double-buffered)");
+  if (int rc = check_space(pre, space)) return rc;
+  hipStream_t stream = (hipStream_t)stream_;
+  CallArrays io(device, space, stream);
+  TrajectoryAdvanceArgs a{};
+  a.n_seq = n_seq;
+  a.min_count = min_count;
+  a.min_used = min_used;
+  io.in(a.rel_q, rel_q, 4 * n_seq);
+  io.in(a.rel_t, rel_t, 3 * n_seq);
+  io.in(a.count, count, n_seq);
+  io.in(a.scale3, scale3, 3 * n_seq);
+  io.in(a.n_used, n_used, n_seq);
+  io.in(a.s, s, n_seq);
+  io.in(a.q, q, 4 * n_seq);
+  io.in(a.p, p, 3 * n_seq);
+  io.out(a.next_s, next_s, n_seq);
+  io.out(a.next_q, next_q, 4 * n_seq);
+  io.out(a.next_p, next_p, 3 * n_seq);
+  io.out(a.out_status, out_status, n_seq);
+  if (int rc = io.commit()) return rc;
+  PNEC_HIP_TRY(launch_trajectory_advance(a, stream));
   return io.finish();
 }
 
@@ -2134,6 +2172,57 @@ int pnec_hip_tracks_append(int64_t n_images, const int64_t *offsets, int64_t n_r
   io.out(a.out_dropped, out_dropped, n_images);
   if (int rc = io.commit()) return rc;
   PNEC_HIP_TRY(launch_tracks_append(a, stream));
+  return io.finish();
+}
+
+// the join of two sets on their ids: pnec_tracks_link.hip.  Staged like the two calls above.
+int pnec_hip_tracks_link(int64_t n_images, const int64_t *cur_offsets, int64_t n_cur, const int64_t *cur_id,
+                         const int64_t *prev_offsets, int64_t n_prev, const int64_t *prev_id, int32_t *out_link,
+                         int32_t *out_n_linked, int space, int device, void *stream_) {
+  const std::string pre = "tracks_link: ";
+  if (n_images < 1 || n_images > 0x7fffffffLL) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "n_images must be 1 .. 2^31-1");
+  if (n_cur < 0 || n_cur > 0x7fffffffLL || n_prev < 0 || n_prev > 0x7fffffffLL)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "n_cur and n_prev must be 0 .. 2^31-1");
+  if (!cur_offsets || !prev_offsets || !out_link)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "cur_offsets, prev_offsets or out_link is NULL");
+  if ((n_cur > 0 && !cur_id) || (n_prev > 0 && !prev_id))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "cur_id or prev_id is NULL");
+  const void *ins[] = {cur_offsets, cur_id, prev_offsets, prev_id};
+  for (const void *i : ins)
+    if (i && (i == out_link || i == out_n_linked))
+      return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "an output is an input (the outputs are fresh arrays)");
+  if ((const void *)out_link == (const void *)out_n_linked)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, pre + "out_link and out_n_linked are the same array");
+  if (int rc = check_space(pre, space)) return rc;
+  if (space == PNEC_HIP_MEM_HOST) {
+    if (int rc = check_set_offsets(pre, "cur_offsets", cur_offsets, n_images, n_cur, "n_cur")) return rc;
+    if (int rc = check_set_offsets(pre, "prev_offsets", prev_offsets, n_images, n_prev, "n_prev")) return rc;
+  }
+  hipStream_t stream = (hipStream_t)stream_;
+  if (n_cur == 0) {   // no row: the counts alone
+    if (!out_n_linked) return 0;
+    if (space == PNEC_HIP_MEM_HOST) {
+      std::memset(out_n_linked, 0, (size_t)n_images * sizeof(int32_t));
+      return 0;
+    }
+    DeviceGuard guard(device);
+    if (!guard.ok) return fail(PNEC_HIP_ERR_HIP_RUNTIME, "hipSetDevice failed (no such device?)");
+    PNEC_HIP_TRY(hipMemsetAsync(out_n_linked, 0, (size_t)n_images * sizeof(int32_t), stream));
+    return 0;
+  }
+  CallArrays io(device, space, stream);
+  TracksLinkArgs a{};
+  a.n_images = n_images;
+  a.n_cur = n_cur;
+  a.n_prev = n_prev;
+  io.in(a.cur_offsets, cur_offsets, n_images + 1);
+  io.in(a.cur_id, cur_id, n_cur);
+  io.in(a.prev_offsets, prev_offsets, n_images + 1);
+  io.in(a.prev_id, prev_id, n_prev);
+  io.out(a.out_link, out_link, n_cur);
+  io.out(a.out_n_linked, out_n_linked, n_images);
+  if (int rc = io.commit()) return rc;
+  PNEC_HIP_TRY(launch_tracks_link(a, stream));
   return io.finish();
 }
 

@@ -9,6 +9,9 @@
 // second time from the total of the lanes below it and writes the poses.  The steps are read twice, the second time from
 // cache; nothing is kept between the passes but seven doubles.
 //
+// advance (pnec_hip_trajectory_advance): the online form, one frame's step of the running scale and pose with the state
+// held by the caller; one lane per sequence, the product and the rotation of compose.
+//
 // metrics: three launches on the call's stream.
 //   error rotations   one lane per row, e = est * conj(gt), whatever sequence the row is in
 //   distances         one wavefront per row lo + d: the wavefront finds its sequence by bisection of the cut offsets,
@@ -225,6 +228,62 @@ __global__ __launch_bounds__(kWaveLanes) void trajectory_compose_kernel(const Tr
 hipError_t launch_trajectory_compose(const TrajectoryComposeArgs &a, hipStream_t stream) {
   if (a.n_seq < 1 || a.n_seq > 0x7fffffffLL) return hipErrorInvalidValue;
   hipLaunchKernelGGL(trajectory_compose_kernel, dim3((unsigned)a.n_seq), dim3(kWaveLanes), 0, stream, a);
+  return hipGetLastError();
+}
+
+// ---- advance ------------------------------------------------------------------------------------------------------
+// One lane per sequence: 14 doubles and two integers in, 8 doubles and a status out, a few dozen dependent FP64
+// operations with one square root and two divisions' worth of normalisation.  Nothing is shared between lanes.
+__global__ __launch_bounds__(kRowBlock) void trajectory_advance_kernel(const TrajectoryAdvanceArgs a) {
+  const int64_t i = (int64_t)blockIdx.x * kRowBlock + threadIdx.x;
+  if (i >= a.n_seq) return;
+  const Quat rq = load_quat(a.rel_q, i);
+  const Vec3 rt = load_vec3(a.rel_t, i);
+  const double n2 = quat_norm2(rq);
+  const bool present = traj_finite(rq.x) && traj_finite(rq.y) && traj_finite(rq.z) && traj_finite(rq.w) && traj_finite(rt.x) &&
+                       traj_finite(rt.y) && traj_finite(rt.z) && n2 > 0.0 && traj_finite(n2) &&
+                       (!a.count || a.count[i] >= a.min_count);
+  const double s = a.s[i];
+  const Quat q = load_quat(a.q, i);
+  const Vec3 p = load_vec3(a.p, i);
+  double *np = a.next_p + 3 * i;
+  if (!present) {   // the state as it is, bit for bit
+    a.next_s[i] = s;
+    store_quat(a.next_q, i, q);
+    np[0] = p.x;
+    np[1] = p.y;
+    np[2] = p.z;
+    if (a.out_status) a.out_status[i] = PNEC_HIP_TRAJ_ABSENT;
+    return;
+  }
+  double next_s = 1.0;
+  int32_t status = PNEC_HIP_TRAJ_STARTED;
+  if (traj_finite(s) && s > 0.0) {
+    next_s = s;
+    status = PNEC_HIP_TRAJ_HELD;
+    if (a.scale3) {
+      const double r = a.scale3[3 * i + 1], sr = s * r;
+      if (traj_finite(r) && r > 0.0 && (!a.n_used || a.n_used[i] >= a.min_used) && traj_finite(sr) && sr > 0.0) {
+        next_s = sr;
+        status = PNEC_HIP_TRAJ_MEASURED;
+      }
+    }
+  }
+  const double n = __builtin_sqrt(n2);
+  const Quat step{rq.x / n, rq.y / n, rq.z / n, rq.w / n};
+  const Vec3 d = quat_rotate(q, Vec3{next_s * rt.x, next_s * rt.y, next_s * rt.z});
+  a.next_s[i] = next_s;
+  store_quat(a.next_q, i, quat_normalise(quat_mul(q, step)));
+  np[0] = p.x + d.x;
+  np[1] = p.y + d.y;
+  np[2] = p.z + d.z;
+  if (a.out_status) a.out_status[i] = status;
+}
+
+hipError_t launch_trajectory_advance(const TrajectoryAdvanceArgs &a, hipStream_t stream) {
+  if (a.n_seq < 1 || a.n_seq > 0x7fffffffLL) return hipErrorInvalidValue;
+  const int64_t blocks = (a.n_seq + kRowBlock - 1) / kRowBlock;
+  hipLaunchKernelGGL(trajectory_advance_kernel, dim3((unsigned)blocks), dim3(kRowBlock), 0, stream, a);
   return hipGetLastError();
 }
 

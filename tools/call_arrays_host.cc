@@ -465,6 +465,31 @@ void image_lists(int64_t F, int64_t elem, int64_t n_points) {
       l.out(angle1, N, 8, kPreload);
       l.out(rt1, N, 8, kPreload);
     }, (F + 1) + 22 * N + 5 * F, 0);
+    // the join of two sets on their ids: N current rows, D previous rows (another count, so that the two cannot be mixed up)
+    run(tag("tracks_link", {F, N, D}), [&](List &l) {
+      l.in(true, F + 1, 8);      // cur_offsets
+      l.in(true, N, 8);          // cur_id
+      l.in(true, F + 1, 8);      // prev_offsets
+      l.in(true, D, 8);          // prev_id
+      l.out(true, N, 4);         // out_link
+      l.out(l.opt(), F, 4);      // out_n_linked
+    }, 2 * (F + 1) + N + D, N + F);
+    // one step of the running scale and pose of F sequences: n_used goes with scale3
+    run(tag("trajectory_advance", {F}), [&](List &l) {
+      const bool count = l.opt(), scale3 = l.opt(), n_used = l.opt() && scale3;
+      l.in(true, 4 * F, 8);      // rel_q
+      l.in(true, 3 * F, 8);      // rel_t
+      l.in(count, F, 4);
+      l.in(scale3, 3 * F, 8);
+      l.in(n_used, F, 4);
+      l.in(true, F, 8);          // s, q, p
+      l.in(true, 4 * F, 8);
+      l.in(true, 3 * F, 8);
+      l.out(true, F, 8);         // next_s, next_q, next_p
+      l.out(true, 4 * F, 8);
+      l.out(true, 3 * F, 8);
+      l.out(l.opt(), F, 4);      // out_status
+    }, 26 * F, 3 * F);
   }
 }
 
