@@ -611,6 +611,70 @@ int pnec_hip_residuals(pnec_hip_problem *p, const double *q, const double *t, in
                        double *out_chi2, double *out_gated_chi2, int32_t *out_gated_count, double *out_max_abs,
                        int space, void *stream);
 
+/* Pose sensitivity: the gradient of a loss of the SOLVED pose with respect to every input of the pair -- what a
+ * training loop needs to push a pose error back through the refinement onto learned covariances (added within ABI 8: a
+ * pure addition, PNEC_HIP_ABI_VERSION is unchanged).  No iteration is unrolled: the pose the refinement returns is a
+ * minimiser, so its derivative follows from the implicit-function theorem at that pose, one 5x5 solve per slot and one
+ * pass per correspondence.
+ *
+ * Poses: q, t, slot s = pair * n_hyp + h and `reg` exactly as in pnec_hip_pose_covariance.
+ *
+ * Chart.  The one of pnec_hip_pose_covariance: x = (tau_1, tau_2, omega), t(x) = normalize(t + tau_1 b_theta + tau_2
+ * e_phi), R(x) = Exp(omega) R.
+ *
+ * Cost.  E(x; theta) = 1/2 sum_i r_i^2 with r_i the residual of the batch's family, `reg` included:
+ *     m = t x f1,  g = R'm,  n = f2.g,  h = t x (R a)   (a = f1 for HOST, f2 for SYM)
+ *     NEC r = n;  TARGET r = n / sqrt(g'S2 g + reg);  HOST r = n / sqrt(h'S h + reg);  SYM r = n / sqrt(g'S2 g + h'S1 h + reg)
+ * theta_i are correspondence i's inputs as the planes hold them: f1 [3], f2 [3], the covariance (symmetric 3x3: S2 of
+ * TARGET and SYM, S of HOST) and for SYM the host covariance S1.  f1 and f2 are used as written -- nothing normalises
+ * them inside -- and the gradients are plain partials in R^3.
+ *     g = grad_x E at x = 0,   H = hess_x E at x = 0 = J'J + sum_i r_i hess_x r_i IN THIS CHART (the curvature of both
+ *     manifolds included);  with PNEC_HIP_SENS_GAUSS_NEWTON  H = J'J (1 - 40 % off at 37 - 200 correspondences).
+ *
+ * Cotangent.  grad_pose [n_pairs * n_hyp, 6] = (dL/d omega [3], dL/d t [3]), in the order of out_cov's rows:
+ *     v = (b_theta . dL/dt, e_phi . dL/dt, dL/d omega),   lambda = H^-1 v
+ * (Cholesky factor of the Jacobi-scaled H, as pnec_hip_pose_covariance inverts its matrix).
+ *
+ * Result per correspondence.  dL/d theta_i = - d/d theta_i [ lambda . grad_x (r_i^2 / 2) ] at x = 0.  For a covariance it
+ * is the symmetric matrix G with dL = sum_jk G_jk dS_jk: an off-diagonal entry holds half the derivative with respect to
+ * the stored plane value.  This is the derivative of the minimiser when g = 0; at any other pose it is exact for the
+ * Newton-corrected pose to first order in x_N = -H^-1 g, which the call returns so that a caller can see how converged
+ * the pose was.
+ *
+ * Outputs; every pointer may be NULL (not wanted), not all of them.
+ *  per correspondence, M = n_hyp * sum N rows each, the row of (pair p, hypothesis h, correspondence i) is
+ *  n_hyp * offsets[p] + h * N_p + i as in pnec_hip_residuals:
+ *   out_grad_bvs1 [M,3]  out_grad_bvs2 [M,3]
+ *   out_grad_covs [M,9]       row-major symmetric G of the batch's `covs` input; not for NEC
+ *   out_grad_covs_host [M,9]  the same for `covs_host`; SYM only
+ *  per slot:
+ *   out_lambda [5]    lambda
+ *   out_hessian [15]  upper triangle of H, row by row, in x (NOT the Ceres tangent space of out_info)
+ *   out_grad [5]      g in x
+ *   out_newton [5]    x_N
+ *   out_status        pnec_hip_sens_status.  PNEC_HIP_SENS_SINGULAR: fewer than 5 correspondences, a non-positive
+ *                     diagonal entry or pivot (H is not positive definite: the pose is not a minimiser);
+ *                     PNEC_HIP_SENS_NONFINITE: a sum is Inf / NaN.  A failed slot's lambda, x_N and per-correspondence
+ *                     rows are NaN, or exactly 0 with PNEC_HIP_SENS_ZERO_ON_FAILURE; H and g are written as computed;
+ *                     other slots are unaffected.  A slot's outputs depend on its own pair, pose and cotangent only.
+ *
+ * All four problem modes; batches made by pnec_hip_problem_select(_view) and reshaped capacity batches included.  `space`
+ * as in pnec_hip_residuals (HOST space resolves a selected batch's sizes first and stages every array; DEVICE space is
+ * asynchronous on `stream`).  NULL problem / q / t / grad_pose, n_hyp < 1, an unknown bit in flags, all outputs NULL, a
+ * covariance output the family has no input for, or a bad `space`: PNEC_HIP_ERR_INVALID_ARGUMENT before the handle's
+ * device is touched. */
+typedef enum pnec_hip_sens_status {
+  PNEC_HIP_SENS_OK = 0,
+  PNEC_HIP_SENS_SINGULAR = 1,
+  PNEC_HIP_SENS_NONFINITE = 2
+} pnec_hip_sens_status;
+enum { PNEC_HIP_SENS_GAUSS_NEWTON = 1, PNEC_HIP_SENS_ZERO_ON_FAILURE = 2 };
+int pnec_hip_pose_sensitivity(pnec_hip_problem *p, const double *q, const double *t, const double *grad_pose,
+                              int32_t n_hyp, double reg, int32_t flags, double *out_grad_bvs1, double *out_grad_bvs2,
+                              double *out_grad_covs, double *out_grad_covs_host, double *out_lambda,
+                              double *out_hessian, double *out_grad, double *out_newton, int32_t *out_status,
+                              int space, void *stream);
+
 /* Triangulation at a pose the caller passes in: depths, points, parallax, depth variance and the cheirality vote that
  * fixes the sign of t (added within ABI 8: a pure addition, PNEC_HIP_ABI_VERSION is unchanged).  Every energy the
  * solvers minimise is even in t; this call is what decides between t and -t.

@@ -43,6 +43,14 @@ class SolveResult:
             raise ValueError("this SolveResult was not produced by Batch.solve: call Batch.residuals(q, t)")
         return self.batch.residuals(self.q, self.t, reg=self.reg, gate=gate, n_hyp=self.n_hyp)
 
+    def sensitivity(self, grad_pose, gauss_newton: bool = False, zero_on_failure: bool = False) -> "PoseSensitivity":
+        """Batch.pose_sensitivity at this result's own poses, with the `reg` and `n_hyp` of the solve it came from: the
+        gradient of a loss of these poses with respect to the pair's bearing vectors and covariances."""
+        if self.batch is None:
+            raise ValueError("this SolveResult was not produced by Batch.solve: call Batch.pose_sensitivity(q, t, grad_pose)")
+        return self.batch.pose_sensitivity(self.q, self.t, grad_pose, reg=self.reg, n_hyp=self.n_hyp,
+                                           gauss_newton=gauss_newton, zero_on_failure=zero_on_failure)
+
     def triangulate(self, orient: bool = True) -> "Triangulation":
         """Batch.triangulate at this result's own poses, with the `n_hyp` of the solve it came from: the structure the
         solved pose implies and, with `orient`, the sign of t that puts it in front of both cameras."""
@@ -127,6 +135,22 @@ class PoseCovariance:
     grad: object    # [S,5]   J'r in the same space
     cost: object    # [S]     1/2 sum r^2
     status: object  # [S]     int32, capi.COV_NAMES
+
+
+@dataclass
+class PoseSensitivity:
+    """pnec_hip_pose_sensitivity's outputs (include/pnec_hip.h has the definitions).  Per correspondence, row
+    n_hyp * offsets[p] + h * N_p + i: the gradient of the loss with respect to that correspondence's inputs; per pose
+    slot (pair-major, hypothesis-minor): what the implicit-function step was made of."""
+    grad_bvs1: object       # [M,3]
+    grad_bvs2: object       # [M,3]
+    grad_covs: object       # [M,3,3] symmetric, None for NEC batches
+    grad_covs_host: object  # [M,3,3] symmetric, SYM batches only (None otherwise)
+    lam: object             # [S,5]   lambda = H^-1 v in the chart (tau_1, tau_2, omega)
+    hessian: object         # [S,5,5] H in the same chart, full symmetric
+    grad: object            # [S,5]   g = grad_x E
+    newton: object          # [S,5]   x_N = -H^-1 g: how far the pose is from the minimiser
+    status: object          # [S]     int32, capi.SENS_NAMES
 
 
 def gate_sigma(confidence: float) -> float:
@@ -825,6 +849,50 @@ class Batch:
                                                       p(cost), p(status), space, stream))
         return PoseCovariance(cov, expand_info(info), grad, cost, status)
 
+
+    def pose_sensitivity(self, q, t, grad_pose, reg: float = 1e-13, n_hyp: int = 1, gauss_newton: bool = False,
+                         zero_on_failure: bool = False) -> PoseSensitivity:
+        """Gradient of a loss of the solved pose with respect to every bearing vector and covariance of its pair, by the
+        implicit-function theorem at the poses passed in (pnec_hip_pose_sensitivity): q [S,4] xyzw, t [S,3], grad_pose
+        [S,6] = (dL/d omega, dL/d t), S = n_pairs * n_hyp.  torch.cuda tensors in -> torch.cuda tensors out, asynchronous
+        on torch's current stream; numpy in -> numpy out.  `gauss_newton`: J'J in place of the full Hessian (1 - 40 % off);
+        `zero_on_failure`: a slot whose Hessian is not positive definite gives zeros, not NaN.  On a batch made by
+        select() the call first reads that batch's offsets to size the outputs, as residuals() does."""
+        n_hyp = int(n_hyp)
+        if n_hyp < 1:
+            raise ValueError("n_hyp must be >= 1")
+        flags = (capi.SENS_GAUSS_NEWTON if gauss_newton else 0) | (capi.SENS_ZERO_ON_FAILURE if zero_on_failure else 0)
+        S = self.n_pairs * n_hyp
+        M = int(self.offsets[-1]) * n_hyp     # (a batch made by select: waits for its sizes)
+        has_cov, has_host = self.mode != capi.MODE_NEC, self.mode == capi.MODE_SYM
+        if _is_torch(q):
+            import torch
+            q = self._dev_tensor(q, "q", (S, 4))
+            t = self._dev_tensor(t, "t", (S, 3))
+            grad_pose = self._dev_tensor(grad_pose, "grad_pose", (S, 6))
+            f64 = dict(dtype=torch.float64, device=q.device)
+            new = lambda *shape: torch.empty(shape, **f64)
+            status = torch.empty((S,), dtype=torch.int32, device=q.device)
+            p = lambda a: None if a is None else a.data_ptr()
+            space, stream = capi.MEM_DEVICE, torch.cuda.current_stream(self.device).cuda_stream
+        else:
+            q = np.ascontiguousarray(q, dtype=np.float64)
+            t = np.ascontiguousarray(t, dtype=np.float64)
+            grad_pose = np.ascontiguousarray(grad_pose, dtype=np.float64)
+            if q.shape != (S, 4) or t.shape != (S, 3) or grad_pose.shape != (S, 6):
+                raise ValueError("q must be [n_pairs*n_hyp,4] (xyzw), t [n_pairs*n_hyp,3], grad_pose [n_pairs*n_hyp,6]")
+            new = lambda *shape: np.empty(shape)
+            status = np.empty(S, dtype=np.int32)
+            p = lambda a: None if a is None else a.ctypes.data
+            space, stream = capi.MEM_HOST, None
+        g1, g2 = new(M, 3), new(M, 3)
+        gc = new(M, 3, 3) if has_cov else None
+        gh = new(M, 3, 3) if has_host else None
+        lam, hess, grad, newton = new(S, 5), new(S, 15), new(S, 5), new(S, 5)
+        capi.check(self._lib.pnec_hip_pose_sensitivity(self._h, p(q), p(t), p(grad_pose), n_hyp, float(reg), flags, p(g1),
+                                                       p(g2), p(gc), p(gh), p(lam), p(hess), p(grad), p(newton), p(status),
+                                                       space, stream))
+        return PoseSensitivity(g1, g2, gc, gh, lam, expand_info(hess), grad, newton, status)
 
     def residuals(self, q, t, reg: float = 1e-13, gate: float = 3.0, n_hyp: int = 1) -> ResidualReport:
         """Whitened residual, propagated variance and chi-square gate verdict (|r| <= gate, in sigmas) of every

@@ -58,6 +58,10 @@ TERM_MAX_ITERATIONS = 3  # PNEC_HIP_TERM_MAX_ITERATIONS
 # pnec_hip_cov_status (pnec_hip_pose_covariance's out_status)
 COV_OK, COV_SINGULAR, COV_NONFINITE = 0, 1, 2
 COV_NAMES = {COV_OK: "ok", COV_SINGULAR: "singular_information", COV_NONFINITE: "non_finite_sums"}
+# pnec_hip_sens_status (pnec_hip_pose_sensitivity's out_status) and its flags
+SENS_OK, SENS_SINGULAR, SENS_NONFINITE = 0, 1, 2
+SENS_NAMES = {SENS_OK: "ok", SENS_SINGULAR: "hessian_not_positive_definite", SENS_NONFINITE: "non_finite_sums"}
+SENS_GAUSS_NEWTON, SENS_ZERO_ON_FAILURE = 1, 2
 NUM_COMPONENTS = {MODE_NEC: 6, MODE_TARGET: 12, MODE_HOST: 12, MODE_SYM: 18}
 
 # every symbol include/pnec_hip.h declares (tests check the library exports all of them)
@@ -93,6 +97,7 @@ SYMBOLS = [
     "pnec_hip_cost_function",
     "pnec_hip_pose_covariance",
     "pnec_hip_residuals",
+    "pnec_hip_pose_sensitivity",
     "pnec_hip_triangulate",
     "pnec_hip_eight_point",
     "pnec_hip_essential_minimal",
@@ -260,6 +265,7 @@ def lib() -> C.CDLL:
     L.pnec_hip_pose_covariance.argtypes = [_vp, _vp, _vp, C.c_int32, C.c_double, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]
     L.pnec_hip_residuals.argtypes = [_vp, _vp, _vp, C.c_int32, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                      C.c_int, _vp]
+    L.pnec_hip_pose_sensitivity.argtypes = [_vp, _vp, _vp, _vp, C.c_int32, C.c_double, C.c_int32] + [_vp] * 9 + [C.c_int, _vp]
     L.pnec_hip_triangulate.argtypes = [_vp, _vp, _vp, C.c_int32, C.c_int32] + [_vp] * 11 + [C.c_int, _vp]
     L.pnec_hip_eight_point.argtypes = [_vp, C.c_int32] + [_vp] * 8 + [C.c_int, _vp]
     L.pnec_hip_essential_minimal.argtypes = [_vp, C.c_int32, C.c_int32] + [_vp] * 10 + [C.c_int, _vp]

@@ -3,6 +3,7 @@
 // tests to exercise the facade without Python.
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -185,9 +186,14 @@ int main(int argc, char **argv) {
   double chi2 = 0.0;
   for (double r : pnec::common::Residuals(ib1, ib2, icovs, sol)) chi2 += r * r;
   const double var_factor = ib1.size() > 5 ? chi2 / (double)(ib1.size() - 5) : std::nan("");
+  // how far the solve stopped from the minimiser of the kept correspondences, in the sensitivity's chart (radians)
+  const pnec::rel_pose_estimation::PoseSensitivityResult sens =
+      pnec::rel_pose_estimation::PoseSensitivity(ib1, ib2, icovs, sol, {1.0, 0.0, 0.0, 0.0, 0.0, 0.0});
+  double newton = 0.0;
+  for (double v : sens.newton) newton = std::fmax(newton, std::fabs(v));
   std::printf("n=%d inliers=%zu rot_err_init_deg=%.6f rot_err_deg=%.6f t_err_deg=%.6f cost=%.6f rot_sigma_deg=%.6f "
-              "t_sigma_deg=%.6f within_3_sigma=%zu variance_factor=%.6f\n", n, inliers.size(), e0, e1, te, cost, rot_sigma,
-              t_sigma, in3, var_factor);
+              "t_sigma_deg=%.6f within_3_sigma=%zu variance_factor=%.6f sens_status=%d newton_step=%.3e\n", n, inliers.size(),
+              e0, e1, te, cost, rot_sigma, t_sigma, in3, var_factor, sens.status, newton);
   if (argc > 3 && std::strcmp(argv[2], "dump") == 0) {
     // everything a checker needs to repeat this call elsewhere: inputs, start pose, result, inliers
     // (text, %.17g: doubles round-trip exactly)

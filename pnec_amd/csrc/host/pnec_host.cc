@@ -1324,6 +1324,34 @@ SE3d RansacEMPoseEstimation(const bearingVectors_t &bvs1, const bearingVectors_t
   return SE3d(Quaterniond(q[3], q[0], q[1], q[2]).toRotationMatrix(), Vector3d(t[0], t[1], t[2]) * singular[0]);
 }
 
+PoseSensitivityResult PoseSensitivity(const bearingVectors_t &bvs_1, const bearingVectors_t &bvs_2,
+                                      const std::vector<Matrix3d> &covs, const SE3d &camera_pose,
+                                      const std::array<double, 6> &grad_pose, double regularization) {
+  if (bvs_1.size() != bvs_2.size() || bvs_1.size() != covs.size())
+    throw std::invalid_argument("bvs_1, bvs_2 and covs differ in size");
+  PoseSensitivityResult out;
+  const double nan = std::nan("");
+  out.lambda.fill(nan);
+  out.newton.fill(nan);
+  if (bvs_1.empty()) return out;   // no information at all: singular
+  out.grad_bvs_1.resize(bvs_1.size());
+  out.grad_bvs_2.resize(bvs_1.size());
+  out.grad_covs.resize(bvs_1.size());
+  const std::vector<int64_t> offsets = {0, (int64_t)bvs_1.size()};
+  Problem prob(optimization::SolverOptions().device, PNEC_HIP_MODE_TARGET, offsets);
+  Check(pnec_hip_problem_fill(prob.p, 0, 1, bvs_1[0].data(), bvs_2[0].data(), covs[0].data(), nullptr, PNEC_HIP_MEM_HOST,
+                              nullptr));
+  const Quaterniond q(camera_pose.rotationMatrix());
+  int32_t status = PNEC_HIP_SENS_SINGULAR;
+  // (symmetric: the ABI's row-major 3x3 is the column-major one)
+  Check(pnec_hip_pose_sensitivity(prob.p, q.coeffs(), camera_pose.translation().data(), grad_pose.data(), 1, regularization,
+                                  0, out.grad_bvs_1[0].data(), out.grad_bvs_2[0].data(), out.grad_covs[0].data(), nullptr,
+                                  out.lambda.data(), nullptr, nullptr, out.newton.data(), &status, PNEC_HIP_MEM_HOST,
+                                  nullptr));
+  out.status = status;
+  return out;
+}
+
 }  // namespace rel_pose_estimation
 
 namespace odometry {

@@ -513,6 +513,22 @@ SE3d RansacEMPoseEstimation(const bearingVectors_t &bvs1, const bearingVectors_t
                             algorithm_t algorithm, std::vector<int> *inliers = nullptr, int max_iterations = 5000,
                             double threshold = 1e-6, uint64_t seed = 1);
 
+// Addition (the reference only dumps training data for learned covariances, src/uncertainty_extraction.cc; the gradient
+// itself it leaves to other code): the gradient of a loss of the refined pose with respect to every bearing vector and
+// covariance -- pnec_hip_pose_sensitivity for one pair of the PNEC residual (target-frame covariances), include/pnec_hip.h
+// has the definitions.  grad_pose = (dL/d omega [3], dL/d t [3]) at camera_pose, omega the rotation vector of a LEFT
+// perturbation.  status is a pnec_hip_sens_status: when it is not PNEC_HIP_SENS_OK (fewer than 5 correspondences, or
+// camera_pose is not a minimiser: the Hessian there is not positive definite) every gradient is NaN.
+struct PoseSensitivityResult {
+  std::vector<Vector3d> grad_bvs_1, grad_bvs_2;
+  std::vector<Matrix3d> grad_covs;    // symmetric: dL = sum_jk G_jk dS_jk
+  std::array<double, 5> lambda{}, newton{};   // in the chart (tau_1, tau_2, omega); newton: the step to the minimiser
+  int status = PNEC_HIP_SENS_SINGULAR;
+};
+PoseSensitivityResult PoseSensitivity(const bearingVectors_t &bvs_1, const bearingVectors_t &bvs_2,
+                                      const std::vector<Matrix3d> &covs, const SE3d &camera_pose,
+                                      const std::array<double, 6> &grad_pose, double regularization = 1e-13);
+
 }  // namespace rel_pose_estimation
 
 namespace odometry {

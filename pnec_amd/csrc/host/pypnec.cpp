@@ -216,6 +216,30 @@ py::array_t<double> pose_covariance(arr bvs1, arr bvs2, arr covs, arr pose, doub
   return out;
 }
 
+// (grad_bvs1 [N,3], grad_bvs2 [N,3], grad_covs [N,3,3], lambda [5], newton [5], status) at `pose`
+py::tuple pose_sensitivity(arr bvs1, arr bvs2, arr covs, arr pose, arr grad_pose, double regularization) {
+  if (grad_pose.ndim() != 1 || grad_pose.shape(0) != 6) throw std::invalid_argument("grad_pose must be a 6-vector");
+  std::array<double, 6> gp;
+  for (int i = 0; i < 6; ++i) gp[i] = grad_pose.unchecked<1>()(i);
+  const pnec::rel_pose_estimation::PoseSensitivityResult r = pnec::rel_pose_estimation::PoseSensitivity(
+      ToBearings(bvs1, "bvs_1"), ToBearings(bvs2, "bvs_2"), ToCovariances(covs, "covs"), ToPose(pose), gp, regularization);
+  const py::ssize_t n = (py::ssize_t)r.grad_bvs_1.size();
+  py::array_t<double> g1({n, (py::ssize_t)3}), g2({n, (py::ssize_t)3}), gc({n, (py::ssize_t)3, (py::ssize_t)3}), lam(5), xn(5);
+  auto o1 = g1.mutable_unchecked<2>(), o2 = g2.mutable_unchecked<2>();
+  auto oc = gc.mutable_unchecked<3>();
+  for (py::ssize_t i = 0; i < n; ++i)
+    for (int j = 0; j < 3; ++j) {
+      o1(i, j) = r.grad_bvs_1[i][j];
+      o2(i, j) = r.grad_bvs_2[i][j];
+      for (int k = 0; k < 3; ++k) oc(i, j, k) = r.grad_covs[i](j, k);
+    }
+  for (int i = 0; i < 5; ++i) {
+    lam.mutable_unchecked<1>()(i) = r.lambda[i];
+    xn.mutable_unchecked<1>()(i) = r.newton[i];
+  }
+  return py::make_tuple(g1, g2, gc, lam, xn, r.status);
+}
+
 // covs_host (optional): the covariances of frame 1 -> the symmetric residual's two-covariance overloads
 py::array_t<double> residuals(arr bvs1, arr bvs2, arr covs, arr pose, double regularization, py::object covs_host) {
   const std::vector<double> r =
@@ -801,6 +825,11 @@ PYBIND11_MODULE(pypnec, m) {
         py::arg("regularization") = 1e-13,
         "pnec::common::PoseCovariance (addition; device): 6x6 covariance of (omega_xyz [left perturbation, rad], t_xyz "
         "[unit direction]) at `pose` -- include/pnec_hip.h pnec_hip_pose_covariance");
+  m.def("pose_sensitivity", &pose_sensitivity, py::arg("bvs1"), py::arg("bvs2"), py::arg("covs"), py::arg("pose"),
+        py::arg("grad_pose"), py::arg("regularization") = 1e-13,
+        "pnec::rel_pose_estimation::PoseSensitivity (addition; device): (grad_bvs1, grad_bvs2, grad_covs, lambda, newton, "
+        "status), the gradient of a loss of the refined pose with respect to the pair's inputs; grad_pose = (dL/d omega, "
+        "dL/d t) at `pose` -- include/pnec_hip.h pnec_hip_pose_sensitivity");
   m.def("residuals", &residuals, py::arg("bvs1"), py::arg("bvs2"), py::arg("covs"), py::arg("pose"),
         py::arg("regularization") = 1e-13, py::arg("covs_host") = py::none(),
         "pnec::common::Residuals (addition; device): the whitened PNEC residual of every correspondence at `pose` -- "

@@ -23,6 +23,7 @@
 #include "pnec_patch_track.hpp"
 #include "pnec_pose_cov.hpp"
 #include "pnec_residuals.hpp"
+#include "pnec_sensitivity.hpp"
 #include "pnec_eight_point.hpp"
 #include "pnec_essential_minimal.hpp"
 #include "pnec_essential_ransac.hpp"
@@ -1396,6 +1397,61 @@ int pnec_hip_residuals(pnec_hip_problem *p, const double *q, const double *t, in
   // n_max of a batch whose sizes still live on the device (select) is the source's: an upper bound, which is all the
   // block size needs (the wavefronts a pair uses follow from its own count)
   PNEC_HIP_TRY(launch_residuals(p->mode, S, cov_waves(p->n_max), a, stream));
+  return io.finish();
+}
+
+// input gradients of the minimiser at every (pair, pose) slot: pnec_sensitivity.hip
+int pnec_hip_pose_sensitivity(pnec_hip_problem *p, const double *q, const double *t, const double *grad_pose,
+                              int32_t n_hyp, double reg, int32_t flags, double *out_grad_bvs1, double *out_grad_bvs2,
+                              double *out_grad_covs, double *out_grad_covs_host, double *out_lambda,
+                              double *out_hessian, double *out_grad, double *out_newton, int32_t *out_status,
+                              int space, void *stream_) {
+  if (int rc = check_pose_args("pose_sensitivity", p, q, t, n_hyp)) return rc;
+  if (!grad_pose) return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "pose_sensitivity: grad_pose is NULL");
+  if (flags & ~(PNEC_HIP_SENS_GAUSS_NEWTON | PNEC_HIP_SENS_ZERO_ON_FAILURE))
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "pose_sensitivity: unknown bit in flags");
+  if (!out_grad_bvs1 && !out_grad_bvs2 && !out_grad_covs && !out_grad_covs_host && !out_lambda && !out_hessian &&
+      !out_grad && !out_newton && !out_status)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "pose_sensitivity: every output is NULL");
+  if (out_grad_covs && p->mode == PNEC_HIP_MODE_NEC)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "pose_sensitivity: out_grad_covs on a NEC batch (it has no covariances)");
+  if (out_grad_covs_host && p->mode != PNEC_HIP_MODE_SYM)
+    return fail(PNEC_HIP_ERR_INVALID_ARGUMENT, "pose_sensitivity: out_grad_covs_host needs a SYM batch");
+  if (int rc = check_space("pose_sensitivity: ", space)) return rc;
+  int64_t S;
+  if (int rc = pose_slots(p, n_hyp, "poses", &S)) return rc;
+  if (S == 0) return 0;
+  hipStream_t stream = (hipStream_t)stream_;
+  CallArrays io(p, space, stream);
+  SensitivityArgs a;
+  a.data = p->d_data;
+  a.block_offset = p->d_block_offset;
+  a.count = p->d_count;
+  a.offsets = p->d_offsets;
+  a.n_hyp = n_hyp;
+  a.flags = flags;
+  a.reg = reg;
+  // HOST space: the lengths of the caller's arrays are the batch's own totals, so a batch made by select waits for its
+  // sizes here.  (DEVICE space needs no host-side number: the kernel reads the batch's offsets.)
+  if (io.host())
+    if (int rc = materialize(p)) return rc;
+  const int64_t M = p->n_corr * (int64_t)n_hyp;   // rows of a per-correspondence array
+  io.in(a.q, q, 4 * S);
+  io.in(a.t, t, 3 * S);
+  io.in(a.grad_pose, grad_pose, 6 * S);
+  io.out(a.out_lambda, out_lambda, 5 * S);
+  io.out(a.out_hessian, out_hessian, 15 * S);
+  io.out(a.out_grad, out_grad, 5 * S);
+  io.out(a.out_newton, out_newton, 5 * S);
+  io.out(a.out_grad_bvs1, out_grad_bvs1, 3 * M);
+  io.out(a.out_grad_bvs2, out_grad_bvs2, 3 * M);
+  io.out(a.out_grad_covs, out_grad_covs, 9 * M);
+  io.out(a.out_grad_covs_host, out_grad_covs_host, 9 * M);
+  io.out(a.out_status, out_status, S);
+  if (int rc = io.commit()) return rc;
+  // n_max of a batch whose sizes still live on the device (select) is the source's: an upper bound, which is all the
+  // block size needs (the wavefronts a pair uses follow from its own count)
+  PNEC_HIP_TRY(launch_pose_sensitivity(p->mode, S, cov_waves(p->n_max), a, stream));
   return io.finish();
 }
 

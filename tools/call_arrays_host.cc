@@ -245,6 +245,22 @@ void batch_lists(int64_t P, int64_t n_hyp, int64_t n) {
     l.out(l.opt(), S, 4);
   }, 10 * S + 2 * M + (M + 7) / 8, S);
 
+  // (no former formula: the call was written with CallArrays; the total is the sum of its documented array lengths)
+  run(tag("pose_sensitivity", {P, n_hyp, M}), [&](List &l) {
+    l.in(true, 4 * S, 8);
+    l.in(true, 3 * S, 8);
+    l.in(true, 6 * S, 8);          // grad_pose
+    l.out(l.opt(), 5 * S, 8);      // lambda
+    l.out(l.opt(), 15 * S, 8);     // hessian
+    l.out(l.opt(), 5 * S, 8);      // grad
+    l.out(l.opt(), 5 * S, 8);      // newton
+    l.out(l.opt(), 3 * M, 8);      // grad_bvs1
+    l.out(l.opt(), 3 * M, 8);      // grad_bvs2
+    l.out(l.opt(), 9 * M, 8);      // grad_covs
+    l.out(l.opt(), 9 * M, 8);      // grad_covs_host
+    l.out(l.opt(), S, 4);
+  }, 43 * S + 24 * M, S);
+
   run(tag("triangulate", {P, n_hyp, M}), [&](List &l) {
     l.in(true, 4 * S, 8);
     l.in(true, 3 * S, 8);
